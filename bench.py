@@ -6,7 +6,12 @@ frame inputs already resident in HBM.  With --gpus N the rays of the view are sh
 rows, one process per GPU) and the fine RGB tiles are gathered with one RCCL all_gather (strong scaling: the view
 is the unit of work).  Rank 0 prints ONE JSON line.
 
-  python bench.py --gpus 1 --steps 5 --warmup 2
+A plain run sets up, warms up, times --steps steps and prints the headline (rays/s, ms_per_step).  --full adds what takes work of its own:
+the per-source-frame setup time, the roofline of the dominant kernel (HIP events around it in the timed steps), the CPU baseline, the parity
+leg against the oracle with its outlier check, and (--gpus N > 1) the check of the gathered image.  --dump-outputs DIR writes what the last
+timed step computed as DIR/<name>.npy (float32 / float64; the inputs are seeded, so two builds can be compared output for output).
+
+  python bench.py --gpus 1 --steps 5 --warmup 2 [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 """
 import argparse
@@ -79,7 +84,7 @@ def explain_outliers(renderer, weights, fdat, frame, px, S, ref, err):
     thresholds / arg-mins turn that into an O(0.1) change of that sample.  The same pixels are marched again with the intermediates kept and
     compared, sample by sample, with the oracle's: visibility flag (interpolated visibility >= 0.1), inside flag (sign of the mesh distance),
     validity mask, a per-sample network output that jumps by more than 1e-3 (nearest vertex / closest face / mask-tap decisions), a fine sample
-    that sits elsewhere (importance sampling's cdf bin, src/model.py:1460).  Checked on every run, not just explained."""
+    that sits elsewhere (importance sampling's cdf bin, src/model.py:1460).  Checked on every --full run, not just explained."""
     o = renderer.render_pass(weights, fdat, frame["cam_tar"], frame["bounds"], 0, 0, 1, px.shape[0], 1, S, S, pixels=px, debug=True, reuse_coarse=False)
     R = px.shape[0]
     bad = (err.max(1)[0] > 1e-4).nonzero().view(-1)
@@ -104,6 +109,43 @@ def explain_outliers(renderer, weights, fdat, frame, px, S, ref, err):
             "flipped_decisions_by_kind": kinds, "pixels_with_a_flip_among_all": int(any_flip.sum())}
 
 
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SAMPLE_RAYS = 4096  # rays whose per-sample depths are written (fixed seed)
+
+
+def dump_outputs(path, image, out):
+    """What the last timed step computed: `image` (the step's result, the fine RGB view (H, W, 3)) and the flat per-ray tensors render_pass
+    returned.  The per-sample depths (z, z_new, z_fine: tens of MB) are written for a fixed, seeded sample of the rays (sample_rays.npy); a
+    per-ray array goes at the same sample only if writing it whole would pass DUMP_MAX_BYTES.  Integer / byte outputs as float64 / float32."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    R = out["color_fine"].shape[0]
+    g = torch.Generator().manual_seed(0)
+    rays = torch.randperm(R, generator=g)[:min(R, DUMP_SAMPLE_RAYS)].sort()[0]
+    arrays = {"image": image, "sample_rays": rays}
+    for k in ("color", "depth", "alpha", "color_fine", "depth_fine", "alpha_fine", "sdf", "index", "hit", "rays_d", "cam_pos"):
+        arrays[k] = out[k]
+    for k in ("z", "z_new", "z_fine"):
+        if out.get(k) is not None:
+            arrays[k] = out[k][rays.to(out[k].device)]
+    for k, v in arrays.items():
+        v = v.detach().cpu()
+        arrays[k] = v.double() if v.dtype in (torch.int64, torch.int32, torch.float64) else v.float()
+    total = sum(v.numel() * v.element_size() for v in arrays.values())
+    for k, v in arrays.items():  # too large to write whole: per-ray arrays at the sampled rays
+        if total > DUMP_MAX_BYTES and k not in ("image", "sample_rays", "cam_pos") and v.shape[0] == R:
+            total -= v.numel() * v.element_size()
+            arrays[k] = v[rays]
+            total += arrays[k].numel() * arrays[k].element_size()
+    if total > DUMP_MAX_BYTES:  # (only at very large views) the image at a seeded sample of its pixels as well
+        pix = arrays["image"].reshape(-1, arrays["image"].shape[-1])
+        arrays["image_pixels"] = torch.randperm(pix.shape[0], generator=g)[:DUMP_SAMPLE_RAYS].sort()[0]
+        arrays["image"] = pix[arrays["image_pixels"]]
+        arrays["image_pixels"] = arrays["image_pixels"].double()
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), v.numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -115,8 +157,13 @@ def main():
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for --gpus > 1 (nccl = RCCL; gloo only for single-GPU rehearsals)")
     ap.add_argument("--precision", choices=["fp32", "bf16x3"], default=DEFAULT_PRECISION,
                     help="arithmetic of the per-sample dense layers: fp32 MFMA, or bf16 MFMA on split (hi + lo) operands with fp32 accumulate")
-    ap.add_argument("--cpu-rays-side", type=int, default=64, help="cpu_baseline sample: side of the strided ray grid (0 = skip)")
+    ap.add_argument("--cpu-rays-side", type=int, default=64, help="--full: cpu_baseline sample: side of the strided ray grid (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the per-source-frame setup time, roofline, CPU baseline, parity vs the oracle and (--gpus N > 1) the gathered-image check")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -150,13 +197,14 @@ def main():
     # Per-source-frame setup (vertex tables, TexVisFusion's global vertex feature, visibility raster, mesh clusters): reported beside the step,
     # outside `value` -- in a data set where every target view has its own source frame (BASELINE config 2) a view costs step + this.
     torch.cuda.synchronize()
-    fs = []
-    for _ in range(3):
-        t0 = time.perf_counter()
-        frame_setup()
-        torch.cuda.synchronize()
-        fs.append((time.perf_counter() - t0) * 1e3)  # wall: includes the host-side table building between the launches
-    frame_setup_ms = min(fs)
+    if args.full:
+        fs = []
+        for _ in range(3):
+            t0 = time.perf_counter()
+            frame_setup()
+            torch.cuda.synchronize()
+            fs.append((time.perf_counter() - t0) * 1e3)  # wall: includes the host-side table building between the launches
+        frame_setup_ms = min(fs)
     weights = renderer.PackedWeights(sd, mode=args.precision)
     bf = args.precision == "bf16x3"
     peak = PEAK_BF16_MFMA_TFLOPS if bf else PEAK_F32_MFMA_TFLOPS
@@ -175,8 +223,8 @@ def main():
                 parts = [torch.empty_like(tile, device="cpu") for _ in range(world)]
                 dist.all_gather(parts, tile.cpu())
                 full = torch.cat(parts, 0).to(tile.device)
-            return full
-        return tile
+            return full, out
+        return tile, out
 
     def barrier():
         if world > 1:
@@ -186,56 +234,66 @@ def main():
     for _ in range(args.warmup):
         step()
     barrier()
-    short0 = weights.short_groups()
+    short0 = weights.short_groups() if args.full else None
+    record = events if args.full else None  # HIP events around the dominant kernel: the roofline's figures
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        img = step(events)
+    for i in range(args.steps):
+        img, out = step(record)
+        if i < args.steps - 1:
+            out = None  # only the last step's outputs are held (--dump-outputs): a step allocates beside the same live tensors as before
     barrier()
     dt = time.perf_counter() - t0
     t = torch.tensor([dt], device="cuda" if args.backend == "nccl" else "cpu", dtype=torch.float64)
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     dt = float(t.item())
+    if args.dump_outputs and rank == 0:
+        from vanerf_amd.parallel import deinterleave
+        dump_outputs(args.dump_outputs, deinterleave(img, H, W, world), out)
+    del out
 
-    # dominant kernel: query_kernel, two launches per step (R*S coarse samples, R*S new importance samples).
-    # Algorithmic FLOPs of a launch = 287 544 per sample, except that a 32-sample group whose samples ALL miss the source view
-    # needs only the colour branch (51 840 FLOP per sample): the kernel counts those groups and they are priced at that figure,
-    # so skipped work never inflates `achieved`.
-    k_ms = [e0.elapsed_time(e1) for e0, e1, _ in events]
-    k_samples = [n for _, _, n in events]
-    kern_s = sum(k_ms) / 1e3
-    short_samples = 32 * (weights.short_groups() - short0)
-    flops = (sum(k_samples) - short_samples) * FLOP_PER_SAMPLE + short_samples * (FLOP_PER_INVALID_SAMPLE_BF16X3 if bf else FLOP_PER_INVALID_SAMPLE)
-    achieved = flops / kern_s / 1e12
-    # HBM bytes per launch.  NOT measured in this run (counters need a rocprofv3 --pmc pass of their own): a static figure from the committed
-    # PMC passes of this kernel, scaled by samples per launch; FETCH_SIZE doubled per MI355X_MICROARCH.md (gfx950 tallies 128-B requests at 64 B).
-    traffic, traffic_src = None, None
-    try:
-        pm = json.load(open(os.path.join(REPO, "profiles", "r03_query_kernel_traffic.json")))
-        per = pm["per_kernel"]["query_kernel<1>" if bf else "query_kernel<0>"]
-        traffic = (2.0 * per["fetch_kb"] + per["write_kb"]) * 1024.0 / pm["samples"] * (sum(k_samples) / len(events))
-        traffic_src = "static: 2 x FETCH_SIZE + WRITE_SIZE of profiles/r03_query_kernel_traffic.json (rocprofv3 --pmc, one counter per pass), not measured in this run"
-    except (OSError, KeyError, ValueError):
-        pass
     rays_total = H * W
     result = {
         "metric": "rendered rays/sec (64 samples/ray) + PSNR vs ref, 512x334 view", "value": rays_total * args.steps / dt, "unit": "rays/s",
         "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * dt / args.steps,
         "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
         "dtype": "bf16x3 (bf16 MFMA on hi+lo split operands, f32 accumulate; per-sample outputs within 3.3e-5 of the f32 kernel)" if bf else "f32", "data": "synthetic",
-        "frame_setup_ms": frame_setup_ms, "ms_per_view_incl_frame": 1e3 * dt / args.steps + frame_setup_ms,
-        "config": {"workload": f"configs/vanerf.json eval view {H}x{W}, {S} coarse + {S} importance samples/ray, "
-                               "two-hand mesh 1558 verts / 3108 faces, 1 source view 256x256, random trained-like weights",
-                   "network_evaluations_per_ray": {"reference": 3 * S, "executed": 2 * S,
-                                                   "note": "fine composite re-uses the coarse evaluations (bit-identical, tests/test_hip_parity.py)"},
-                   "rays": rays_total, "parallelism": f"rays{world}" if world > 1 else "single"},
-        "roofline": {"bound": "mfma", "achieved": achieved, "peak": peak, "unit": "TFLOP/s", "frac": achieved / peak,
-                     "traffic": traffic, "traffic_unit": "HBM bytes per launch", "traffic_source": traffic_src, "kernel": "query_kernel<1> (v_mfma_f32_32x32x16_bf16, 3 MFMA FLOPs executed per algorithmic FLOP)" if bf else "query_kernel<0> (v_mfma_f32_32x32x2_f32)", "launches": len(events),
-                     "avg_launch_ms": statistics.mean(k_ms), "kernel_ms_per_step": sum(k_ms) / args.steps,
-                     "flop_per_launch_avg": flops / len(events), "samples_per_launch_avg": sum(k_samples) / len(events),
-                     "all_invalid_group_fraction": short_samples / max(1, sum(k_samples))},
     }
-    if rank == 0 and world == 1 and args.cpu_rays_side > 0:
+    if args.full:
+        result.update({"frame_setup_ms": frame_setup_ms, "ms_per_view_incl_frame": 1e3 * dt / args.steps + frame_setup_ms})
+    result["config"] = {"workload": f"configs/vanerf.json eval view {H}x{W}, {S} coarse + {S} importance samples/ray, "
+                                    "two-hand mesh 1558 verts / 3108 faces, 1 source view 256x256, random trained-like weights",
+                        "network_evaluations_per_ray": {"reference": 3 * S, "executed": 2 * S,
+                                                        "note": "fine composite re-uses the coarse evaluations (bit-identical, tests/test_hip_parity.py)"},
+                        "rays": rays_total, "parallelism": f"rays{world}" if world > 1 else "single"}
+
+    if args.full:
+        # dominant kernel: query_kernel, two launches per step (R*S coarse samples, R*S new importance samples).
+        # Algorithmic FLOPs of a launch = 287 544 per sample, except that a 32-sample group whose samples ALL miss the source view
+        # needs only the colour branch (51 840 FLOP per sample): the kernel counts those groups and they are priced at that figure,
+        # so skipped work never inflates `achieved`.
+        k_ms = [e0.elapsed_time(e1) for e0, e1, _ in events]
+        k_samples = [n for _, _, n in events]
+        kern_s = sum(k_ms) / 1e3
+        short_samples = 32 * (weights.short_groups() - short0)
+        flops = (sum(k_samples) - short_samples) * FLOP_PER_SAMPLE + short_samples * (FLOP_PER_INVALID_SAMPLE_BF16X3 if bf else FLOP_PER_INVALID_SAMPLE)
+        achieved = flops / kern_s / 1e12
+        # HBM bytes per launch.  NOT measured in this run (counters need a rocprofv3 --pmc pass of their own): a static figure from the committed
+        # PMC passes of this kernel, scaled by samples per launch; FETCH_SIZE doubled per MI355X_MICROARCH.md (gfx950 tallies 128-B requests at 64 B).
+        traffic, traffic_src = None, None
+        try:
+            pm = json.load(open(os.path.join(REPO, "profiles", "r03_query_kernel_traffic.json")))
+            per = pm["per_kernel"]["query_kernel<1>" if bf else "query_kernel<0>"]
+            traffic = (2.0 * per["fetch_kb"] + per["write_kb"]) * 1024.0 / pm["samples"] * (sum(k_samples) / len(events))
+            traffic_src = "static: 2 x FETCH_SIZE + WRITE_SIZE of profiles/r03_query_kernel_traffic.json (rocprofv3 --pmc, one counter per pass), not measured in this run"
+        except (OSError, KeyError, ValueError):
+            pass
+        result["roofline"] = {"bound": "mfma", "achieved": achieved, "peak": peak, "unit": "TFLOP/s", "frac": achieved / peak,
+                              "traffic": traffic, "traffic_unit": "HBM bytes per launch", "traffic_source": traffic_src, "kernel": "query_kernel<1> (v_mfma_f32_32x32x16_bf16, 3 MFMA FLOPs executed per algorithmic FLOP)" if bf else "query_kernel<0> (v_mfma_f32_32x32x2_f32)", "launches": len(events),
+                              "avg_launch_ms": statistics.mean(k_ms), "kernel_ms_per_step": sum(k_ms) / args.steps,
+                              "flop_per_launch_avg": flops / len(events), "samples_per_launch_avg": sum(k_samples) / len(events),
+                              "all_invalid_group_fraction": short_samples / max(1, sum(k_samples))}
+    if args.full and rank == 0 and world == 1 and args.cpu_rays_side > 0:
         base, ref, grids = cpu_baseline(sd, frame, S, args.cpu_rays_side)
         result["cpu_baseline"] = base
         # PSNR of the rendered view against the CPU oracle on the sampled pixels (src/evaluator.py:16-19)
@@ -257,10 +315,10 @@ def main():
                                  "note": "first three figures: the timed image (HIP ray generator) vs the oracle; *_same_rays: the oracle's rays and depths injected"})
         result["parity"].update(explain_outliers(renderer, weights, fdat, frame, px, S, ref, err))
         result["speedup_vs_cpu"] = result["value"] / base["value"]
-    if world > 1:  # the gathered, de-interleaved image must contain this rank's own rows at their place
+    if args.full and world > 1:  # the gathered, de-interleaved image must contain this rank's own rows at their place
         from vanerf_amd.parallel import deinterleave, rank_rows
         full_img = deinterleave(img, H, W, world)
-        own = step()
+        own = step()[0]
         own = own.view(world, rows[2], W, 3)[rank]
         rr = rank_rows(H, world, rank)
         keep = rr < H  # (a height that is not a multiple of 8 * world is padded below the image)

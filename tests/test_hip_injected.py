@@ -239,7 +239,7 @@ def test_model_training_pass_and_gt_gathers_vs_reference(golden, hot_weights):
 def test_every_outlier_of_the_uninjected_image_has_a_flipped_decision(R, sd_full, precision):
     """The shipped path (HIP ray generator, no injection) against the oracle on 40 x 40 strided rays of the 512x334 benchmark view, 64 + 64
     samples: whatever pixel exceeds 1e-4 must show a flipped discrete decision at one of its samples -- visibility flag, inside flag,
-    validity, a per-sample output jump, a fine sample in another cdf bin (bench.py: explain_outliers, which runs in every bench)."""
+    validity, a per-sample output jump, a fine sample in another cdf bin (bench.py: explain_outliers, which runs in every bench --full)."""
     import bench
     frame = synth.make_frame(seed=11, tar_h=512, tar_w=334, orbit_deg=15.0)
     fd = synth.to_device(frame, "cuda")
