@@ -125,19 +125,38 @@ def _softplus100(x):
     return F.softplus(x, beta=100, threshold=20)  # src/utils.py:656
 
 
-def _wn_linear(sd, prefix, x):
+def _record(rec, name, x, y):
+    """Hook of the per-sample layers: rec["layers"][name] = (input, output before the activation) when a record dict is given.
+    `name` is the layer's parameter key as in vanerf_amd.hip_backward.LAYER_PARAMS.  Returns y."""
+    if rec is not None:
+        rec.setdefault("layers", {})[name] = (x, y)
+    return y
+
+
+def _gathered(rec, name, x):
+    """Hook of the gathered per-sample inputs (the tensors whose gradients the fused backward spills as IG): recorded in
+    rec["gathered"][name]; rec["shift"][name], if present, is added first (a zero tensor there makes the input a gradcheck variable)."""
+    if rec is None:
+        return x
+    if name in rec.get("shift", {}):
+        x = x + rec["shift"][name]
+    rec.setdefault("gathered", {})[name] = x
+    return x
+
+
+def _wn_linear(sd, prefix, x, rec=None):
     """weight-normed Linear (src/utils.py:670-685): W = g * v / ||v||_row."""
     if prefix + ".weight_v" in sd:
         v, g = sd[prefix + ".weight_v"], sd[prefix + ".weight_g"]
         W = v * (g / v.norm(2, dim=1, keepdim=True))
     else:
         W = sd[prefix + ".weight"]
-    return F.linear(x, W, sd[prefix + ".bias"])
+    return _record(rec, prefix, x, F.linear(x, W, sd[prefix + ".bias"]))
 
 
-def _conv1(sd, key, x):
+def _conv1(sd, key, x, rec=None):
     """bias-free Conv1d(k=1) on (B,N,C) tensors."""
-    return F.linear(x, sd[key][:, :, 0])
+    return _record(rec, key, x, F.linear(x, sd[key][:, :, 0]))
 
 
 def knn_vis(query, vert, vert_feat, vert_vis):
@@ -150,24 +169,25 @@ def knn_vis(query, vert, vert_feat, vert_vis):
     return feat_knn, feat_knn_toh, vert_vis[:, idx], vis_toh[:, idx], idx
 
 
-def geo_vis_fusion(sd, vert_xy, fg, feat_sampled, vert, v, vert_vis, query_vis, query_sdf, pre="geo_vis_fusion."):
-    """GeoVisFusion.forward (src/networks.py:75-106).  feat_sampled: [(B,1,N,64),(B,1,N,8)] -> same shapes."""
+def geo_vis_fusion(sd, vert_xy, fg, feat_sampled, vert, v, vert_vis, query_vis, query_sdf, pre="geo_vis_fusion.", rec=None):
+    """GeoVisFusion.forward (src/networks.py:75-106).  feat_sampled: [(B,1,N,64),(B,1,N,8)] -> same shapes.  rec: see query()."""
     B = vert_xy.shape[0]
     out = []
     for i, (at, ated) in enumerate((("fconv_at", "fconv_ated"), ("fconv_at1", "fconv_ated1"))):
         vfeat = feat_sample(fg[i], vert_xy)
         knn, toh, vis_th, vis_toh, _ = knn_vis(v, vert, vfeat, vert_vis)
-        pix = feat_sampled[i].squeeze(1)
+        knn, toh = _gathered(rec, f"nn{i}", knn), _gathered(rec, f"tw{i}", toh)
+        pix = _gathered(rec, f"pix{i}", feat_sampled[i].squeeze(1))
         tail = [query_sdf, query_vis, vis_th, vis_toh]
-        f = torch.cat([pix, knn, toh] + tail, 2).float()
-        a = torch.sigmoid(_conv1(sd, pre + at + ".2.weight", torch.relu(_conv1(sd, pre + at + ".0.weight", f))))
-        g = torch.cat([pix * a[:, :, 0:1], knn * a[:, :, 1:2], toh * a[:, :, 2:3]] + tail, 2).float()
-        h = _conv1(sd, pre + ated + ".2.weight", torch.relu(_conv1(sd, pre + ated + ".0.weight", g)))
+        f = torch.cat([pix, knn, toh] + tail, 2).to(pix.dtype)  # (the visibility flags are int: the features' dtype, fp32 or fp64)
+        a = torch.sigmoid(_conv1(sd, pre + at + ".2.weight", torch.relu(_conv1(sd, pre + at + ".0.weight", f, rec)), rec))
+        g = torch.cat([pix * a[:, :, 0:1], knn * a[:, :, 1:2], toh * a[:, :, 2:3]] + tail, 2).to(pix.dtype)
+        h = _conv1(sd, pre + ated + ".2.weight", torch.relu(_conv1(sd, pre + ated + ".0.weight", g, rec)), rec)
         out.append(h.view(B, 1, *h.shape[-2:]))
     return out
 
 
-def mlp_geo(sd, y, f, a, w, pre="mlp_geo."):
+def mlp_geo(sd, y, f, a, w, pre="mlp_geo.", rec=None):
     """MLPUNetFusion.forward (src/utils.py:633-649) with MLPUNet (822-852), PoolModule (744-779), pool_ops (854-880),
     MLP (709-719) for the shipped config: n_dims1 [294,128,128,120,64], skip_layers [0,2], pool mean+var, n_dims2 [128,64,64,2]."""
     x = y
@@ -176,7 +196,7 @@ def mlp_geo(sd, y, f, a, w, pre="mlp_geo."):
     for i in range(n1):
         if i in skip:
             x = torch.cat([x, f[skip[i]]], -1)
-        x = _wn_linear(sd, f"{pre}layers1.layers.{i}.linear", x)
+        x = _wn_linear(sd, f"{pre}layers1.layers.{i}.linear", x, rec)
         if i != n1 - 1:
             x = _softplus100(x)
     x_view = x
@@ -187,7 +207,7 @@ def mlp_geo(sd, y, f, a, w, pre="mlp_geo."):
     valid = a_sum > 0.0
     x = x_pool
     for i in range(3):
-        x = _wn_linear(sd, f"{pre}layers2.layers.{i}.linear", x)
+        x = _wn_linear(sd, f"{pre}layers2.layers.{i}.linear", x, rec)
         if i != 2:
             x = _softplus100(x)
     return x, valid, x_view, x_pool
@@ -218,18 +238,19 @@ def tex_vertex_features(sd, vert_xy, ft1, img, pre="tex_vis_fusion."):
     return torch.cat([vert_feat, x], 2)
 
 
-def tex_vis_fusion(sd, vert_feat29, ft_xy, vert, v, vert_vis, query_vis, img_xy, latent24, pre="tex_vis_fusion."):
-    """Per-sample part of TexVisFusion.forward (src/networks.py:281-293) -> (B,N,40)."""
+def tex_vis_fusion(sd, vert_feat29, ft_xy, vert, v, vert_vis, query_vis, img_xy, latent24, pre="tex_vis_fusion.", rec=None):
+    """Per-sample part of TexVisFusion.forward (src/networks.py:281-293) -> (B,N,40).  rec: see query()."""
     knn, toh, vis_th, vis_toh, _ = knn_vis(v, vert, vert_feat29, vert_vis)
+    knn, toh, ft_xy = _gathered(rec, "row_nn", knn), _gathered(rec, "row_tw", toh), _gathered(rec, "tex_xy", ft_xy)
     knn_gf, toh_gf = knn[:, :, 11:], toh[:, :, 11:]
     knn, toh = knn[:, :, :11], toh[:, :, :11]
     q = torch.cat([img_xy, ft_xy], 2)
     tail = [query_vis, vis_th, vis_toh]
-    y = torch.cat([q, knn, toh, knn_gf, toh_gf, latent24] + tail, 2).float()
-    a = torch.sigmoid(_conv1(sd, pre + "fconv_at.2.weight", torch.relu(_conv1(sd, pre + "fconv_at.0.weight", y))))
+    y = torch.cat([q, knn, toh, knn_gf, toh_gf, latent24] + tail, 2).to(q.dtype)
+    a = torch.sigmoid(_conv1(sd, pre + "fconv_at.2.weight", torch.relu(_conv1(sd, pre + "fconv_at.0.weight", y, rec)), rec))
     g = torch.cat([q * a[:, :, 0:1], knn * a[:, :, 1:2], toh * a[:, :, 2:3], knn_gf * a[:, :, 3:4],
                    toh_gf * a[:, :, 4:5], latent24 * a[:, :, 5:6]] + tail, 2)
-    return _conv1(sd, pre + "fconv.2.weight", torch.relu(_conv1(sd, pre + "fconv.0.weight", g)))
+    return _conv1(sd, pre + "fconv.2.weight", torch.relu(_conv1(sd, pre + "fconv.0.weight", g, rec)), rec)
 
 
 def ibr_head(sd, rgb_feats, ray_diffs, proj_mask, pre="mlp_tex."):
@@ -370,7 +391,14 @@ def project_verts(vert, cam):
 def query(sd, pts, cam, targets, feat_geo, feat_tex, vert_vis, query_vis, query_sdf, sp_data, img, view,
           fg_mask, sp_args=None, want=None):
     """VANeRF.query + query_color for n_views == 1 (src/model.py:748-957) -> out (B,N,5) = [sdf_pred, rad, r, g, b], valid (B,N,1).
-    `want`: optional dict that receives named intermediates."""
+    `want`: optional dict that receives named intermediates, and in particular
+      want["layers"][name] = (input, output before the activation) of every per-sample layer, keyed by its parameter name
+        (vanerf_amd.hip_backward.LAYER_PARAMS: the weight key of a Conv1d, the module prefix of a Linear);
+      want["gathered"][name]: the gathered per-sample inputs, named after the fused backward's IG tensors -- pix0 / pix1 (feat_sampled),
+        nn0 / tw0 / nn1 / tw1 (feat_knn / feat_knn_toh of GeoVisFusion's two scales), row_nn / row_tw (TexVisFusion's), tex_xy (ft_xy);
+      want["shift"] (given by the caller): name -> tensor added to that gathered input (see _gathered).
+    Runs in the dtype of its inputs: fp64 weights, frame and features give an fp64 reference (the pi 2^l constants stay fp32-rounded,
+    as in the reference and the kernels; knn1 and the caller's q_sdf / q_vis are the same discrete inputs in both)."""
     sp_args = sp_args or {"sp_level": 3, "scale": 1.0, "sigma": 0.1}
     B, N = pts.shape[:2]
     xy, z = project(pts, cam)
@@ -378,7 +406,7 @@ def query(sd, pts, cam, targets, feat_geo, feat_tex, vert_vis, query_vis, query_
     mask_xy = (xy >= -1.0 - eps) & (xy <= 1.0 + eps)
     out_mask = (mask_xy[..., 0] & mask_xy[..., 1] & (z >= -1.0)[..., 0])[..., None].float()
     out_mask = out_mask.view(-1, 1, *out_mask.shape[1:])  # (B,V=1,N,1)
-    fg = fg_mask.view(-1, 1, *fg_mask.shape[-2:]).float()
+    fg = fg_mask.view(-1, 1, *fg_mask.shape[-2:]).to(xy.dtype)
     fg_xy = feat_sample(fg, xy).view(-1, 1, N, 1)
     out_mask = out_mask * (fg_xy > 0.1).all(1, keepdim=True) * out_mask.bool().all(1, keepdim=True)
     xyz = 0.5 * torch.cat([xy, z], -1) + 0.5
@@ -392,15 +420,16 @@ def query(sd, pts, cam, targets, feat_geo, feat_tex, vert_vis, query_vis, query_
     vert3d = targets["vert_world"]
     vert_xy = project_verts(vert3d, cam)
     vv = vert_vis.type(torch.int)
-    fused = geo_vis_fusion(sd, vert_xy, feat_geo, feat_sampled, vert3d, pts, vv, query_vis, query_sdf.unsqueeze(-1))
-    out, valid, x_view, latent = mlp_geo(sd, y, fused, out_mask, pix_weight)
+    rec = None if want is None else {"layers": {}, "gathered": {}, "shift": want.get("shift", {})}
+    fused = geo_vis_fusion(sd, vert_xy, feat_geo, feat_sampled, vert3d, pts, vv, query_vis, query_sdf.unsqueeze(-1), rec=rec)
+    out, valid, x_view, latent = mlp_geo(sd, y, fused, out_mask, pix_weight, rec=rec)
     # query_color (src/model.py:884-957)
     img_xy = feat_sample(img, xy)
     ft_xy = feat_sample(feat_tex, xy)
-    latent24 = F.linear(latent, sd["ibr_compress_gfeat.weight"], sd["ibr_compress_gfeat.bias"])
+    latent24 = _record(rec, "ibr_compress_gfeat", latent, F.linear(latent, sd["ibr_compress_gfeat.weight"], sd["ibr_compress_gfeat.bias"]))
     vfeat29 = tex_vertex_features(sd, vert_xy, feat_tex, img)
-    rgb_feat = tex_vis_fusion(sd, vfeat29, ft_xy, vert3d, pts, vv, query_vis, img_xy, latent24)
-    cam_pos = torch.inverse(cam["KRT"].float())[:, :3, 3:4]
+    rgb_feat = tex_vis_fusion(sd, vfeat29, ft_xy, vert3d, pts, vv, query_vis, img_xy, latent24, rec=rec)
+    cam_pos = torch.inverse(cam["KRT"].to(pts.dtype))[:, :3, 3:4]
     cam_rays = F.normalize(pts - cam_pos.view(-1, 1, 3), p=2, dim=-1)
     ray_diff = view - cam_rays
     ray_dot = (cam_rays * view).sum(-1, keepdim=True)
@@ -409,7 +438,7 @@ def query(sd, pts, cam, targets, feat_geo, feat_tex, vert_vis, query_vis, query_
     if want is not None:
         want.update(xy=xy, z=z, out_mask=out_mask, pix_weight=pix_weight, y=y, geo_fused0=fused[0], geo_fused1=fused[1],
                     x_view=x_view, latent=latent, latent24=latent24, vert_feat29=vfeat29, rgb_feat=rgb_feat,
-                    ray_diff=ray_diff, vert_xy=vert_xy)
+                    ray_diff=ray_diff, vert_xy=vert_xy, layers=rec["layers"], gathered=rec["gathered"])
     return torch.cat([out, rgb], -1), valid
 
 
