@@ -371,6 +371,21 @@ int vanerf_layer_rows(int layer, int* x_row, int* y_row, int* n_out);
  *     -> near[R], far[R] (1.0 when the ray does not cross the box exactly twice), hit[R] (u8).                               */
 int vanerf_ray_bbox(const float* bounds, const float* orig, const float* dirs, int R, float* near, float* far, uint8_t* hit, void* stream);
 
+/* render_vis (src/render_vis.py:181-226): the mesh rendered in the target camera with the per-vertex visibility as its colour,
+ * Phong-shaded and blended, and the visibility image thresholded from it.  Semantics restated from pytorch3d 0.7.5;
+ * parity against pytorch3d itself is unpinned.
+ *     verts[NV][3] (world, metres), faces[NF][3] int32 (a face with an index outside [0, NV) draws nothing), vert_vis[NV] ({0, 1}),
+ *     R[3][3], T[3]: pytorch3d row-vector convention, Xv = X_world R + T;  focal[2] = (fx, fy), princpt[2] = (px, py): screen space,
+ *         vertex -> (px - fx Xv/Zv, py - fy Yv/Zv); pixel (row r, col c) samples (c + 0.5, r + 0.5).  All four are DEVICE pointers.
+ *     scratch: device memory of at least NV * 16 floats (16-byte aligned): per vertex (u, v, x_ndc, y_ndc), (Xv, Yv, Zv, vert_vis),
+ *         (world xyz, 0), (unit vertex normal, 0) -- written by the vertex pass, read by the raster pass.
+ *     -> rgb[3][H][W] (vis_img_rbg), vis[H][W] (vis_img: 1 where mean(rgb * 255) >= 50, else 0; the background is 1),
+ *        pix_to_face[H][W] int32 (-1: background) and zbuf[H][W] (view depth, -1: background), both may be NULL.
+ *     Two launches on `stream`; no allocation, no host synchronisation.                                                      */
+int vanerf_render_vis(const float* verts, int nv, const int32_t* faces, int nf, const float* vert_vis, const float* R, const float* T,
+                      const float* focal, const float* princpt, int H, int W, float* scratch, int64_t scratch_bytes, float* rgb, float* vis,
+                      int32_t* pix_to_face, float* zbuf, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,6 +20,8 @@ if "--hip_backward_block" in sys.argv:
     cfg["models"]["VANeRF"]["hip_backward_block"] = int(sys.argv[sys.argv.index("--hip_backward_block") + 1])
 if "--graph_encoders" in sys.argv:  # the two image encoders as HIP graphs (forward and backward)
     cfg["models"]["VANeRF"]["graph_encoders"] = True
+if "--render_vis" in sys.argv:  # vis_img_all / vis_img rendered by the HIP rasteriser (vanerf_amd/render_vis.py) instead of zeros
+    cfg["models"]["VANeRF"]["render_vis"] = True
 # --cudnn_benchmark: the reference's trainer runs with `benchmark=True` (train.py:60: PyTorch Lightning sets torch.backends.cudnn.benchmark), i.e. MIOpen
 # searches the convolution algorithms of the two image encoders during the first steps.  Measured: 28.1 / 28.8 ms (min / median) against 28.5 / 29.5 without,
 # for minutes of search at start-up -- not the default here.
@@ -31,6 +33,8 @@ if "--channels_last" in sys.argv:  # experiment: the two image encoders' convolu
         if enc is not None:
             enc.to(memory_format=torch.channels_last)
 frame = synth.to_device(synth.make_frame(seed=3, tar_h=256, tar_w=256), "cuda")
+if "--render_vis" in sys.argv:
+    frame["targets"]["tar_cam"] = synth.p3d_tar_cam(frame["cam_tar"])
 dr = {"img": frame["img_in"], "cam": frame["cam_in"], "cam_tar": frame["cam_tar"], "tar": torch.rand(1, 3, 256, 256, device="cuda"),
       "msk": torch.ones(1, 1, 256, 256, device="cuda")}
 opt = torch.optim.Adam(net.parameters(), lr=1e-5, fused=("--fused_adam" in sys.argv) or None)  # (--fused_adam: one launch per dtype group; default: PyTorch's foreach path)

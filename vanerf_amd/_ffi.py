@@ -118,6 +118,7 @@ _SIGS = {
     "vanerf_scatter_add_taps": (c_int, [_FP, _FP, c_int64, _FP, c_int64, c_int64, c_int, _FP, c_int, c_void_p]),
     "vanerf_ig_tensor": (c_int, [c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
     "vanerf_ray_bbox": (c_int, [POINTER(c_float), POINTER(c_float), _FP, c_int, _FP, _FP, _FP, c_void_p]),
+    "vanerf_render_vis": (c_int, [_FP, c_int, _FP, c_int, _FP, _FP, _FP, _FP, _FP, c_int, c_int, _FP, c_int64, _FP, _FP, _FP, _FP, c_void_p]),
 }
 EXPORTS = tuple(_SIGS)
 

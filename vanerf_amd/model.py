@@ -190,6 +190,9 @@ class VANeRF(nn.Module):
         # identical rays, bit-reproducible; the configuration every published number is measured in) | "fp32" (fp32 MFMA, 2.2x slower);
         # renderer.PRECISIONS; not a reference key
         self.precision = model_cfg.get("mfma_precision", "bf16x3")
+        # render_vis (src/model.py:1373-1389) on the GPU for vis_img_all / vis_img (vanerf_amd/render_vis.py); off: zeros of the reference's
+        # shape, as before the kernel existed.  Not a reference key
+        self.render_vis = bool(model_cfg.get("render_vis", False))
         self._packed = None  # (version key, PackedWeights)
         self._frame_cache = None
         self._encoders_graphed = False
@@ -516,8 +519,16 @@ class VANeRF(nn.Module):
                 g = gather(config["msk"].reshape(1, 1, -1), 1)
                 if g is not None:
                     out["tar_alpha"] = g.float()
-        # render_vis (pytorch3d soft rasteriser, discriminator supervision only) is out of scope: zeros of the reference's shape
-        out["vis_img_all"] = torch.zeros(1, 1, 256, 256, device=dev)
+        if net.render_vis:  # src/model.py:1373-1383: the mesh coloured by vertex visibility, rendered 256x256 in the target camera
+            tc = targets["tar_cam"]
+            f32 = torch.float32
+            with torch.no_grad():
+                _, vis_all = R.render_vis(fd.verts3, fd.faces, fd.vert_vis, tc["tar_R"][0].to(dev, f32).contiguous(),
+                                          tc["tar_T"][0].to(dev, f32).contiguous(), tc["tar_focal"][0].to(dev, f32).contiguous(),
+                                          tc["tar_princpt"][0].to(dev, f32).contiguous(), 256, 256)
+            out["vis_img_all"] = vis_all[None, None]
+        else:  # zeros of the reference's shape
+            out["vis_img_all"] = torch.zeros(1, 1, 256, 256, device=dev)
         for key, t, ch in (("vis_img", out["vis_img_all"], 1), ("input_mask", config["src_foreground_mask"].reshape(1, 1, *config["src_foreground_mask"].shape[-2:]), 1),
                            ("img_in", img_in, 3)):
             g = gather(t, ch)

@@ -366,6 +366,24 @@ def vertex_visibility(vert_xy01, vert_z01, faces_i32, raster=256):
     return vis
 
 
+def render_vis(verts3, faces_i32, vert_vis, R, T, focal, princpt, H=256, W=256, want_raster=False):
+    """render_vis (src/render_vis.py:181-226) through vanerf_render_vis -> rgb (3,H,W), vis (H,W)[, pix_to_face (H,W) int32, zbuf (H,W)].
+    verts3 (NV,3), faces_i32 (NF,3), vert_vis (NV,), R (3,3), T (3,), focal (2,) = (fx, fy), princpt (2,) = (px, py): fp32 / int32 device
+    tensors, the camera in pytorch3d's row-vector convention.  The camera is read on the device: nothing here waits for the GPU."""
+    dev = verts3.device
+    f32 = torch.float32
+    nv = verts3.shape[0]
+    scratch = torch.empty(nv * 16, dtype=f32, device=dev)
+    rgb = torch.empty(3, H, W, dtype=f32, device=dev)
+    vis = torch.empty(H, W, dtype=f32, device=dev)
+    p2f = torch.empty(H, W, dtype=torch.int32, device=dev) if want_raster else None
+    zbuf = torch.empty(H, W, dtype=f32, device=dev) if want_raster else None
+    check(lib.vanerf_render_vis(_ptr(verts3, f32), nv, _ptr(faces_i32, torch.int32), faces_i32.shape[0], _ptr(vert_vis, f32), _ptr(R, f32),
+                                _ptr(T, f32), _ptr(focal, f32), _ptr(princpt, f32), int(H), int(W), _ptr(scratch), scratch.numel() * 4, _ptr(rgb),
+                                _ptr(vis), _ptr(p2f), _ptr(zbuf), _stream()))
+    return (rgb, vis, p2f, zbuf) if want_raster else (rgb, vis)
+
+
 def mesh_query(verts3, faces_i32, vert_vis, pts, want_face=False):
     """cal_vis_sdf_batch (mesh_util.py:498-524) -> sdf (N,), vis (N,) uint8[, closest face (N,) int32]."""
     n = pts.shape[0]

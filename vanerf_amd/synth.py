@@ -148,6 +148,16 @@ def make_frame(seed=0, tar_h=64, tar_w=64, src_hw=256, orbit_deg=8.0, device="cp
     return to_device(frame, device)
 
 
+def p3d_tar_cam(cam_tar):
+    """targets['tar_cam'] in pytorch3d's convention, as the reference's dataset builds it from the OpenCV target camera
+    (src/dataset.py:501-503): tar_R = (F R_cv)^T, tar_T = F t_cv with F = diag(-1, -1, 1); focal and principal point from K.
+    render_vis with this camera registers with cam_tar["KRT"]."""
+    RT, K = cam_tar["RT"], cam_tar["K"]
+    flip = torch.tensor([-1.0, -1.0, 1.0], dtype=RT.dtype, device=RT.device)
+    return {"tar_R": (flip[:, None] * RT[:, :3, :3]).transpose(1, 2).contiguous(), "tar_T": (flip * RT[:, :3, 3]).contiguous(),
+            "tar_focal": torch.stack([K[:, 0, 0], K[:, 1, 1]], 1), "tar_princpt": torch.stack([K[:, 0, 2], K[:, 1, 2]], 1)}
+
+
 def to_tr_batch(frame):
     """The dict VANeRFLightningModule.decode_batch hands to the renderer (reference src/model.py:213-262), filled from a synthetic frame."""
     return {"im": frame["img_in"], "cam": frame["cam_in"], "hand_type": frame["hand_type"], "targets": frame["targets"], "sp_data": frame["sp_data"],
