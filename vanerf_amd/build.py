@@ -16,8 +16,11 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=o
 FILE_FLAGS = {"query_kernel.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-slp-vectorize"],
               "query_backward.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-slp-vectorize"],
               # mesh_query_accel_kernel sits exactly at 128 registers (four waves per SIMD): loop-invariant address arithmetic goes back into the
-              # work loop instead of being parked in scratch (7 spilled VGPRs without the flag; scratch fails the build, _check_no_scratch)
-              "mesh_kernels.hip": ["-mllvm", "-sink-insts-to-avoid-spills"]}
+              # work loop instead of being parked in scratch (7 spilled VGPRs without the flag; scratch fails the build, _check_no_scratch).
+              # No SLP vectoriser here either: a v_pk_mul_f32 / v_pk_add_f32 takes the issue slots of two scalar ops on gfx950
+              # (tools/probe_pk_f32.hip), so its packs save no issue time in this VALU-bound kernel and their operand pairs cost registers
+              # (128 -> 111 VGPRs without it; 1.96 -> 1.79 ms on the benchmark view).
+              "mesh_kernels.hip": ["-mllvm", "-sink-insts-to-avoid-spills", "-fno-slp-vectorize"]}
 
 
 def _stale():
