@@ -16,6 +16,7 @@
  *   - return value: 0 on success, negative on error (message via vanerf_last_error(), thread local);
  *   - B = V = 1 (one target view, one source view): the non-spconv reference path is
  *     structurally single-view (src/networks.py:86,94) and evaluates batch items in Python loops.
+ *     The *_views entry points march several TARGET views of the one source view in one pass.
  */
 #ifndef VANERF_HIP_H
 #define VANERF_HIP_H
@@ -146,8 +147,18 @@ int vanerf_ray_setup_pixels(const int32_t* pixels_xy, int n_rays, int width, con
                             float zfar, const float* bounds, int S, const float* t_lin, const float* jitter, int64_t* index,
                             float* rays_d, float* cam_pos, float* near, float* far, uint8_t* hit, float* z, void* stream);
 
+/* The regular grid (y_block = 1) for n_views target cameras at once: cams[n_views][24] (DEVICE, fp32) = invK_T[9], RT[12], znear, zfar, one pad;
+ * every view has the same grid and width.  Ray v * nx * ny + iy * nx + ix of the outputs is ray (ix, iy) of view v, with the bits
+ * vanerf_ray_setup gives for that camera alone (one ray function behind both); jitter[n_views*nx*ny][S] or NULL; cam_pos is [n_views][4].
+ * n_views * nx * ny * S must stay below 2^31 - 1 (the 32-bit sample index of vanerf_query_order).                                        */
+int vanerf_ray_setup_views(const float* cams, int n_views, int x0, int y0, int step_x, int step_y, int nx, int ny, int width,
+                           const float* bounds, int S, const float* t_lin, const float* jitter, int64_t* index, float* rays_d,
+                           float* cam_pos, float* near, float* far, uint8_t* hit, float* z, void* stream);
+
 /* eval_pts = cam_pos + dir * z (src/model.py:1234-1235).  pts[R*S][3]. */
 int vanerf_sample_points(const float* rays_d, const float* cam_pos, const float* z, int R, int S, float* pts, void* stream);
+/* ... with one origin per view: ray r starts at cam_pos[r / rays_per_view][4] (the table vanerf_ray_setup_views writes); R is a whole number of views */
+int vanerf_sample_points_views(const float* rays_d, const float* cam_pos, const float* z, int R, int rays_per_view, int S, float* pts, void* stream);
 
 /* a6  get_visibility (mesh_util.py:284-318): vert_xy01[NV][2], vert_z01[NV], faces[NF][3] int32 -> vert_vis[NV];
  *     pix_to_face[S*S] int32 is scratch (may be NULL only if `scratch` given).                                          */
@@ -318,6 +329,29 @@ int64_t vanerf_render_pass_scratch(int n_rays, int Sc, int Sf, int fine, int reu
 int vanerf_render_pass(const VanerfWeights* w, const VanerfFrame* frame, const VanerfMeshAccel* accel, const float* verts, int nv,
                        const int32_t* faces, int nf, const VanerfPassDesc* desc, const VanerfPassOut* out, void* scratch, int64_t scratch_bytes,
                        void* stream);
+
+/* One pass over n_views target views of the same source frame that share a pixel grid (the frames of an orbit, the views of a validation step):
+ * the kernels of vanerf_render_pass once over n_views * nx * ny rays instead of n_views times over nx * ny.  Behind the ray setup nothing
+ * depends on the camera but the ray origin, so view v's slice of every output holds the bits vanerf_render_pass gives for that camera alone.
+ * Evaluation only: no pixel list, no row blocks, no per-sample noise (training patches and multi-GPU ray shards keep vanerf_render_pass).    */
+typedef struct {
+    int n_views;
+    int x0, y0, step_x, step_y, nx, ny; /* x = x0 + ix*step_x, y = y0 + iy*step_y, the same for every view */
+    int width;                 /* target image width (pixel index = x + y * width) */
+    const float* cams;         /* [n_views][24] DEVICE table: invK_T[9], RT[12], znear, zfar, pad (as vanerf_ray_setup_views) */
+    float bounds[6];
+    int Sc, Sf, fine, reuse_coarse; /* as VanerfPassDesc */
+    const float* t_lin_c;      /* th.linspace(0, 1, Sc) (device) */
+    const float* t_lin_f;      /* th.linspace(0, 1, Sf) (device); used when u == NULL */
+    const float* jitter;       /* [n_views*nx*ny][Sc] or NULL */
+    const float* u;            /* [n_views*nx*ny][Sf] or NULL */
+} VanerfViewsDesc;
+
+/* out: VanerfPassOut with R = n_views * nx * ny (view-major).  The largest march, n_views * nx * ny * (Sf, Sc or Sc + Sf), must stay below 2^31 - 1. */
+int64_t vanerf_render_pass_views_scratch(int n_views, int rays_per_view, int Sc, int Sf, int fine, int reuse_coarse); /* 0: bad arguments */
+int vanerf_render_pass_views(const VanerfWeights* w, const VanerfFrame* frame, const VanerfMeshAccel* accel, const float* verts, int nv,
+                             const int32_t* faces, int nf, const VanerfViewsDesc* desc, const VanerfPassOut* out, void* scratch,
+                             int64_t scratch_bytes, void* stream);
 
 /* Training step, backward of the row gathers (bilinear taps of feat_sample, src/utils.py:136-151; nearest / twin vertex rows of KNN_vis,
  * src/networks.py:27-33):  table[idx[i]][0..C) += w[i] * g[i][0..C)  for i < n  (w may be NULL = 1; rows outside [0, R) are ignored).

@@ -62,6 +62,14 @@ class VanerfPassDesc(Structure):
     ]
 
 
+class VanerfViewsDesc(Structure):
+    _fields_ = [
+        ("n_views", c_int), ("x0", c_int), ("y0", c_int), ("step_x", c_int), ("step_y", c_int), ("nx", c_int), ("ny", c_int), ("width", c_int),
+        ("cams", _FP), ("bounds", c_float * 6), ("Sc", c_int), ("Sf", c_int), ("fine", c_int), ("reuse_coarse", c_int),
+        ("t_lin_c", _FP), ("t_lin_f", _FP), ("jitter", _FP), ("u", _FP),
+    ]
+
+
 class VanerfPassOut(Structure):
     _fields_ = [("index", _FP), ("hit", _FP), ("z", _FP), ("color", _FP), ("depth", _FP), ("alpha", _FP), ("color_fine", _FP), ("depth_fine", _FP),
                 ("alpha_fine", _FP), ("sdf", _FP), ("z_fine", _FP)]
@@ -86,7 +94,10 @@ _SIGS = {
                                         _FP, _FP, _FP, _FP, _FP, _FP, _FP, c_void_p]),
     "vanerf_ray_setup_blocks": (c_int, [_FP, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_float), POINTER(c_float), c_float, c_float,
                                         POINTER(c_float), c_int, _FP, _FP, _FP, _FP, _FP, _FP, _FP, _FP, _FP, c_void_p]),
+    "vanerf_ray_setup_views": (c_int, [_FP, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_float), c_int, _FP, _FP, _FP, _FP, _FP, _FP,
+                                       _FP, _FP, _FP, c_void_p]),
     "vanerf_sample_points": (c_int, [_FP, _FP, _FP, c_int, c_int, _FP, c_void_p]),
+    "vanerf_sample_points_views": (c_int, [_FP, _FP, _FP, c_int, c_int, c_int, _FP, c_void_p]),
     "vanerf_vertex_visibility": (c_int, [_FP, _FP, c_int, _FP, c_int, c_int, _FP, _FP, c_void_p]),
     "vanerf_mesh_query": (c_int, [_FP, c_int, _FP, c_int, _FP, _FP, c_int64, _FP, _FP, _FP, c_void_p]),
     "vanerf_mesh_query_accel": (c_int, [POINTER(VanerfMeshAccel), _FP, c_int, _FP, c_int, _FP, _FP, c_int64, _FP, _FP, _FP, _FP, c_int, c_int, c_int,
@@ -112,6 +123,9 @@ _SIGS = {
     "vanerf_render_pass_scratch": (c_int64, [c_int, c_int, c_int, c_int, c_int]),
     "vanerf_render_pass": (c_int, [c_void_p, POINTER(VanerfFrame), POINTER(VanerfMeshAccel), _FP, c_int, _FP, c_int, POINTER(VanerfPassDesc),
                                    POINTER(VanerfPassOut), _FP, c_int64, c_void_p]),
+    "vanerf_render_pass_views_scratch": (c_int64, [c_int, c_int, c_int, c_int, c_int, c_int]),
+    "vanerf_render_pass_views": (c_int, [c_void_p, POINTER(VanerfFrame), POINTER(VanerfMeshAccel), _FP, c_int, _FP, c_int, POINTER(VanerfViewsDesc),
+                                         POINTER(VanerfPassOut), _FP, c_int64, c_void_p]),
     "vanerf_scatter_add_rows": (c_int, [_FP, _FP, _FP, c_int64, c_int64, c_int, _FP, c_int, c_void_p]),
     "vanerf_bilinear_taps": (c_int, [_FP, c_int64, c_int, c_int, _FP, _FP, c_void_p]),
     "vanerf_scatter_add_rows2": (c_int, [_FP, _FP, _FP, _FP, _FP, _FP, c_int64, c_int64, c_int, _FP, c_int, c_void_p]),

@@ -37,14 +37,14 @@ struct Layout {
 
 // reuse: 0 the fine march evaluates all Sc + Sf samples; 1 it evaluates the Sf new ones and the composite gathers the coarse evaluations;
 // 2 the same under per-sample noise: raw network outputs once per point, eval_func once per set of draws (vanerf_eval_func)
-Layout carve(void* base, int R, int Sc, int Sf, int fine, int reuse)
+Layout carve(void* base, int R, int Sc, int Sf, int fine, int reuse, int n_views = 1)
 {
     Carver c(base);
     Layout L{};
     const int64_t nc = (int64_t)R * Sc, nf = fine ? (int64_t)R * (reuse ? Sf : Sc + Sf) : 0, nmax = nc > nf ? nc : nf;
     L.queue_words = c.take<unsigned long long>(4);
     L.rays_d = c.take<float>(3LL * R);
-    L.cam_pos = c.take<float>(4);
+    L.cam_pos = c.take<float>(4LL * n_views); // [n_views][4]
     L.near = c.take<float>(R);
     L.far = c.take<float>(R);
     L.pts = c.take<float>(3 * nmax);
@@ -75,11 +75,81 @@ Layout carve(void* base, int R, int Sc, int Sf, int fine, int reuse)
     return L;
 }
 
-void ok(int rc, const char* what)
+// Everything of a pass behind its ray setup, for both entry points: the marches, the composites and the importance merge over R rays whose
+// directions, clip range and coarse depths (o.z) are in place.  The entry points differ only in what they hand in here.
+struct Marches {
+    const char* who;          // the entry point's name, for error messages
+    int R, Sc, Sf, fine, reuse;
+    int rays_per_view;        // 0: one origin L.cam_pos[3] for every ray; else ray r starts at L.cam_pos[r / rays_per_view][4]
+    int grid_nx, grid_ny;     // ray-grid hint of the mesh query (0, 0: none); a pass over V views stacks their rows: (nx, V * ny)
+    const float *u, *t_lin_f, *noise_c, *noise_f;
+};
+
+void run_marches(const VanerfWeights* w, const VanerfFrame* frame, const VanerfMeshAccel* accel, const float* verts, int nv, const int32_t* faces, int nf,
+                 const Marches& m, const Layout& L, const VanerfPassOut& o, void* stream)
+{
+    const int R = m.R, Sc = m.Sc, Sf = m.Sf, reuse = m.reuse;
+    auto ok = [&](int rc, const char* what) {
+        if (rc != VANERF_OK) {
+            const std::string inner = vanerf_last_error();
+            throw Error(rc, std::string(m.who) + ": " + what + ": " + inner);
+        }
+    };
+    // one march: points, mesh query (+ 1-NN), validity partition, per-sample networks
+    int marches = 0; // every launch with a work queue gets a word of its own from the scratch block (nothing is shared between launches in flight)
+    auto march = [&](const float* z, int S, const float* noise, float* q_sdf, float* rgba, uint8_t* valid_raw = nullptr) { // valid_raw: raw outputs + flags
+        unsigned long long* const qw = L.queue_words + 2 * marches++;
+        const int64_t n = (int64_t)R * S;
+        if (m.rays_per_view)
+            ok(vanerf_sample_points_views(L.rays_d, L.cam_pos, z, R, m.rays_per_view, S, L.pts, stream), "sample points");
+        else
+            ok(vanerf_sample_points(L.rays_d, L.cam_pos, z, R, S, L.pts, stream), "sample points");
+        const bool grid = m.grid_nx != 0;
+        ok(vanerf_mesh_query_accel(accel, verts, nv, faces, nf, frame->vert_vis, L.pts, n, q_sdf, L.q_vis, nullptr, L.knn, m.grid_nx, m.grid_ny, grid ? S : 0, qw,
+                                   stream), "mesh query");
+        const int32_t* order = nullptr;
+        if (n >= PARTITION_MIN_SAMPLES) {
+            ok(vanerf_query_order(frame, L.pts, n, L.order, L.order_scratch, L.order_scratch_bytes, stream), "validity partition");
+            order = L.order;
+        }
+        ok(vanerf_query_samples(w, frame, L.pts, q_sdf, L.q_vis, L.knn, noise, order, valid_raw ? 1 : 0, n, rgba, valid_raw, qw + 1, stream), "per-sample networks");
+    };
+    if (reuse == 2) { // the networks once per point; eval_func with the coarse draws here, with the fine batch's draws below
+        march(o.z, Sc, nullptr, L.q_sdf_c, L.raw_c, L.valid_c);
+        ok(vanerf_eval_func(L.raw_c, L.valid_c, nullptr, nullptr, nullptr, m.noise_c, Sc, 0, R, frame->invalid_sdf, L.rgba_c, nullptr, stream), "eval_func (coarse)");
+    } else {
+        march(o.z, Sc, m.noise_c, L.q_sdf_c, L.rgba_c);
+    }
+    composite_with_handle(w, L.rgba_c, o.z, L.q_sdf_c, nullptr, nullptr, nullptr, Sc, 0, R, o.color, o.depth, o.alpha, L.s1, L.contrib, stream);
+    if (!m.fine) return;
+    float* z_fine = o.z_fine ? o.z_fine : L.z_fine;
+    float* cf = o.color_fine ? o.color_fine : L.color_f3;
+    float* df = o.depth_fine ? o.depth_fine : L.s1 + R;
+    float* af = o.alpha_fine ? o.alpha_fine : L.s1 + 2LL * R;
+    float* sf = o.sdf ? o.sdf : L.s1 + 3LL * R;
+    ok(vanerf_importance_merge(L.contrib, o.z, m.u, m.u ? nullptr : m.t_lin_f, R, Sc, Sf, L.z_new, z_fine, L.src, nullptr, stream), "importance sampling");
+    if (reuse == 2) {
+        march(L.z_new, Sf, nullptr, L.q_sdf_f, L.rgba_f, L.valid_f);
+        // noise_f holds one draw per position of the merged order (the reference draws them for the re-evaluated fine batch, src/model.py:1155-1156)
+        ok(vanerf_eval_func(L.raw_c, L.valid_c, L.rgba_f, L.valid_f, L.src, m.noise_f, Sc, Sf, R, frame->invalid_sdf, L.rgba_cf, L.rgba_f, stream), "eval_func (fine)");
+        composite_with_handle(w, L.rgba_cf, z_fine, L.q_sdf_c, L.rgba_f, L.q_sdf_f, L.src, Sc, Sf, R, cf, df, af, sf, nullptr, stream);
+    } else if (reuse) {
+        march(L.z_new, Sf, nullptr, L.q_sdf_f, L.rgba_f);
+        composite_with_handle(w, L.rgba_c, z_fine, L.q_sdf_c, L.rgba_f, L.q_sdf_f, L.src, Sc, Sf, R, cf, df, af, sf, nullptr, stream);
+    } else {
+        march(z_fine, Sc + Sf, m.noise_f, L.q_sdf_f, L.rgba_f);
+        composite_with_handle(w, L.rgba_f, z_fine, L.q_sdf_f, nullptr, nullptr, nullptr, Sc + Sf, 0, R, cf, df, af, sf, nullptr, stream);
+    }
+}
+
+// samples per ray of the largest march of a pass (what the multi-view entry points hold against VIEWS_MAX_ITEMS)
+int views_s_max(int Sc, int Sf, bool fine, bool reuse) { return !fine ? Sc : reuse ? (Sc > Sf ? Sc : Sf) : Sc + Sf; }
+
+void ok_setup(const char* who, int rc)
 {
     if (rc != VANERF_OK) {
         const std::string inner = vanerf_last_error();
-        throw Error(rc, std::string("vanerf_render_pass: ") + what + ": " + inner);
+        throw Error(rc, std::string(who) + ": ray setup: " + inner);
     }
 }
 
@@ -108,56 +178,57 @@ extern "C" int vanerf_render_pass(const VanerfWeights* w, const VanerfFrame* fra
         const Layout L = carve(scratch, R, Sc, Sf, fine, reuse);
         if (scratch_bytes < L.total) throw_error("vanerf_render_pass: scratch of %lld bytes, %lld needed (vanerf_render_pass_scratch)", (long long)scratch_bytes, (long long)L.total);
         // a1-a4: pixel grid, rays, bbox clip, coarse depths
+        const char* const who = "vanerf_render_pass";
         if (d.pixels_xy)
-            ok(vanerf_ray_setup_pixels(d.pixels_xy, R, d.width, d.invK_T, d.RT, d.znear, d.zfar, d.bounds, Sc, d.t_lin_c, d.jitter, o.index, L.rays_d,
-                                       L.cam_pos, L.near, L.far, o.hit, o.z, stream), "ray setup");
+            ok_setup(who, vanerf_ray_setup_pixels(d.pixels_xy, R, d.width, d.invK_T, d.RT, d.znear, d.zfar, d.bounds, Sc, d.t_lin_c, d.jitter, o.index, L.rays_d,
+                                                  L.cam_pos, L.near, L.far, o.hit, o.z, stream));
         else if (d.row_blocks)
-            ok(vanerf_ray_setup_blocks(d.row_blocks, d.x0, d.step_x, d.y_block, d.nx, d.ny, d.width, d.invK_T, d.RT, d.znear, d.zfar, d.bounds, Sc, d.t_lin_c,
-                                       d.jitter, o.index, L.rays_d, L.cam_pos, L.near, L.far, o.hit, o.z, stream), "ray setup");
+            ok_setup(who, vanerf_ray_setup_blocks(d.row_blocks, d.x0, d.step_x, d.y_block, d.nx, d.ny, d.width, d.invK_T, d.RT, d.znear, d.zfar, d.bounds, Sc, d.t_lin_c,
+                                                  d.jitter, o.index, L.rays_d, L.cam_pos, L.near, L.far, o.hit, o.z, stream));
         else
-            ok(vanerf_ray_setup(d.x0, d.y0, d.step_x, d.step_y, d.y_block, d.nx, d.ny, d.width, d.invK_T, d.RT, d.znear, d.zfar, d.bounds, Sc, d.t_lin_c,
-                                d.jitter, o.index, L.rays_d, L.cam_pos, L.near, L.far, o.hit, o.z, stream), "ray setup");
-        // one march: points, mesh query (+ 1-NN), validity partition, per-sample networks
-        int marches = 0; // every launch with a work queue gets a word of its own from the scratch block (nothing is shared between launches in flight)
-        auto march = [&](const float* z, int S, const float* noise, float* q_sdf, float* rgba, uint8_t* valid_raw = nullptr) { // valid_raw: raw outputs + flags
-            unsigned long long* const qw = L.queue_words + 2 * marches++;
-            const int64_t n = (int64_t)R * S;
-            ok(vanerf_sample_points(L.rays_d, L.cam_pos, z, R, S, L.pts, stream), "sample points");
-            const bool grid = d.pixels_xy == nullptr;
-            ok(vanerf_mesh_query_accel(accel, verts, nv, faces, nf, frame->vert_vis, L.pts, n, q_sdf, L.q_vis, nullptr, L.knn, grid ? d.nx : 0,
-                                       grid ? d.ny : 0, grid ? S : 0, qw, stream), "mesh query");
-            const int32_t* order = nullptr;
-            if (n >= PARTITION_MIN_SAMPLES) {
-                ok(vanerf_query_order(frame, L.pts, n, L.order, L.order_scratch, L.order_scratch_bytes, stream), "validity partition");
-                order = L.order;
-            }
-            ok(vanerf_query_samples(w, frame, L.pts, q_sdf, L.q_vis, L.knn, noise, order, valid_raw ? 1 : 0, n, rgba, valid_raw, qw + 1, stream), "per-sample networks");
-        };
-        if (reuse == 2) { // the networks once per point; eval_func with the coarse draws here, with the fine batch's draws below
-            march(o.z, Sc, nullptr, L.q_sdf_c, L.raw_c, L.valid_c);
-            ok(vanerf_eval_func(L.raw_c, L.valid_c, nullptr, nullptr, nullptr, d.noise_c, Sc, 0, R, frame->invalid_sdf, L.rgba_c, nullptr, stream), "eval_func (coarse)");
-        } else {
-            march(o.z, Sc, d.noise_c, L.q_sdf_c, L.rgba_c);
-        }
-        composite_with_handle(w, L.rgba_c, o.z, L.q_sdf_c, nullptr, nullptr, nullptr, Sc, 0, R, o.color, o.depth, o.alpha, L.s1, L.contrib, stream);
-        if (!fine) return;
-        float* z_fine = o.z_fine ? o.z_fine : L.z_fine;
-        float* cf = o.color_fine ? o.color_fine : L.color_f3;
-        float* df = o.depth_fine ? o.depth_fine : L.s1 + R;
-        float* af = o.alpha_fine ? o.alpha_fine : L.s1 + 2LL * R;
-        float* sf = o.sdf ? o.sdf : L.s1 + 3LL * R;
-        ok(vanerf_importance_merge(L.contrib, o.z, d.u, d.u ? nullptr : d.t_lin_f, R, Sc, Sf, L.z_new, z_fine, L.src, nullptr, stream), "importance sampling");
-        if (reuse == 2) {
-            march(L.z_new, Sf, nullptr, L.q_sdf_f, L.rgba_f, L.valid_f);
-            // noise_f holds one draw per position of the merged order (the reference draws them for the re-evaluated fine batch, src/model.py:1155-1156)
-            ok(vanerf_eval_func(L.raw_c, L.valid_c, L.rgba_f, L.valid_f, L.src, d.noise_f, Sc, Sf, R, frame->invalid_sdf, L.rgba_cf, L.rgba_f, stream), "eval_func (fine)");
-            composite_with_handle(w, L.rgba_cf, z_fine, L.q_sdf_c, L.rgba_f, L.q_sdf_f, L.src, Sc, Sf, R, cf, df, af, sf, nullptr, stream);
-        } else if (reuse) {
-            march(L.z_new, Sf, nullptr, L.q_sdf_f, L.rgba_f);
-            composite_with_handle(w, L.rgba_c, z_fine, L.q_sdf_c, L.rgba_f, L.q_sdf_f, L.src, Sc, Sf, R, cf, df, af, sf, nullptr, stream);
-        } else {
-            march(z_fine, Sc + Sf, d.noise_f, L.q_sdf_f, L.rgba_f);
-            composite_with_handle(w, L.rgba_f, z_fine, L.q_sdf_f, nullptr, nullptr, nullptr, Sc + Sf, 0, R, cf, df, af, sf, nullptr, stream);
-        }
+            ok_setup(who, vanerf_ray_setup(d.x0, d.y0, d.step_x, d.step_y, d.y_block, d.nx, d.ny, d.width, d.invK_T, d.RT, d.znear, d.zfar, d.bounds, Sc, d.t_lin_c,
+                                           d.jitter, o.index, L.rays_d, L.cam_pos, L.near, L.far, o.hit, o.z, stream));
+        const bool grid = d.pixels_xy == nullptr;
+        run_marches(w, frame, accel, verts, nv, faces, nf,
+                    Marches{who, R, Sc, Sf, fine, reuse, 0, grid ? d.nx : 0, grid ? d.ny : 0, d.u, d.t_lin_f, d.noise_c, d.noise_f}, L, o, stream);
+    });
+}
+
+// A pass over n_views target views of one source frame that share a pixel grid: one ray setup that reads the cameras from a device table, then
+// the marches above over n_views * nx * ny rays (the views' rows stacked: the ray-grid hint is nx x (n_views * ny)).  Nothing behind the ray
+// setup knows about cameras except the per-view ray origin, so the outputs hold, view after view, the bits of n_views single passes.
+extern "C" int64_t vanerf_render_pass_views_scratch(int n_views, int rays_per_view, int Sc, int Sf, int fine, int reuse_coarse)
+{
+    if (n_views <= 0 || rays_per_view <= 0 || Sc <= 0 || Sf < 0) return 0;
+    if ((long long)n_views * rays_per_view * views_s_max(Sc, Sf, fine != 0, reuse_coarse && fine) >= VIEWS_MAX_ITEMS) return 0; // as the pass itself
+    return carve(nullptr, n_views * rays_per_view, Sc, Sf, fine, reuse_coarse ? 1 : 0, n_views).total;
+}
+
+extern "C" int vanerf_render_pass_views(const VanerfWeights* w, const VanerfFrame* frame, const VanerfMeshAccel* accel, const float* verts, int nv,
+                                        const int32_t* faces, int nf, const VanerfViewsDesc* desc, const VanerfPassOut* out, void* scratch,
+                                        int64_t scratch_bytes, void* stream)
+{
+    return guarded([&] {
+        const char* const who = "vanerf_render_pass_views";
+        if (!w || !frame || !accel || !verts || !faces || !desc || !out || !scratch) throw_error("vanerf_render_pass_views: null argument");
+        const VanerfViewsDesc& d = *desc;
+        const VanerfPassOut& o = *out;
+        const int V = d.n_views, Sc = d.Sc, Sf = d.Sf, fine = d.fine != 0;
+        if (V <= 0 || d.nx <= 0 || d.ny <= 0 || Sc < 2 || (fine && Sf < 1))
+            throw_error("vanerf_render_pass_views: n_views=%d nx=%d ny=%d Sc=%d Sf=%d", V, d.nx, d.ny, Sc, Sf);
+        if (!d.cams) throw_error("vanerf_render_pass_views: camera table missing");
+        if (!o.index || !o.hit || !o.z || !o.color || !o.depth || !o.alpha) throw_error("vanerf_render_pass_views: a coarse output pointer is null");
+        if (!d.t_lin_c || (fine && !d.u && !d.t_lin_f)) throw_error("vanerf_render_pass_views: linspace tables missing");
+        const int reuse = d.reuse_coarse && fine ? 1 : 0;
+        const int S_max = views_s_max(Sc, Sf, fine, reuse);
+        if ((long long)V * d.nx * d.ny * S_max >= VIEWS_MAX_ITEMS)
+            throw_error("vanerf_render_pass_views: %d views of %d x %d rays at %d samples do not fit a 32-bit sample index", V, d.nx, d.ny, S_max);
+        const int rpv = d.nx * d.ny, R = V * rpv;
+        const Layout L = carve(scratch, R, Sc, Sf, fine, reuse, V);
+        if (scratch_bytes < L.total)
+            throw_error("vanerf_render_pass_views: scratch of %lld bytes, %lld needed (vanerf_render_pass_views_scratch)", (long long)scratch_bytes, (long long)L.total);
+        ok_setup(who, vanerf_ray_setup_views(d.cams, V, d.x0, d.y0, d.step_x, d.step_y, d.nx, d.ny, d.width, d.bounds, Sc, d.t_lin_c, d.jitter, o.index, L.rays_d,
+                                             L.cam_pos, L.near, L.far, o.hit, o.z, stream));
+        run_marches(w, frame, accel, verts, nv, faces, nf, Marches{who, R, Sc, Sf, fine, reuse, rpv, d.nx, V * d.ny, d.u, d.t_lin_f, nullptr, nullptr}, L, o, stream);
     });
 }

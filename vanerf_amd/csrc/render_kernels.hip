@@ -79,34 +79,39 @@ __global__ void ray_bbox_kernel(const BboxParams B, const float* __restrict__ di
     near[r] = z1; far[r] = z2; hit[r] = h;
 }
 
-__global__ __launch_bounds__(256) void ray_setup_kernel(const RayParams P)
+// One block of up to 256 rays of one camera: pixel, direction, bbox clip, near / far and the rows of coarse depths.  The body of both ray
+// kernels below, so that a ray has the same arithmetic (hence, under -ffp-contract=off, the same bits) whichever of them generates it.
+//   K = inverse(K[:3,:3]) transposed [9], M = [R|t] rows 0..2 [12]: block-uniform (kernel arguments, or the camera table's row in LDS)
+//   blk: the block's number among the blocks of its view; ray0: the view's first ray in the output arrays (0 for a single view)
+__device__ __forceinline__ void ray_setup_block(const RayParams& P, const float* K, const float* M, float znear, float zfar, int blk, size_t ray0,
+                                                float* cam_pos)
 {
     __shared__ float s_near[256], s_far[256];
     const int R = P.nx * P.ny;
-    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    const int r = blk * blockDim.x + threadIdx.x;
+    const size_t g = ray0 + r; // the ray's slot in the outputs (and in jitter)
     // camera centre: -(t . R)  (src/model.py:1213)
-    const float* M = P.RT;
     const float tx = M[3], ty = M[7], tz = M[11];
     const float ox = -((tx * M[0] + ty * M[4]) + tz * M[8]);
     const float oy = -((tx * M[1] + ty * M[5]) + tz * M[9]);
     const float oz = -((tx * M[2] + ty * M[6]) + tz * M[10]);
-    if (r == 0) { P.cam_pos[0] = ox; P.cam_pos[1] = oy; P.cam_pos[2] = oz; }
+    if (r == 0) { cam_pos[0] = ox; cam_pos[1] = oy; cam_pos[2] = oz; }
     float near = 0.0f, far = 0.0f;
     if (r < R) {
     const int ix = r % P.nx, iy = r / P.nx;
     const int gxi = P.pixels ? P.pixels[2 * r] : P.x0 + ix * P.step_x;
     const int gyi = P.pixels ? P.pixels[2 * r + 1]
                              : (P.row_blocks ? P.row_blocks[iy / P.y_block] : P.y0 + (iy / P.y_block) * P.step_y) + (iy % P.y_block) * P.step_x;
-    P.index[r] = (int64_t)gxi + (int64_t)gyi * P.width;
+    P.index[g] = (int64_t)gxi + (int64_t)gyi * P.width;
     const float gx = (float)gxi, gy = (float)gyi;
-    const float* K = P.invK_T; // row-major 3x3: c_j = gx*K[0][j] + gy*K[1][j] + K[2][j]
+    // K row-major 3x3: c_j = gx*K[0][j] + gy*K[1][j] + K[2][j]
     float c0 = (gx * K[0] + gy * K[3]) + K[6];
     float c1 = (gx * K[1] + gy * K[4]) + K[7];
     float c2 = (gx * K[2] + gy * K[5]) + K[8];
     // znear/zfar along the ray: || (z * [x, y, 1]) K^-T ||  (src/model.py:1204-1211)
-    float nx_ = P.znear * gx, ny_ = P.znear * gy, nz_ = P.znear;
+    float nx_ = znear * gx, ny_ = znear * gy, nz_ = znear;
     float zn = norm3((nx_ * K[0] + ny_ * K[3]) + nz_ * K[6], (nx_ * K[1] + ny_ * K[4]) + nz_ * K[7], (nx_ * K[2] + ny_ * K[5]) + nz_ * K[8]);
-    float fx_ = P.zfar * gx, fy_ = P.zfar * gy, fz_ = P.zfar;
+    float fx_ = zfar * gx, fy_ = zfar * gy, fz_ = zfar;
     float zf = norm3((fx_ * K[0] + fy_ * K[3]) + fz_ * K[6], (fx_ * K[1] + fy_ * K[4]) + fz_ * K[7], (fx_ * K[2] + fy_ * K[5]) + fz_ * K[8]);
     // world direction: normalize(c . R)
     float dx = (c0 * M[0] + c1 * M[4]) + c2 * M[8];
@@ -114,41 +119,62 @@ __global__ __launch_bounds__(256) void ray_setup_kernel(const RayParams P)
     float dz = (c0 * M[2] + c1 * M[6]) + c2 * M[10];
     float nrm = fmaxf(norm3(dx, dy, dz), 1e-12f);
     dx /= nrm; dy /= nrm; dz /= nrm;
-    P.rays_d[3 * r] = dx; P.rays_d[3 * r + 1] = dy; P.rays_d[3 * r + 2] = dz;
+    P.rays_d[3 * g] = dx; P.rays_d[3 * g + 1] = dy; P.rays_d[3 * g + 2] = dz;
 
     float z1, z2;
     const bool hit = ray_bbox(P.bounds, ox, oy, oz, dx, dy, dz, z1, z2);
     near = (hit && z1 > zn) ? z1 : zn; // src/model.py:1217-1220
     far = (hit && z2 < zf) ? z2 : zf;
-    P.near[r] = near; P.far[r] = far; P.hit[r] = hit;
+    P.near[g] = near; P.far[g] = far; P.hit[g] = hit;
     }
     // coarse depths (src/model.py:1222-1232), written by the whole block in memory order (a thread per ray wrote 64 cache lines per store)
     s_near[threadIdx.x] = near; s_far[threadIdx.x] = far;
     __syncthreads();
     const int S = P.S;
-    const int r0 = blockIdx.x * blockDim.x, nr = min((int)blockDim.x, R - r0);
+    const int r0 = blk * blockDim.x, nr = min((int)blockDim.x, R - r0);
+    const size_t g0 = ray0 + r0;
     for (int k = threadIdx.x; k < nr * S; k += blockDim.x) {
         const int rl = k / S, i = k - rl * S;
         float t = P.t_lin[i];
         if (P.jitter) {
             float lo_t = i == 0 ? P.t_lin[0] : 0.5f * (P.t_lin[i] + P.t_lin[i - 1]);
             float hi_t = i == S - 1 ? P.t_lin[S - 1] : 0.5f * (P.t_lin[i + 1] + P.t_lin[i]);
-            t = lo_t + P.jitter[(size_t)(r0 + rl) * S + i] * (hi_t - lo_t);
+            t = lo_t + P.jitter[(g0 + rl) * S + i] * (hi_t - lo_t);
         }
-        P.z[(size_t)(r0 + rl) * S + i] = s_near[rl] + (s_far[rl] - s_near[rl]) * t;
+        P.z[(g0 + rl) * S + i] = s_near[rl] + (s_far[rl] - s_near[rl]) * t;
     }
 }
 
+__global__ __launch_bounds__(256) void ray_setup_kernel(const RayParams P)
+{
+    ray_setup_block(P, P.invK_T, P.RT, P.znear, P.zfar, blockIdx.x, 0, P.cam_pos);
+}
+
+// The same for V cameras that share one pixel grid: cams[V][24] = invK_T[9], RT[12], znear, zfar, pad (device).  blockIdx.y is the view, so a
+// block never straddles two views: its camera is uniform, read once per block into LDS (24 lanes, one float each) and broadcast from there.
+// Ray v * nx * ny + r of the outputs is ray r of view v; cam_pos is [V][4].  P's own camera fields are not read.
+constexpr int CAM_FLOATS = 24;
+__global__ __launch_bounds__(256) void ray_setup_views_kernel(const RayParams P, const float* __restrict__ cams)
+{
+    __shared__ float s_cam[CAM_FLOATS];
+    const int v = blockIdx.y;
+    if (threadIdx.x < CAM_FLOATS) s_cam[threadIdx.x] = cams[(size_t)v * CAM_FLOATS + threadIdx.x];
+    __syncthreads();
+    ray_setup_block(P, s_cam, s_cam + 9, s_cam[21], s_cam[22], blockIdx.x, (size_t)v * (size_t)(P.nx * P.ny), P.cam_pos + 4 * v);
+}
+
+// rays_per_view: 0 = one origin for every ray (cam_pos[3]); otherwise ray r starts at cam_pos[r / rays_per_view][4] (a pass over several views)
 __global__ void sample_points_kernel(const float* __restrict__ rays_d, const float* __restrict__ cam_pos,
-                                     const float* __restrict__ z, long long n, int S, float* __restrict__ pts)
+                                     const float* __restrict__ z, long long n, int S, int rays_per_view, float* __restrict__ pts)
 {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const long long r = i / S;
+    const int r = (int)(i / S); // a ray index fits 32 bits (R is an int)
+    const float* o = rays_per_view ? cam_pos + 4 * (r / rays_per_view) : cam_pos;
     const float t = z[i];
-    pts[3 * i + 0] = cam_pos[0] + rays_d[3 * r + 0] * t;
-    pts[3 * i + 1] = cam_pos[1] + rays_d[3 * r + 1] * t;
-    pts[3 * i + 2] = cam_pos[2] + rays_d[3 * r + 2] * t;
+    pts[3 * i + 0] = o[0] + rays_d[3LL * r + 0] * t;
+    pts[3 * i + 1] = o[1] + rays_d[3LL * r + 1] * t;
+    pts[3 * i + 2] = o[2] + rays_d[3LL * r + 2] * t;
 }
 
 // sdf_activation + rgba2out.  Sums are accumulated in fp64 from fp32 products so the result does not
@@ -371,14 +397,48 @@ static void ray_setup_impl(const int32_t* pixels, const int32_t* row_blocks, int
     }
 }
 
-extern "C" int vanerf_sample_points(const float* rays_d, const float* cam_pos, const float* z, int R, int S, float* pts, void* stream)
+extern "C" int vanerf_ray_setup_views(const float* cams, int n_views, int x0, int y0, int step_x, int step_y, int nx, int ny, int width,
+                                      const float* bounds, int S, const float* t_lin, const float* jitter, int64_t* index, float* rays_d,
+                                      float* cam_pos, float* near, float* far, uint8_t* hit, float* z, void* stream)
 {
     return guarded([&] {
-        if (!rays_d || !cam_pos || !z || !pts) throw_error("vanerf_sample_points: null argument");
-        if (R <= 0 || S <= 0) throw_error("vanerf_sample_points: R=%d S=%d", R, S);
-        const long long n = (long long)R * S;
-        hipLaunchKernelGGL(sample_points_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, rays_d, cam_pos, z, n, S, pts);
+        if (!cams || !bounds || !t_lin || !index || !rays_d || !cam_pos || !near || !far || !hit || !z) throw_error("vanerf_ray_setup_views: null argument");
+        if (n_views <= 0 || n_views > 65535) throw_error("vanerf_ray_setup_views: n_views = %d outside [1, 65535]", n_views);
+        if (nx <= 0 || ny <= 0 || step_x <= 0 || step_y <= 0 || S < 2 || width <= 0)
+            throw_error("vanerf_ray_setup_views: bad grid (nx=%d ny=%d step=%d,%d S=%d)", nx, ny, step_x, step_y, S);
+        if ((long long)n_views * nx * ny * S >= VIEWS_MAX_ITEMS)
+            throw_error("vanerf_ray_setup_views: %d views of %d x %d rays at %d samples do not fit a 32-bit sample index", n_views, nx, ny, S);
+        RayParams P{};
+        P.x0 = x0; P.y0 = y0; P.step_x = step_x; P.step_y = step_y; P.y_block = 1; P.nx = nx; P.ny = ny; P.width = width;
+        std::copy_n(bounds, 6, P.bounds);
+        P.S = S; P.t_lin = t_lin; P.jitter = jitter;
+        P.index = index; P.rays_d = rays_d; P.cam_pos = cam_pos; P.near = near; P.far = far; P.hit = hit; P.z = z;
+        const int R = nx * ny;
+        hipLaunchKernelGGL(ray_setup_views_kernel, dim3((R + 255) / 256, n_views), dim3(256), 0, (hipStream_t)stream, P, cams);
         HIP_CHECK(hipGetLastError());
+    });
+}
+
+static void sample_points_impl(const char* who, const float* rays_d, const float* cam_pos, const float* z, int R, int S, int rays_per_view, float* pts, void* stream)
+{
+    if (!rays_d || !cam_pos || !z || !pts) throw_error("%s: null argument", who);
+    if (R <= 0 || S <= 0 || rays_per_view < 0) throw_error("%s: R=%d S=%d rays_per_view=%d", who, R, S, rays_per_view);
+    const long long n = (long long)R * S;
+    hipLaunchKernelGGL(sample_points_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, rays_d, cam_pos, z, n, S, rays_per_view, pts);
+    HIP_CHECK(hipGetLastError());
+}
+
+extern "C" int vanerf_sample_points(const float* rays_d, const float* cam_pos, const float* z, int R, int S, float* pts, void* stream)
+{
+    return guarded([&] { sample_points_impl("vanerf_sample_points", rays_d, cam_pos, z, R, S, 0, pts, stream); });
+}
+
+extern "C" int vanerf_sample_points_views(const float* rays_d, const float* cam_pos, const float* z, int R, int rays_per_view, int S, float* pts, void* stream)
+{
+    return guarded([&] {
+        if (rays_per_view <= 0 || R % (rays_per_view > 0 ? rays_per_view : 1) != 0)
+            throw_error("vanerf_sample_points_views: R = %d is not a whole number of views of %d rays", R, rays_per_view);
+        sample_points_impl("vanerf_sample_points_views", rays_d, cam_pos, z, R, S, rays_per_view, pts, stream);
     });
 }
 

@@ -567,6 +567,53 @@ class VANeRF(nn.Module):
         ret["vert_vis"] = out["vert_vis"]
         return ret
 
+    @torch.no_grad()
+    def render_pifu_nerf_views(net, img_in, cam_in, hand_type, targets, cam_tars, sp_data={}, **config):
+        """render_pifu_nerf for several target views of one source frame in ONE pass (vanerf_render_pass_views): the callers of the reference
+        that render a frame from many cameras (render_novel_views, render_video, the validation and test steps, src/model.py:513-545, 140-197)
+        call render_pifu_nerf once per camera.  cam_tars: list of cam_tar dicts of one width / height.  Evaluation only: eval mode, uniform=True,
+        no rand_noise_std (a training patch has a pixel list and noise draws of its own and keeps the single-view pass).  Returns one dict per
+        view with tex_fg, depth, alpha[, tex_fg_fine, depth_fine, alpha_fine, sdf], vert_xy, vert_vis laid out as render_pifu_nerf lays them
+        out, bit-identical to it; the GT gathers of a single target image (tar_img, msk) are not part of it."""
+        if net.training:
+            raise ValueError("render_pifu_nerf_views is an evaluation path: call net.eval() (training passes are single-view)")
+        if float(config.get("rand_noise_std", 0.0)) > 0.0:
+            raise ValueError("render_pifu_nerf_views takes no rand_noise_std (per-sample noise belongs to the single-view training pass)")
+        if not config.get("uniform", False):
+            raise ValueError("render_pifu_nerf_views renders with uniform=True (stratified draws belong to the single-view pass)")
+        if config.get("separate_cf", False):
+            raise NotImplementedError("separate_cf is not used by the shipped configs")
+        cam_tars = list(cam_tars)
+        if not cam_tars:
+            raise ValueError("render_pifu_nerf_views needs at least one target camera")
+        if any(c["K"].shape[0] != 1 for c in cam_tars):
+            raise ValueError("one camera per cam_tar dict (K of shape (1, 4, 4))")
+        cam_in = net.fold_transf(cam_in)
+        sizes = {(int(c.get("width", cam_in["width"])), int(c.get("height", cam_in["height"]))) for c in cam_tars}
+        if len(sizes) != 1:
+            raise ValueError(f"the views of one pass share one width / height, got {sorted(sizes)}")
+        (width, height), = sizes
+        Sc, Sf, fine = config.get("sample_per_ray_c", 64), config.get("sample_per_ray_f", 64), config.get("fine", False)
+        feat_geo, feat_tex = net.encoded(img_in)
+        fd = net.frame_data(img_in, cam_in, targets, feat_geo, feat_tex, sp_data, config["src_foreground_mask"])
+        cam_ts = [dict(c, width=width, height=height, znear=c.get("znear", cam_in["znear"]), zfar=c.get("zfar", cam_in["zfar"])) for c in cam_tars]
+        o = R.render_pass_views(net.packed_weights(), fd, cam_ts, config["bounds"], 0, 0, 1, width, height, Sc, Sf, fine=fine)
+        vert3d = targets["vert_world"]
+        outs = []
+        for v, cam_tar in enumerate(cam_tars):
+            ret = {"tex_fg": o["color"][v].view(height, width, 3).permute(2, 0, 1), "depth": o["depth"][v].view(1, height, width),
+                   "alpha": o["alpha"][v].view(1, height, width)}
+            if fine:
+                ret.update({"tex_fg_fine": o["color_fine"][v].view(height, width, 3).permute(2, 0, 1), "depth_fine": o["depth_fine"][v].view(1, height, width),
+                            "alpha_fine": o["alpha_fine"][v].view(1, height, width), "sdf": o["sdf"][v].view(1, height, width)})
+            vimg = vert3d @ cam_tar["KRT"][:, :3, :3].transpose(1, 2) + cam_tar["KRT"][:, :3, 3][:, None]
+            ret["vert_xy"] = vimg[..., :2] / (vimg[..., 2:3] + 1e-8)
+            if "transf" in cam_tar:  # src/model.py:1093-1095
+                ret["vert_xy"] = ret["vert_xy"] @ cam_tar["transf"][:, :2, :2].transpose(1, 2) + cam_tar["transf"][:, :, 2][:, None]
+            ret["vert_vis"] = fd.vert_vis[None, :, None]
+            outs.append(ret)
+        return outs
+
     def attach_autograd(self, out, img_in, feat_geo, feat_tex, targets, sp_data, fg_mask):
         """Replaces the differentiable entries of `out` (a batch_render_pifu_nerf result computed with _autograd=True) by tensors that
         carry the HIP values and, in backward, the gradients of vanerf_amd.torch_graph evaluated at the same samples (same points, same

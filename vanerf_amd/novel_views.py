@@ -72,6 +72,15 @@ def _default_render(net, tr_batch, cam_tar, nerf_level):
                                 src_foreground_mask=tr_batch["src_foreground_mask"], bounds=dr["bounds"], mask_at_box=dr.get("mask_at_box"))
 
 
+def _default_render_views(net, tr_batch, cam_tars, nerf_level):
+    """Several frames of one size in one pass on the HIP path (VANeRF.render_pifu_nerf_views): one out_nerf per camera."""
+    kw = net.kwargs["dr_kwargs"]
+    return net.render_pifu_nerf_views(tr_batch["im"], tr_batch["cam"], tr_batch["hand_type"], tr_batch["targets"], cam_tars,
+                                      sp_data=dict(tr_batch["sp_data"]), fine=kw["fine"], uniform=True, sample_per_ray_c=kw["sample_per_ray_c"],
+                                      sample_per_ray_f=kw["sample_per_ray_f"], src_foreground_mask=tr_batch["src_foreground_mask"],
+                                      bounds=tr_batch["dr_data"]["bounds"])
+
+
 def _default_render_rows(net, tr_batch, cam_tar, rank, world):
     """This rank's rows of one frame on the HIP path: (rows * width, 3) fine colour, rows dealt out by parallel.shard_rows."""
     from . import renderer as R
@@ -99,7 +108,7 @@ def _gather_rows(tile, h, w, world):
 
 @torch.no_grad()
 def render_novel_views(net, cameras, tr_batch, only_renderings=False, rank=0, world=1, gather=False, render_fn=None, on_frame=None,
-                       shard="frames", render_rows_fn=None):
+                       shard="frames", render_rows_fn=None, views_per_pass=1, render_views_fn=None):
     """src/model.py:513-545.  cameras: list of get_360cameras dicts; tr_batch: the decode_batch dict (im, cam, hand_type, targets,
     sp_data, src_foreground_mask, dr_data{bounds, objcenter, mask_at_box}).
     Returns uint8 (N,H,W,3) renderings with the source views pasted to their left, or (renderings, source images) when
@@ -107,9 +116,22 @@ def render_novel_views(net, cameras, tr_batch, only_renderings=False, rank=0, wo
     on_frame(frame_index, uint8 HWC device tensor) is called as each frame completes (render_video hands them to the PNG writers).
     render_fn(net, tr_batch, cam_tar, level) -> out_nerf replaces the renderer (tests of the scheduling use a stub).
     shard="rays": every rank renders ITS ROWS of every frame (render_rows_fn(net, tr_batch, cam_tar, rank, world) -> (rows * W, 3) tile,
-    default: the HIP path) and the frame is assembled on every rank by one all_gather; every rank then returns the whole orbit."""
+    default: the HIP path) and the frame is assembled on every rank by one all_gather; every rank then returns the whole orbit.
+    views_per_pass > 1 (shard="frames", the default renderer or a render_views_fn): a rank's frames are rendered in consecutive groups of up
+    to that many cameras, one pass per group (render_views_fn(net, tr_batch, cam_tars, level) -> list of out_nerf, default: the HIP path's
+    render_pifu_nerf_views); a group ends early where the image size changes.  Same frames, same on_frame calls in the same order."""
     if shard not in ("frames", "rays"):
         raise ValueError("shard must be 'frames' or 'rays'")
+    views_per_pass = int(views_per_pass)
+    if views_per_pass < 1:
+        raise ValueError("views_per_pass must be at least 1")
+    if views_per_pass > 1 and shard == "rays":
+        raise ValueError("views_per_pass > 1 groups whole frames: it needs shard='frames'")
+    if views_per_pass > 1 and render_fn is not None and render_views_fn is None:
+        raise ValueError("views_per_pass > 1 with a custom render_fn needs a render_views_fn")
+    grouped = views_per_pass > 1 or (render_views_fn is not None and render_fn is None)
+    default_views = grouped and render_views_fn is None
+    render_views_fn = render_views_fn or _default_render_views
     by_rays = shard == "rays" and world > 1
     render_fn = render_fn or _default_render
     render_rows_fn = render_rows_fn or _default_render_rows
@@ -119,23 +141,33 @@ def render_novel_views(net, cameras, tr_batch, only_renderings=False, rank=0, wo
         net.attach_im_feat(tr_batch["im"])
     tr_batch["dr_data"]["tar"] = None
     mine = list(range(len(cameras))) if by_rays else frames_of_rank(len(cameras), rank, world)
-    if (render_rows_fn is _default_render_rows if by_rays else render_fn is _default_render) and mine:  # the camera matrices go to the kernels by value: one read-back for the whole orbit, not one per frame
+    if (render_rows_fn is _default_render_rows if by_rays else default_views if grouped else render_fn is _default_render) and mine:  # the camera matrices go to the kernels by value: one read-back for the whole orbit, not one per frame
         from . import renderer as R
         R.prefetch_host_copies([cameras[fi][k] for fi in mine for k in ("intrinsics", "w2cs")] + [tr_batch["dr_data"]["bounds"]])
     frames = []
-    for fi in mine:
-        camera = cameras[fi]
+    size = lambda fi: (cameras[fi]["im_h"], cameras[fi]["im_w"])
+    k = 0
+    while k < len(mine):
+        group = [mine[k]]  # consecutive frames of this rank that go through one pass
+        while grouped and len(group) < views_per_pass and k + len(group) < len(mine) and size(mine[k + len(group)]) == size(group[0]):
+            group.append(mine[k + len(group)])
+        k += len(group)
+        camera = cameras[group[0]]
         nerf_level = max(0, int(math.log(camera["im_h"], 2)) - 5)
-        cam_tar = camera_to_cam_tar(camera)
-        tr_batch["dr_data"]["cam_tar"] = cam_tar
+        cam_tars = [camera_to_cam_tar(cameras[fi]) for fi in group]
+        cam_tar = tr_batch["dr_data"]["cam_tar"] = cam_tars[-1]
         if by_rays:
             full = _gather_rows(render_rows_fn(net, tr_batch, cam_tar, rank, world), int(camera["im_h"]), int(camera["im_w"]), world)
-            img = (full.clamp(min=0.0, max=1.0) * 255.0).to(torch.uint8)  # (H, W, 3), as arrange_nerf_images
+            imgs = [(full.clamp(min=0.0, max=1.0) * 255.0).to(torch.uint8)]  # (H, W, 3), as arrange_nerf_images
         else:
-            img = (arrange_nerf_images(render_fn(net, tr_batch, cam_tar, nerf_level)) * 255.0).to(torch.uint8)
-        if on_frame is not None:
-            on_frame(fi, img)
-        frames.append(img)
+            outs = render_views_fn(net, tr_batch, cam_tars, nerf_level) if grouped else [render_fn(net, tr_batch, cam_tar, nerf_level)]
+            if len(outs) != len(group):
+                raise ValueError(f"render_views_fn returned {len(outs)} frames for {len(group)} cameras")
+            imgs = [(arrange_nerf_images(o) * 255.0).to(torch.uint8) for o in outs]
+        for fi, img in zip(group, imgs):
+            if on_frame is not None:
+                on_frame(fi, img)
+            frames.append(img)
     h, w = cameras[0]["im_h"], cameras[0]["im_w"]
     dev = frames[0].device if frames else tr_batch["im"].device
     stack = torch.stack(frames) if frames else torch.empty(0, h, w, 3, dtype=torch.uint8, device=dev)
@@ -201,11 +233,12 @@ class AsyncImageWriter:
 
 @torch.no_grad()
 def render_video(net, batches, save_dir, decode_batch=lambda b: b, sc_factor=1.0, label="", n_frames=20, rank=0, world=1, render_fn=None,
-                 video_dirname="video", shard="frames", render_rows_fn=None):
+                 video_dirname="video", shard="frames", render_rows_fn=None, views_per_pass=1, render_views_fn=None):
     """src/model.py:140-197: one orbit per batch, frames as <save_dir>/<video_dirname><label>/<session>/<identity>/%06d.png, then a GIF per
     identity (PIL; the reference also writes an .mp4 through cv2, which this image does not have).  `batches` yields the dataloader's
     dicts ('index'.'segment', 'human', 'headpose', optional 'near_fars'); decode_batch maps one to the tr_batch of render_novel_views.
-    Camera constants are the reference's (trans 10, 256x256, focal from the 30x..0.05x sweep at 1 %)."""
+    Camera constants are the reference's (trans 10, 256x256, focal from the 30x..0.05x sweep at 1 %).
+    views_per_pass, render_views_fn: as render_novel_views (several frames of an orbit per pass; the PNGs are the same)."""
     trans = 10
     znear, zfar = (trans - 5.0) * sc_factor, (trans + 5.0) * sc_factor
     im_w, im_h = 256, 256
@@ -234,7 +267,7 @@ def render_video(net, batches, save_dir, decode_batch=lambda b: b, sc_factor=1.0
             writer.submit(os.path.join(sub, f"{fi:06d}.png"), torch.cat((src_dev, img), dim=1))  # source views | rendering, as the reference
 
         render_novel_views(net, cameras[identity], tr_batch, only_renderings=True, rank=rank, world=world, render_fn=render_fn, on_frame=on_frame,
-                           shard=shard, render_rows_fn=render_rows_fn)
+                           shard=shard, render_rows_fn=render_rows_fn, views_per_pass=views_per_pass, render_views_fn=render_views_fn)
     written = writer.close()
     if world > 1:
         import torch.distributed as dist

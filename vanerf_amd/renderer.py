@@ -12,7 +12,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _ffi
-from ._ffi import VanerfFrame, VanerfMeshAccel, VanerfPassDesc, VanerfPassOut, VanerfWeightTable, check, lib
+from ._ffi import VanerfFrame, VanerfMeshAccel, VanerfPassDesc, VanerfPassOut, VanerfViewsDesc, VanerfWeightTable, check, lib
 
 NV, NV_HAND, NKPT = 1558, 779, 42
 
@@ -624,6 +624,79 @@ def ray_setup(cam_tar, bounds, x0, y0, step, nx, ny, S, jitter=None, device=None
     return dict(index=index, rays_d=rays_d, cam_pos=cam_pos, near=near, far=far, hit=hit, z=z)
 
 
+CAM_FLOATS = 24  # a row of the camera table of the *_views entry points: invK_T[9], RT[12], znear, zfar, one pad
+
+
+def camera_table(cam_tars, dev):
+    """(V, 24) device table of the target cameras for vanerf_ray_setup_views / vanerf_render_pass_views.  Every number is produced the way the
+    single-view path produces the values it passes to the kernels -- host_copy, th.inverse on the host per matrix, Python float -> fp32 -- so a
+    view's rays are bit-identical to ray_setup's; one asynchronous host -> device copy for all of them (_staged_upload)."""
+    if not cam_tars:
+        raise ValueError("at least one target camera")
+    size = lambda c: (int(c["width"]), int(c.get("height", 0)))
+    if any(size(c) != size(cam_tars[0]) for c in cam_tars):
+        raise ValueError("the views of one pass share one width / height")
+    rows = []
+    for cam in cam_tars:
+        K, RT = host_copy(cam["K"]), host_copy(cam["RT"])
+        rows.append(torch.inverse(K[:, :3, :3]).transpose(1, 2)[0].reshape(-1).tolist() + RT[0, :3, :4].reshape(-1).tolist()
+                    + [float(cam["znear"]), float(cam["zfar"]), 0.0])
+    table = torch.tensor(rows, dtype=torch.float32)
+    assert table.shape == (len(cam_tars), CAM_FLOATS)
+    if torch.device(dev).type != "cuda":
+        return table.to(dev)
+    return _staged_upload(table, torch.device(dev))
+
+
+_STAGE = {}  # device -> [slots, next]: a ring of pinned staging blocks for small host -> device copies, each with the event of its last copy
+_STAGE_SLOTS, _STAGE_FLOATS = 8, 64 * CAM_FLOATS
+
+
+def _staged_upload(host, dev):
+    """host (a small fp32 CPU tensor) -> a new device tensor through a pinned block that is kept and used again: the copy is asynchronous (a
+    copy from pageable memory makes the host wait for everything queued on the stream, see _t_lin) and no pinned memory is allocated per call.
+    A slot is written again only after the copy that last read it has finished (its event; eight copies later, so the wait is a formality)."""
+    n = host.numel()
+    if n > _STAGE_FLOATS:  # more than 64 views in one pass: not worth a ring
+        return host.pin_memory().to(dev, non_blocking=True)
+    ring = _STAGE.setdefault(dev, [[], 0])
+    slots, k = ring
+    if len(slots) < _STAGE_SLOTS:
+        slots.append([torch.empty(_STAGE_FLOATS, dtype=torch.float32).pin_memory(), None])
+        k = len(slots) - 1
+    ring[1] = (k + 1) % _STAGE_SLOTS
+    block, ev = slots[k]
+    if ev is not None:
+        ev.synchronize()
+    block[:n].copy_(host.reshape(-1))
+    out = torch.empty(host.shape, dtype=torch.float32, device=dev)
+    out.view(-1).copy_(block[:n], non_blocking=True)
+    slots[k][1] = torch.cuda.Event()
+    slots[k][1].record(torch.cuda.current_stream(dev))
+    return out
+
+
+def ray_setup_views(cam_tars, bounds, x0, y0, step, nx, ny, S, jitter=None, device=None, y_step=None):
+    """ray_setup for several target cameras on one pixel grid in ONE launch (vanerf_ray_setup_views): the tensors of ray_setup with a leading
+    view dimension -- index (V,R), rays_d (V,R,3), cam_pos (V,4: xyz + pad), near, far, hit (V,R), z (V,R,S) -- each view bit-identical to
+    ray_setup(cam_tars[v], ...).  jitter: optional (V*R, S) draws."""
+    dev = device or bounds.device
+    V, R = len(cam_tars), nx * ny
+    cams = camera_table(cam_tars, dev)
+    index = torch.empty(V, R, dtype=torch.int64, device=dev)
+    rays_d = torch.empty(V, R, 3, dtype=torch.float32, device=dev)
+    cam_pos = torch.zeros(V, 4, dtype=torch.float32, device=dev)  # (the kernel writes xyz; the pad stays 0)
+    near, far = torch.empty(V, R, dtype=torch.float32, device=dev), torch.empty(V, R, dtype=torch.float32, device=dev)
+    hit = torch.empty(V, R, dtype=torch.uint8, device=dev)
+    z = torch.empty(V, R, S, dtype=torch.float32, device=dev)
+    if jitter is not None and jitter.numel() != V * R * S:
+        raise ValueError("jitter: one draw per coarse sample of every view (V*R, S)")
+    check(lib.vanerf_ray_setup_views(_ptr(cams, torch.float32), V, int(x0), int(y0), int(step), int(y_step or step), int(nx), int(ny), int(cam_tars[0]["width"]),
+                                     _farr(host_copy(bounds).reshape(-1).tolist(), 6), int(S), _ptr(_t_lin(S, dev)), _ptr(jitter, torch.float32),
+                                     _ptr(index), _ptr(rays_d), _ptr(cam_pos), _ptr(near), _ptr(far), _ptr(hit), _ptr(z), _stream()))
+    return dict(index=index, rays_d=rays_d, cam_pos=cam_pos, near=near, far=far, hit=hit, z=z)
+
+
 def sample_points(rays_d, cam_pos, z):
     R, S = z.shape
     pts = torch.empty(R * S, 3, dtype=torch.float32, device=z.device)
@@ -797,6 +870,55 @@ def render_pass_c(weights, frame, cam_tar, bounds, x0, y0, step, nx, ny, sample_
     scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     check(lib.vanerf_render_pass(weights.handle, byref(frame.c), byref(frame.accel.c), _ptr(frame.verts3, f32), frame.verts3.shape[0],
                                  _ptr(frame.faces, torch.int32), frame.faces.shape[0], byref(d), byref(o), _ptr(scratch), nbytes, _stream()))
+    return out
+
+
+def render_pass_views_scratch(n_views, rays_per_view, Sc, Sf, fine=True, reuse_coarse=True):
+    """Bytes of scratch vanerf_render_pass_views needs for one group of views."""
+    return int(lib.vanerf_render_pass_views_scratch(int(n_views), int(rays_per_view), int(Sc), int(Sf), int(bool(fine)), int(bool(reuse_coarse))))
+
+
+def render_pass_views(weights, frame, cam_tars, bounds, x0, y0, step, nx, ny, sample_per_ray_c=64, sample_per_ray_f=64, fine=True, jitter=None, u=None,
+                      y_step=None, reuse_coarse=True, scratch=None):
+    """One pass over several target views of the same source frame (vanerf_render_pass_views): every kernel of render_pass_c once over
+    V * nx * ny rays.  cam_tars: list of the dicts render_pass takes, all of one width / height.  Returns the flat tensors of render_pass_c
+    with a leading view dimension; out[k][v] is bit-identical to render_pass_c(cam_tars[v], ...)[k].  jitter (V*R, Sc), u (V*R, Sf): optional
+    draws (evaluation: no pixel list, no row blocks, no noise).  scratch: optional uint8 device tensor of at least render_pass_views_scratch
+    bytes (a caller that renders group after group keeps one)."""
+    Sc, Sf, V, R = int(sample_per_ray_c), int(sample_per_ray_f), len(cam_tars), nx * ny
+    dev = frame.verts3.device
+    cams = camera_table(cam_tars, dev)
+    d = VanerfViewsDesc()
+    d.n_views = V
+    d.x0, d.y0, d.step_x, d.step_y, d.nx, d.ny = int(x0), int(y0), int(step), int(y_step or step), int(nx), int(ny)
+    d.width = int(cam_tars[0]["width"])
+    d.cams = _ptr(cams, torch.float32)
+    d.bounds = _farr(host_copy(bounds).reshape(-1).tolist(), 6)
+    d.Sc, d.Sf, d.fine, d.reuse_coarse = Sc, Sf, int(bool(fine)), int(bool(reuse_coarse))
+    t_c, t_f = _t_lin(Sc, dev), _t_lin(Sf, dev) if fine else None
+    d.t_lin_c, d.t_lin_f = _ptr(t_c), _ptr(t_f)
+    if jitter is not None and jitter.numel() != V * R * Sc or u is not None and u.numel() != V * R * Sf:
+        raise ValueError("jitter / u: one draw per sample of every view, (V*R, Sc) / (V*R, Sf)")
+    d.jitter, d.u = _ptr(jitter, torch.float32), _ptr(u, torch.float32)
+    f32 = torch.float32
+    out = {"index": torch.empty(V, R, dtype=torch.int64, device=dev), "hit": torch.empty(V, R, dtype=torch.uint8, device=dev),
+           "z": torch.empty(V, R, Sc, dtype=f32, device=dev), "color": torch.empty(V, R, 3, dtype=f32, device=dev),
+           "depth": torch.empty(V, R, dtype=f32, device=dev), "alpha": torch.empty(V, R, dtype=f32, device=dev)}
+    if fine:
+        out.update({"color_fine": torch.empty(V, R, 3, dtype=f32, device=dev), "depth_fine": torch.empty(V, R, dtype=f32, device=dev),
+                    "alpha_fine": torch.empty(V, R, dtype=f32, device=dev), "sdf": torch.empty(V, R, dtype=f32, device=dev),
+                    "z_fine": torch.empty(V, R, Sc + Sf, dtype=f32, device=dev)})
+    o = VanerfPassOut()
+    for k in ("index", "hit", "z", "color", "depth", "alpha", "color_fine", "depth_fine", "alpha_fine", "sdf", "z_fine"):
+        setattr(o, k, _ptr(out.get(k)))
+    nbytes = render_pass_views_scratch(V, R, Sc, Sf, fine, reuse_coarse)
+    if nbytes <= 0:
+        raise ValueError(f"{V} views of {nx} x {ny} rays at {Sc} + {Sf} samples: not a valid multi-view pass")
+    if scratch is None:
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    check(lib.vanerf_render_pass_views(weights.handle, byref(frame.c), byref(frame.accel.c), _ptr(frame.verts3, f32), frame.verts3.shape[0],
+                                       _ptr(frame.faces, torch.int32), frame.faces.shape[0], byref(d), byref(o), _ptr(scratch, torch.uint8), scratch.numel(),
+                                       _stream()))
     return out
 
 
