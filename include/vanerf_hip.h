@@ -420,6 +420,31 @@ int vanerf_render_vis(const float* verts, int nv, const int32_t* faces, int nf, 
                       const float* focal, const float* princpt, int H, int W, float* scratch, int64_t scratch_bytes, float* rgb, float* vis,
                       int32_t* pix_to_face, float* zbuf, void* stream);
 
+/* Image scores of the reference's validation and test steps for V rendered views, on the device.  Neither kornia
+ * nor scikit-image is a dependency: the arithmetic is restated below, parity against kornia 0.7.1 / scikit-image 0.16.2 is unpinned.
+ *     pred[V][3][H][W], gt[V][3][H][W] fp32 (channel-first, as render_pifu_nerf returns them); clamp_pred != 0: pred is clamped to [0, 1]
+ *     on load.  mask[V][H][W], mask_at_box[V][H][W]: uint8, nonzero = set, either may be NULL.  All are DEVICE pointers.
+ *     -> out[V][8] fp32 (device):
+ *        0 mse          mean of (pred - gt)^2 over the 3 H W elements                          (Evaluator.compute_score, src/evaluator.py:84-114)
+ *        1 psnr         -10 log10(mse)
+ *        2 ssim_box     skimage structural_similarity(multichannel=True) of float images on the crop to cv2.boundingRect(mask_at_box) (the
+ *                       whole image without one): 7 x 7 uniform window, data_range 2 (C1 = 0.02^2, C2 = 0.06^2), sample covariance
+ *                       v = 49/48 (E[xy] - E[x]E[y]), S = (2 ux uy + C1)(2 vxy + C2) / ((ux^2 + uy^2 + C1)(vx + vy + C2)) averaged over the
+ *                       windows that lie wholly inside the crop, per channel, then over the channels.  NaN for an empty mask or a crop
+ *                       narrower or lower than 7 (the reference raises there)
+ *        3 psnr_masked  10 log10(max_val^2 / mean((pred - gt)^2)) over the pixels of mask x 3 channels    (compute_test_metric, src/model.py:210-235)
+ *        4 ssim_masked  mean over the same elements of kornia's ssim(window_size=7): 7 x 7 Gaussian window (sigma 1.5, normalised outer
+ *                       product of the 1-D kernel), images reflect-padded by 3 without repeating the edge pixel, sigma = E[x^2] - mu^2,
+ *                       C1 = (0.01 max_val)^2, C2 = (0.03 max_val)^2, S = num / (den + 1e-12).  Without a mask every pixel counts;
+ *                       slots 3 and 4 are NaN for an empty mask
+ *        5 n_mask, 6 box_w, 7 box_h   (exact)
+ *     scratch: vanerf_image_metrics_scratch(V, H, W) bytes of device memory, 16-byte aligned (0: not a valid shape; 1 <= V <= 65535,
+ *         4 <= H, W <= 4096).  Every byte the call reads of it is written by the call first: its previous contents do not matter.
+ *     Three launches on `stream`; no allocation, no host synchronisation, no atomics: the same bits every call, per view whatever V is.     */
+int64_t vanerf_image_metrics_scratch(int V, int H, int W);
+int vanerf_image_metrics(const float* pred, const float* gt, const uint8_t* mask, const uint8_t* mask_at_box, int V, int H, int W,
+                         double max_val, int clamp_pred, void* scratch, int64_t scratch_bytes, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

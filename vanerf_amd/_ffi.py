@@ -8,7 +8,7 @@ import os
 
 import torch  # noqa: F401  -- FIRST: torch ships its own libamdhip64; if libvanerf_hip.so (linked against /opt/rocm's) is loaded before
 #                          torch, two HIP runtimes live in the process and the second reports "no ROCm-capable device"
-from ctypes import POINTER, Structure, c_char_p, c_float, c_int, c_int64, c_uint, c_uint64, c_void_p
+from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int64, c_uint, c_uint64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VANERF_HIP_LIB") or os.path.join(_HERE, "lib", "libvanerf_hip.so")  # the override is for A/B runs of kernel builds (tools/)
@@ -133,6 +133,8 @@ _SIGS = {
     "vanerf_ig_tensor": (c_int, [c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
     "vanerf_ray_bbox": (c_int, [POINTER(c_float), POINTER(c_float), _FP, c_int, _FP, _FP, _FP, c_void_p]),
     "vanerf_render_vis": (c_int, [_FP, c_int, _FP, c_int, _FP, _FP, _FP, _FP, _FP, c_int, c_int, _FP, c_int64, _FP, _FP, _FP, _FP, c_void_p]),
+    "vanerf_image_metrics_scratch": (c_int64, [c_int, c_int, c_int]),
+    "vanerf_image_metrics": (c_int, [_FP, _FP, _FP, _FP, c_int, c_int, c_int, c_double, c_int, c_void_p, c_int64, _FP, c_void_p]),
 }
 EXPORTS = tuple(_SIGS)
 
