@@ -445,6 +445,25 @@ int64_t vanerf_image_metrics_scratch(int V, int H, int W);
 int vanerf_image_metrics(const float* pred, const float* gt, const uint8_t* mask, const uint8_t* mask_at_box, int V, int H, int W,
                          double max_val, int clamp_pred, void* scratch, int64_t scratch_bytes, float* out, void* stream);
 
+/* The dataset's mask_at_box and near / far range of V target views, on the device: Dataset.get_mask_at_box ->
+ * get_rays / get_near_far (src/dataset.py:122-129, 609-658) restated.
+ *     cams[V][24]: the DEVICE table of vanerf_ray_setup_views (invK_T[9], RT[12]; znear, zfar and the pad are not read).  bounds[6]: HOST,
+ *     min xyz then max xyz, read before the call returns.  Per pixel (r, c) of view v, in fp64 from the fp32 values:
+ *        pc = (c, r, 1) . invK_T,  o = -R^T T,  d = (pc - T) . R - o;  o and d are each rounded to fp32 once, and a component of d with
+ *        |d| < 1e-5 becomes +1e-5 (both in fp32; the sign is lost, as in the reference).
+ *        b = bounds + (-0.01, +0.01).  For each of the six planes (min x, y, z, max x, y, z): t = (b - o) / d on the plane's axis,
+ *        p = t d + o; the plane is hit iff all three coordinates of p lie in [b_min - 1e-6, b_max + 1e-6].
+ *        mask = exactly two planes are hit; near / far = the smaller / larger of |p - o| / |d| over the two hits.
+ *     -> mask[V][H][W] uint8 (0 / 1); near[V][H][W], far[V][H][W] fp32 (either may be NULL): the ray's values on mask pixels, NaN elsewhere;
+ *        out[V][8] fp32: 0 near_min, 1 far_max (NaN for an empty mask: the reference raises there), 2 n_mask, 3-6 box_x, box_y, box_w, box_h
+ *        (cv2.boundingRect of the mask; 0, 0, 0, 0 for an empty one), 7 zero.  Slots 2-6 are exact.  All DEVICE pointers.
+ *     scratch: vanerf_mask_at_box_scratch(V, H, W) bytes of device memory, 16-byte aligned (0: not a valid shape; 1 <= V <= 65535,
+ *         1 <= H, W <= 4096).  Every byte the call reads of it is written by the call first: its previous contents do not matter.
+ *     Two launches on `stream`; no allocation, no host synchronisation, no atomics: the same bits every call, per view whatever V is.       */
+int64_t vanerf_mask_at_box_scratch(int V, int H, int W);
+int vanerf_mask_at_box(const float* cams, int V, int H, int W, const float bounds[6], uint8_t* mask, float* near, float* far, void* scratch,
+                       int64_t scratch_bytes, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -135,6 +135,8 @@ _SIGS = {
     "vanerf_render_vis": (c_int, [_FP, c_int, _FP, c_int, _FP, _FP, _FP, _FP, _FP, c_int, c_int, _FP, c_int64, _FP, _FP, _FP, _FP, c_void_p]),
     "vanerf_image_metrics_scratch": (c_int64, [c_int, c_int, c_int]),
     "vanerf_image_metrics": (c_int, [_FP, _FP, _FP, _FP, c_int, c_int, c_int, c_double, c_int, c_void_p, c_int64, _FP, c_void_p]),
+    "vanerf_mask_at_box_scratch": (c_int64, [c_int, c_int, c_int]),
+    "vanerf_mask_at_box": (c_int, [_FP, c_int, c_int, c_int, POINTER(c_float), _FP, _FP, _FP, c_void_p, c_int64, _FP, c_void_p]),
 }
 EXPORTS = tuple(_SIGS)
 

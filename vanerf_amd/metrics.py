@@ -94,13 +94,17 @@ def compute_score(rgb_pred, rgb_gt, mask_at_box):
     return {"mse": mse, "psnr": psnr, "ssim": ssim}
 
 
-def evaluate_views(net, tr_batch, cam_tars, tar_imgs, masks_at_box, masks=None, views_per_pass=None):
+def evaluate_views(net, tr_batch, cam_tars, tar_imgs, masks_at_box, masks=None, views_per_pass=None, mask_from_bounds=False):
     """The test loop of one source frame: renders the target views `cam_tars` through VANeRF.render_pifu_nerf_views, `views_per_pass` at a time
     (default: all in one pass), and scores each view's tex_fg_fine, clamped to [0, 1] as the reference clamps before it scores, against
     tar_imgs (V, 3, H, W) with masks_at_box (V, H, W) [and masks (V, H, W) for the masked pair; None: every pixel].  Returns (scores (V, 8) on
     the device -- `SLOTS` --, list of the V rendered images (3, H, W)).  Never waits for the GPU: the caller reads the scores back when it
-    wants them, once for the whole frame."""
+    wants them, once for the whole frame.
+    mask_from_bounds: masks_at_box must be None; the masks are made on the device from tr_batch["dr_data"]["bounds"] and the same cameras
+    (mask_at_box.mask_at_box, the dataset's get_mask_at_box) on the stream of the pass, before the first render."""
     from .novel_views import _default_render_views
+    if mask_from_bounds and masks_at_box is not None:
+        raise ValueError("evaluate_views: masks_at_box and mask_from_bounds are two sources of one mask, give one of them")
     cam_tars = list(cam_tars)
     V = len(cam_tars)
     if V == 0:
@@ -126,6 +130,9 @@ def evaluate_views(net, tr_batch, cam_tars, tar_imgs, masks_at_box, masks=None, 
             raise ValueError(f"{name}: expected {V} mask(s) of {H} x {W}, got {tuple(m.shape)}")
         return m.reshape(V, H, W)
 
+    if mask_from_bounds:
+        from .mask_at_box import mask_at_box
+        masks_at_box = mask_at_box(cam_tars, tr_batch["dr_data"]["bounds"])[0]
     masks_at_box, masks = per_view(masks_at_box, "masks_at_box"), per_view(masks, "masks")
     scores = torch.empty(V, 8, dtype=torch.float32, device=tar_imgs.device)
     images = []
