@@ -116,10 +116,11 @@ int vanerf_weights_short_groups(const VanerfWeights* w, uint64_t* count);
 /* Host-only view of the packed fragment stream (no GPU touched): out[cap] or NULL to query the size; offsets[20]. */
 int vanerf_weights_pack_host(const VanerfWeightTable* w, float* out, int64_t cap, int64_t* n_out, unsigned* offsets);
 /* Host-only view of any stream a handle can carry: which = 0 the fp32 forward stream, 1 the bf16x3 forward stream (32-bit words of two bf16
- * each, copied raw), 2 the transposed fp32 stream of the fused backward pass.  out[cap] or NULL to query the size.                            */
+ * each, copied raw), 2 the transposed fp32 stream of the fused backward pass, 3 the hoisted bf16x3 stream a bf16x3 handle carries behind
+ * stream 1 (what vanerf_query_samples_vp runs on: three first layers packed with their per-sample k-pairs only).  out[cap] or NULL: the size. */
 int vanerf_weights_stream_host(const VanerfWeightTable* w, int which, float* out, int64_t cap, int64_t* n_out);
 /* The streams a handle holds on the device, copied back to host memory (blocking; for tests of vanerf_weights_update): which = 0 the forward
- * stream of the handle's mode, 2 the backward stream (fp32 handles only).                                                                       */
+ * stream of the handle's mode, 2 the backward stream (fp32 handles only), 3 the hoisted bf16x3 stream (bf16x3 handles only).                     */
 int vanerf_weights_download(const VanerfWeights* w, int which, float* out, int64_t cap, int64_t* n_out);
 
 /* a1-a4  Pixel grid, ray generation, bbox clipping, coarse depths (src/model.py:1191-1238, 1496-1570).
@@ -233,6 +234,19 @@ int vanerf_query_samples(const VanerfWeights* w, const VanerfFrame* frame, const
                          const uint8_t* query_vis, const int32_t* knn_idx, const float* noise, const int32_t* order, int raw, int64_t n,
                          float* out, uint8_t* valid, void* queue_word /* as for vanerf_mesh_query_accel */, void* stream);
 
+/* The per-vertex half of three first layers, once per source frame (bf16x3 handles).  geo_vis_fusion.fconv_at.0, geo_vis_fusion.fconv_ated.0 and
+ * tex_vis_fusion.fconv_at.0 (src/networks.py:86-93, 285-288) multiply, per sample, rows of the frame's vertex tables that depend only on the
+ * sample's 1-NN vertex; their products are a fixed vector per vertex: table = [A0 | N0 | T0 | P] (vanerf_amd/csrc/layer_spec.h), fp32, evaluated in
+ * fp32 in a fixed order (two builds give the same bits).  table == NULL: returns the number of floats needed (> 0).  Otherwise one launch on
+ * `stream` into table[cap_floats] (16-byte aligned; no allocation, no host synchronisation), returns 0; < 0: error.  The table belongs to
+ * (handle contents, frame): rebuild it after vanerf_weights_update -- the library keeps no cache.                                          */
+int vanerf_vertex_products(const VanerfWeights* w, const VanerfFrame* frame, float* table, int64_t cap_floats, void* stream);
+/* vanerf_query_samples with that table: the hoisted bf16x3 kernel starts the three layers' accumulators from the gathered table rows and runs
+ * their per-sample k-steps only (outputs within 1e-5 of vanerf_query_samples': summation order).  vertex_products == NULL is vanerf_query_samples. */
+int vanerf_query_samples_vp(const VanerfWeights* w, const VanerfFrame* frame, const float* pts, const float* query_sdf,
+                            const uint8_t* query_vis, const int32_t* knn_idx, const float* noise, const int32_t* order, int raw, int64_t n,
+                            float* out, uint8_t* valid, void* queue_word, const float* vertex_products, void* stream);
+
 /* Validity partition for vanerf_query_samples: order[N] = the samples whose projection hits the source view and its foreground mask
  * (src/model.py:780-803), in their order, then the others, in their order.  A 32-sample group of vanerf_query_samples in which no sample
  * is valid skips the geometry networks; with this order only one group per launch is mixed.  scratch: device memory of at least
@@ -330,6 +344,11 @@ int vanerf_render_pass(const VanerfWeights* w, const VanerfFrame* frame, const V
                        const int32_t* faces, int nf, const VanerfPassDesc* desc, const VanerfPassOut* out, void* scratch, int64_t scratch_bytes,
                        void* stream);
 
+/* ... with the frame's table of vanerf_vertex_products for the pass's per-sample launches (NULL: vanerf_render_pass itself) */
+int vanerf_render_pass_vp(const VanerfWeights* w, const VanerfFrame* frame, const VanerfMeshAccel* accel, const float* verts, int nv,
+                          const int32_t* faces, int nf, const VanerfPassDesc* desc, const VanerfPassOut* out, void* scratch, int64_t scratch_bytes,
+                          const float* vertex_products, void* stream);
+
 /* One pass over n_views target views of the same source frame that share a pixel grid (the frames of an orbit, the views of a validation step):
  * the kernels of vanerf_render_pass once over n_views * nx * ny rays instead of n_views times over nx * ny.  Behind the ray setup nothing
  * depends on the camera but the ray origin, so view v's slice of every output holds the bits vanerf_render_pass gives for that camera alone.
@@ -352,6 +371,10 @@ int64_t vanerf_render_pass_views_scratch(int n_views, int rays_per_view, int Sc,
 int vanerf_render_pass_views(const VanerfWeights* w, const VanerfFrame* frame, const VanerfMeshAccel* accel, const float* verts, int nv,
                              const int32_t* faces, int nf, const VanerfViewsDesc* desc, const VanerfPassOut* out, void* scratch,
                              int64_t scratch_bytes, void* stream);
+
+int vanerf_render_pass_views_vp(const VanerfWeights* w, const VanerfFrame* frame, const VanerfMeshAccel* accel, const float* verts, int nv,
+                                const int32_t* faces, int nf, const VanerfViewsDesc* desc, const VanerfPassOut* out, void* scratch,
+                                int64_t scratch_bytes, const float* vertex_products /* as vanerf_render_pass_vp */, void* stream);
 
 /* Training step, backward of the row gathers (bilinear taps of feat_sample, src/utils.py:136-151; nearest / twin vertex rows of KNN_vis,
  * src/networks.py:27-33):  table[idx[i]][0..C) += w[i] * g[i][0..C)  for i < n  (w may be NULL = 1; rows outside [0, R) are ignored).

@@ -17,3 +17,6 @@ timed("FrameData (all)", mk)
 timed("  tex_global_vertex_feature", lambda: R.tex_global_vertex_feature(sdd, fd["feat_tex"], fd["img_in"]))
 timed("  vertex_visibility (raster)", lambda: R.vertex_visibility(f0.vert_xy01, f0.vert_z01, f0.faces))
 timed("  MeshAccel", lambda: R.MeshAccel(f0.verts3, f0.faces))
+# not part of FrameData (it needs the geometry weights): built at the frame's first pass with a bf16x3 handle, so bench.py's frame_setup_ms does not see it
+w1 = R.PackedWeights(sd, mode="bf16x3")
+timed("first pass: vertex products table", lambda: R.build_vertex_products(w1, f0))

@@ -15,6 +15,7 @@ ap.add_argument("--iters", type=int, default=5)
 ap.add_argument("--rows", type=int, default=512)
 ap.add_argument("--mode", type=int, default=0, help="0 = fp32 MFMA, 1 = split-bf16 x3")
 ap.add_argument("--order", type=int, default=1, help="1: work order from the validity partition (what render_pass does), 0: natural order")
+ap.add_argument("--vertex-products", type=int, default=1, help="mode 1: 1 = the hoisted kernel on the frame's table of per-vertex products (the default path), 0 = the un-hoisted kernel")
 args = ap.parse_args()
 sd = synth.make_full_weights(0)
 frame = synth.make_frame(seed=11, tar_h=512, tar_w=334, orbit_deg=15.0)
@@ -26,13 +27,19 @@ rays = R.ray_setup(frame["cam_tar"], frame["bounds"], 0, 0, 1, 334, args.rows, 6
 pts = R.sample_points(rays["rays_d"], rays["cam_pos"], rays["z"])
 q_sdf, q_vis, knn = R.mesh_query_accel(fdat.accel, fdat.verts3, fdat.faces, fdat.vert_vis, pts)
 order = R.query_order(fdat, pts) if args.order else None
-out = R.query_samples(w, fdat, pts, q_sdf, q_vis, knn, order=order)
+vp = fdat.vertex_products(w) if args.vertex_products else None  # None for fp32 handles
+if vp is not None:
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record(); R.build_vertex_products(w, fdat); e1.record(); torch.cuda.synchronize()
+    print(f"table of per-vertex products: {vp.numel() * 4 / 1e6:.2f} MB, build {e0.elapsed_time(e1):.3f} ms")
+out = R.query_samples(w, fdat, pts, q_sdf, q_vis, knn, order=order, vertex_products=vp)
 torch.cuda.synchronize()
 ts = []
 for _ in range(args.iters):
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
-    out = R.query_samples(w, fdat, pts, q_sdf, q_vis, knn, order=order)
+    out = R.query_samples(w, fdat, pts, q_sdf, q_vis, knn, order=order, vertex_products=vp)
     e1.record()
     torch.cuda.synchronize()
     ts.append(e0.elapsed_time(e1))

@@ -104,6 +104,8 @@ _SIGS = {
                                         _FP, c_void_p]),
     "vanerf_knn1": (c_int, [_FP, c_int, _FP, c_int64, _FP, c_void_p]),
     "vanerf_query_samples": (c_int, [c_void_p, POINTER(VanerfFrame), _FP, _FP, _FP, _FP, _FP, _FP, c_int, c_int64, _FP, _FP, _FP, c_void_p]),
+    "vanerf_vertex_products": (c_int, [c_void_p, POINTER(VanerfFrame), _FP, c_int64, c_void_p]),
+    "vanerf_query_samples_vp": (c_int, [c_void_p, POINTER(VanerfFrame), _FP, _FP, _FP, _FP, _FP, _FP, c_int, c_int64, _FP, _FP, _FP, _FP, c_void_p]),
     "vanerf_query_forward_spill": (c_int, [c_void_p, POINTER(VanerfFrame), _FP, _FP, _FP, _FP, c_int64, c_int64, _FP, _FP, _FP, _FP, _FP, c_void_p]),
     "vanerf_query_backward": (c_int, [c_void_p, _FP, _FP, _FP, _FP, _FP, _FP, c_int64, c_int64, _FP, _FP, _FP, _FP, c_void_p]),
     "vanerf_weight_products": (c_int, [_FP, _FP, c_int64, c_int, c_int, _FP, c_void_p]),
@@ -123,6 +125,10 @@ _SIGS = {
     "vanerf_render_pass_scratch": (c_int64, [c_int, c_int, c_int, c_int, c_int]),
     "vanerf_render_pass": (c_int, [c_void_p, POINTER(VanerfFrame), POINTER(VanerfMeshAccel), _FP, c_int, _FP, c_int, POINTER(VanerfPassDesc),
                                    POINTER(VanerfPassOut), _FP, c_int64, c_void_p]),
+    "vanerf_render_pass_vp": (c_int, [c_void_p, POINTER(VanerfFrame), POINTER(VanerfMeshAccel), _FP, c_int, _FP, c_int, POINTER(VanerfPassDesc),
+                                      POINTER(VanerfPassOut), _FP, c_int64, _FP, c_void_p]),
+    "vanerf_render_pass_views_vp": (c_int, [c_void_p, POINTER(VanerfFrame), POINTER(VanerfMeshAccel), _FP, c_int, _FP, c_int, POINTER(VanerfViewsDesc),
+                                            POINTER(VanerfPassOut), _FP, c_int64, _FP, c_void_p]),
     "vanerf_render_pass_views_scratch": (c_int64, [c_int, c_int, c_int, c_int, c_int, c_int]),
     "vanerf_render_pass_views": (c_int, [c_void_p, POINTER(VanerfFrame), POINTER(VanerfMeshAccel), _FP, c_int, _FP, c_int, POINTER(VanerfViewsDesc),
                                          POINTER(VanerfPassOut), _FP, c_int64, c_void_p]),

@@ -26,18 +26,22 @@ extern "C" int vanerf_weights_pack(const VanerfWeightTable* w, int mode, VanerfW
         constexpr size_t n_ptrs = offsetof(VanerfWeightTable, sigmoid_beta) / sizeof(const float*);
         for (size_t i = 0; i < n_ptrs; ++i)
             if (!ptrs[i]) throw_error("vanerf_weights_pack: weight pointer #%d is null", (int)i);
-        std::vector<float> host, host_bwd;
+        std::vector<float> host, host_bwd, host_h, eff;
         LayerOffsets offs{};
-        pack_weights_host(*w, host, offs, mode, mode == 0 ? &host_bwd : nullptr);
+        pack_weights_host(*w, host, offs, mode, mode == 0 ? &host_bwd : nullptr, mode == 1 ? &host_h : nullptr, mode == 1 ? &eff : nullptr);
         auto* h = new VanerfWeights();
         h->n_floats_bwd = host_bwd.size();
         h->n_floats = host.size();
+        h->n_floats_h = host_h.size();
         h->offs = offs;
         h->mode = mode;
         h->beta = w->sigmoid_beta < 2e-3f ? 2e-3f : w->sigmoid_beta; // sdf_activation clamp (src/model.py:880)
         hipError_t e = hipGetDevice(&h->device);
-        if (e == hipSuccess) e = hipMalloc(&h->dev, host.size() * sizeof(float));
+        if (e == hipSuccess) e = hipMalloc(&h->dev, (host.size() + host_h.size()) * sizeof(float));
         if (e == hipSuccess) e = hipMemcpy(h->dev, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice);
+        if (e == hipSuccess && !host_h.empty()) e = hipMemcpy(h->dev + host.size(), host_h.data(), host_h.size() * sizeof(float), hipMemcpyHostToDevice);
+        if (e == hipSuccess && !eff.empty()) e = hipMalloc(&h->dev_eff, eff.size() * sizeof(float));
+        if (e == hipSuccess && !eff.empty()) e = hipMemcpy(h->dev_eff, eff.data(), eff.size() * sizeof(float), hipMemcpyHostToDevice);
         if (e == hipSuccess && !host_bwd.empty()) e = hipMalloc(&h->dev_bwd, host_bwd.size() * sizeof(float));
         if (e == hipSuccess && !host_bwd.empty()) e = hipMemcpy(h->dev_bwd, host_bwd.data(), host_bwd.size() * sizeof(float), hipMemcpyHostToDevice);
         if (e == hipSuccess) e = hipMalloc(&h->stats, sizeof(unsigned long long));
@@ -49,6 +53,7 @@ extern "C" int vanerf_weights_pack(const VanerfWeightTable* w, int mode, VanerfW
             if (h->dev_bwd) (void)hipFree(h->dev_bwd);
             if (h->stats) (void)hipFree(h->stats);
             if (h->dev_beta) (void)hipFree(h->dev_beta);
+            if (h->dev_eff) (void)hipFree(h->dev_eff);
             delete h;
             hip_check(e, "vanerf_weights_pack: device upload");
         }
@@ -86,17 +91,17 @@ extern "C" int vanerf_weights_pack_host(const VanerfWeightTable* w, float* out, 
     });
 }
 
-// Host-only view of any of the three streams a handle can carry: which = 0 the fp32 forward stream, 1 the bf16x3 forward stream (32-bit words
-// of two bf16 each, returned as raw floats), 2 the transposed fp32 stream of the fused backward pass.
+// Host-only view of any of the streams a handle can carry: which = 0 the fp32 forward stream, 1 the bf16x3 forward stream (32-bit words
+// of two bf16 each, returned as raw floats), 2 the transposed fp32 stream of the fused backward pass, 3 the hoisted bf16x3 stream (layer_spec.h).
 extern "C" int vanerf_weights_stream_host(const VanerfWeightTable* w, int which, float* out, int64_t cap, int64_t* n_out)
 {
     return guarded([&] {
         if (!w || !n_out) throw_error("vanerf_weights_stream_host: null argument");
-        if (which < 0 || which > 2) throw_error("vanerf_weights_stream_host: which = %d (0 fp32, 1 bf16x3, 2 backward)", which);
-        std::vector<float> host, bwd;
+        if (which < 0 || which > 3) throw_error("vanerf_weights_stream_host: which = %d (0 fp32, 1 bf16x3, 2 backward, 3 hoisted bf16x3)", which);
+        std::vector<float> host, bwd, hoisted;
         LayerOffsets offs{};
-        pack_weights_host(*w, host, offs, which == 1 ? 1 : 0, which == 2 ? &bwd : nullptr);
-        const std::vector<float>& src = which == 2 ? bwd : host;
+        pack_weights_host(*w, host, offs, which == 1 ? 1 : 0, which == 2 ? &bwd : nullptr, which == 3 ? &hoisted : nullptr);
+        const std::vector<float>& src = which == 2 ? bwd : which == 3 ? hoisted : host;
         *n_out = (int64_t)src.size();
         if (out) {
             if (cap < (int64_t)src.size()) throw_error("vanerf_weights_stream_host: buffer too small");
@@ -111,9 +116,9 @@ extern "C" int vanerf_weights_download(const VanerfWeights* w, int which, float*
 {
     return guarded([&] {
         if (!w || !n_out) throw_error("vanerf_weights_download: null argument");
-        if (which != 0 && which != 2) throw_error("vanerf_weights_download: which = %d (0 forward, 2 backward)", which);
-        const float* src = which ? w->dev_bwd : w->dev;
-        const size_t n = which ? w->n_floats_bwd : w->n_floats;
+        if (which != 0 && which != 2 && which != 3) throw_error("vanerf_weights_download: which = %d (0 forward, 2 backward, 3 hoisted bf16x3)", which);
+        const float* src = which == 2 ? w->dev_bwd : which == 3 ? (w->n_floats_h ? w->dev + w->n_floats : nullptr) : w->dev;
+        const size_t n = which == 2 ? w->n_floats_bwd : which == 3 ? w->n_floats_h : w->n_floats;
         if (!src) throw_error("vanerf_weights_download: the handle carries no such stream");
         *n_out = (int64_t)n;
         if (out) {

@@ -63,7 +63,10 @@ int guarded(F&& fn) noexcept
     }
 }
 
-void pack_weights_host(const VanerfWeightTable& w, std::vector<float>& out, LayerOffsets& offs, int mode = 0, std::vector<float>* bwd = nullptr);
+// hoisted: the second bf16x3 stream (layer_spec.h), eff_out: the effective weights themselves (stage 1 below)
+void pack_weights_host(const VanerfWeightTable& w, std::vector<float>& out, LayerOffsets& offs, int mode = 0, std::vector<float>* bwd = nullptr,
+                       std::vector<float>* hoisted = nullptr, std::vector<float>* eff_out = nullptr);
+unsigned eff_layer_offset(int l); // where layer l's [nout][kin] matrix starts in eff
 // The packer's two stages (weights_pack.cpp): where a layer's parameters are and where its effective weights go in the flat array `eff` ...
 struct LayerSrc {
     const float* w; // [nout][kin] (weight-normed layers: weight_v)
@@ -76,7 +79,7 @@ void layer_sources(const VanerfWeightTable& w, LayerSrc out[NUM_LAYERS]);
 // ... and the placement of eff in the streams: out[i] = id ? eff[id - 1] : 0.  fwd / bwd: the fp32 forward stream and the transposed stream of
 // the fused backward; fwd_b: the bf16x3 stream, two ints per 32-bit word (low half's id | part << 30, high half's id; part 0 = high bf16 part).
 struct PackTables {
-    std::vector<int> fwd, bwd, fwd_b;
+    std::vector<int> fwd, bwd, fwd_b, fwd_bh; // fwd_bh: the hoisted bf16x3 stream (layer_spec.h)
     LayerOffsets offs{};
     unsigned n_eff = 0;
 };
@@ -93,7 +96,8 @@ void composite_with_handle(const VanerfWeights* w, const float* rgba, const floa
 } // namespace vanerf
 
 struct VanerfWeights {
-    float* dev = nullptr;   // packed fragment streams
+    float* dev = nullptr;   // packed fragment streams; bf16x3 handles: [the stream | the hoisted stream (layer_spec.h)]
+    size_t n_floats_h = 0;  // 32-bit words of the hoisted stream, which starts at dev + n_floats (bf16x3 handles only)
     float* dev_bwd = nullptr; // fp32 handles only: the transposed streams of the fused backward pass (query_backward.hip)
     size_t n_floats_bwd = 0;
     size_t n_floats = 0;
@@ -101,7 +105,8 @@ struct VanerfWeights {
     int mode = 0;
     float beta = 0.1f;      // sigmoid_beta as packed from the host (clamped); stale once vanerf_weights_update took it from the device ...
     float* dev_beta = nullptr; // ... so the passes' composites read this device copy (one float, clamped)
-    float* dev_eff = nullptr;  // vanerf_weights_update's stage 1: the effective weights (allocated at the first update)
+    float* dev_eff = nullptr;  // the effective weights, stage 1 of the packer: what vanerf_vertex_products multiplies (bf16x3 handles: uploaded at
+                               // the pack) and what vanerf_weights_update folds into (fp32 handles: allocated at the first update)
     int device = 0;
     unsigned long long* stats = nullptr; // [0]: running count of 32-sample groups that took query_kernel's all-invalid short path
 };

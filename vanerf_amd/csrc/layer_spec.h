@@ -62,14 +62,38 @@ constexpr unsigned layer_offset(int l)
 // ---- split-bf16 ("bf16x3") stream: W = W_hi + W_lo (two bf16), one k-step of v_mfma_f32_32x32x16_bf16 covers 8 consecutive
 // k-pairs of the fp32 ordering (lane half h supplies its 8 channels), three products per step: W_hi X_hi + W_hi X_lo + W_lo X_hi.
 // Layout of a layer: uint32 [S = ceil(T/8)][NB][2 (hi, lo)][64 lanes][4] -- each (step, block, part) is one coalesced 1 KB load.
-constexpr int steps_b(int l) { return (kT[l] + 7) / 8; }
-constexpr unsigned layer_dwords_b(int l) { return (unsigned)steps_b(l) * (unsigned)kNB[l] * 2u * 64u * 4u; }
-constexpr unsigned layer_offset_b(int l)
+//
+// A bf16x3 handle carries a second, HOISTED stream behind the first.  Three first layers have no bias and nothing in front of their matrix
+// product, and part of their input depends only on the sample's 1-NN vertex i (twin vertex tw(i) = (i + 779) mod 1558) and the source frame:
+//   L_GEO_AT0_A / L_GEO_ATED0_A  columns 64..191 = vfeat0[i] | vfeat0[tw(i)]            (64 of 98 k-pairs)
+//   L_TEX_AT_A                   columns 11..68  = vfeat_tex[i] | vfeat_tex[tw(i)] rows  (29 of 49 k-pairs)
+// Those products come from a per-frame table (vertex_products.hip) as the accumulators' initial values; the hoisted stream of the three
+// layers holds the per-sample k-pairs only: [pix32 | (sdf, qvis) | (vis_nn, vis_tw)] and [query6 | latent12 | (qvis, vis_nn) | (vis_tw, -)].
+constexpr int kT_b(int l, bool hoist)
+{
+    if (hoist && (l == L_GEO_AT0_A || l == L_GEO_ATED0_A)) return 32 + 2;
+    if (hoist && l == L_TEX_AT_A) return 6 + 12 + 2;
+    return kT[l];
+}
+constexpr int steps_b(int l, bool hoist = false) { return (kT_b(l, hoist) + 7) / 8; }
+constexpr unsigned layer_dwords_b(int l, bool hoist = false) { return (unsigned)steps_b(l, hoist) * (unsigned)kNB[l] * 2u * 64u * 4u; }
+constexpr unsigned layer_offset_b(int l, bool hoist = false)
 {
     unsigned o = 0;
-    for (int i = 0; i < l; ++i) o += layer_dwords_b(i);
+    for (int i = 0; i < l; ++i) o += layer_dwords_b(i, hoist);
     return o;
 }
+
+// The table of per-vertex products (vanerf_vertex_products), fp32, four sub-tables one after the other.  A vertex's row of a sub-table with NB
+// output blocks is [lane half h][block ob][register r] = output row 32 ob + (r & 3) + 8 (r >> 2) + 4 h of the layer: the D-register order, so
+// a lane's 16 values of a block are four consecutive 16-byte loads.  Rows beyond the layer's outputs hold 0.
+//   A0[i] = Wat[:, 64:128] vfeat0[i] + Wat[:, 128:192] vfeat0[tw(i)]          [2][8]      (10 rows: registers 0..5 / 0..3)
+//   N0[i] = Wated[:, 64:128] vfeat0[i],  T0[i] = Wated[:, 128:192] vfeat0[tw(i)]   [2][2][16] each (scaled by the sample's gates a1, a2)
+//   P[i]  = Wtex_at[:, 11:22 | 33:51] vfeat_tex[i][:29] + Wtex_at[:, 22:33 | 51:69] vfeat_tex[tw(i)][:29]   [2][3][16]
+constexpr unsigned VP_NV = 1558u;
+constexpr unsigned VP_A0_ROW = 16u, VP_N0_ROW = 64u, VP_P_ROW = 96u;
+constexpr unsigned VP_A0 = 0u, VP_N0 = VP_A0 + VP_NV * VP_A0_ROW, VP_T0 = VP_N0 + VP_NV * VP_N0_ROW, VP_P = VP_T0 + VP_NV * VP_N0_ROW;
+constexpr unsigned VP_FLOATS = VP_P + VP_NV * VP_P_ROW;
 
 // ---- training: spills of the fused backward pass (query_backward.hip) ---------------------------------------
 // The forward kernel in spill mode writes every layer's B operands X (the layer's inputs after the previous activation, slot (t, h) = k-pair t

@@ -83,6 +83,7 @@ struct Marches {
     int rays_per_view;        // 0: one origin L.cam_pos[3] for every ray; else ray r starts at L.cam_pos[r / rays_per_view][4]
     int grid_nx, grid_ny;     // ray-grid hint of the mesh query (0, 0: none); a pass over V views stacks their rows: (nx, V * ny)
     const float *u, *t_lin_f, *noise_c, *noise_f;
+    const float* vertex_products; // the frame's table for the per-sample launches, or NULL (vanerf_query_samples_vp)
 };
 
 void run_marches(const VanerfWeights* w, const VanerfFrame* frame, const VanerfMeshAccel* accel, const float* verts, int nv, const int32_t* faces, int nf,
@@ -112,7 +113,8 @@ void run_marches(const VanerfWeights* w, const VanerfFrame* frame, const VanerfM
             ok(vanerf_query_order(frame, L.pts, n, L.order, L.order_scratch, L.order_scratch_bytes, stream), "validity partition");
             order = L.order;
         }
-        ok(vanerf_query_samples(w, frame, L.pts, q_sdf, L.q_vis, L.knn, noise, order, valid_raw ? 1 : 0, n, rgba, valid_raw, qw + 1, stream), "per-sample networks");
+        ok(vanerf_query_samples_vp(w, frame, L.pts, q_sdf, L.q_vis, L.knn, noise, order, valid_raw ? 1 : 0, n, rgba, valid_raw, qw + 1, m.vertex_products, stream),
+           "per-sample networks");
     };
     if (reuse == 2) { // the networks once per point; eval_func with the coarse draws here, with the fine batch's draws below
         march(o.z, Sc, nullptr, L.q_sdf_c, L.raw_c, L.valid_c);
@@ -165,6 +167,13 @@ extern "C" int vanerf_render_pass(const VanerfWeights* w, const VanerfFrame* fra
                                   const int32_t* faces, int nf, const VanerfPassDesc* desc, const VanerfPassOut* out, void* scratch,
                                   int64_t scratch_bytes, void* stream)
 {
+    return vanerf_render_pass_vp(w, frame, accel, verts, nv, faces, nf, desc, out, scratch, scratch_bytes, nullptr, stream);
+}
+
+extern "C" int vanerf_render_pass_vp(const VanerfWeights* w, const VanerfFrame* frame, const VanerfMeshAccel* accel, const float* verts, int nv,
+                                     const int32_t* faces, int nf, const VanerfPassDesc* desc, const VanerfPassOut* out, void* scratch,
+                                     int64_t scratch_bytes, const float* vertex_products, void* stream)
+{
     return guarded([&] {
         if (!w || !frame || !accel || !verts || !faces || !desc || !out || !scratch) throw_error("vanerf_render_pass: null argument");
         const VanerfPassDesc& d = *desc;
@@ -190,7 +199,7 @@ extern "C" int vanerf_render_pass(const VanerfWeights* w, const VanerfFrame* fra
                                            d.jitter, o.index, L.rays_d, L.cam_pos, L.near, L.far, o.hit, o.z, stream));
         const bool grid = d.pixels_xy == nullptr;
         run_marches(w, frame, accel, verts, nv, faces, nf,
-                    Marches{who, R, Sc, Sf, fine, reuse, 0, grid ? d.nx : 0, grid ? d.ny : 0, d.u, d.t_lin_f, d.noise_c, d.noise_f}, L, o, stream);
+                    Marches{who, R, Sc, Sf, fine, reuse, 0, grid ? d.nx : 0, grid ? d.ny : 0, d.u, d.t_lin_f, d.noise_c, d.noise_f, vertex_products}, L, o, stream);
     });
 }
 
@@ -207,6 +216,13 @@ extern "C" int64_t vanerf_render_pass_views_scratch(int n_views, int rays_per_vi
 extern "C" int vanerf_render_pass_views(const VanerfWeights* w, const VanerfFrame* frame, const VanerfMeshAccel* accel, const float* verts, int nv,
                                         const int32_t* faces, int nf, const VanerfViewsDesc* desc, const VanerfPassOut* out, void* scratch,
                                         int64_t scratch_bytes, void* stream)
+{
+    return vanerf_render_pass_views_vp(w, frame, accel, verts, nv, faces, nf, desc, out, scratch, scratch_bytes, nullptr, stream);
+}
+
+extern "C" int vanerf_render_pass_views_vp(const VanerfWeights* w, const VanerfFrame* frame, const VanerfMeshAccel* accel, const float* verts, int nv,
+                                           const int32_t* faces, int nf, const VanerfViewsDesc* desc, const VanerfPassOut* out, void* scratch,
+                                           int64_t scratch_bytes, const float* vertex_products, void* stream)
 {
     return guarded([&] {
         const char* const who = "vanerf_render_pass_views";
@@ -229,6 +245,6 @@ extern "C" int vanerf_render_pass_views(const VanerfWeights* w, const VanerfFram
             throw_error("vanerf_render_pass_views: scratch of %lld bytes, %lld needed (vanerf_render_pass_views_scratch)", (long long)scratch_bytes, (long long)L.total);
         ok_setup(who, vanerf_ray_setup_views(d.cams, V, d.x0, d.y0, d.step_x, d.step_y, d.nx, d.ny, d.width, d.bounds, Sc, d.t_lin_c, d.jitter, o.index, L.rays_d,
                                              L.cam_pos, L.near, L.far, o.hit, o.z, stream));
-        run_marches(w, frame, accel, verts, nv, faces, nf, Marches{who, R, Sc, Sf, fine, reuse, rpv, d.nx, V * d.ny, d.u, d.t_lin_f, nullptr, nullptr}, L, o, stream);
+        run_marches(w, frame, accel, verts, nv, faces, nf, Marches{who, R, Sc, Sf, fine, reuse, rpv, d.nx, V * d.ny, d.u, d.t_lin_f, nullptr, nullptr, vertex_products}, L, o, stream);
     });
 }

@@ -7,8 +7,11 @@
 // layers run as MFMA chains -- query_kernel<0>: v_mfma_f32_32x32x2_f32 on fp32 operands; query_kernel<1>:
 // v_mfma_f32_32x32x16_bf16 on split (hi + lo) operands, fp32 accumulate -- whose accumulators stay in registers
 // from the bilinear gathers to the final (alpha, sdf, rgb) store: activations never touch LDS or HBM.
-// No LDS at all: key points come through the scalar cache (fp32 kernel) or live in registers (bf16 kernel); the 1-NN
-// vertex index arrives from vanerf_mesh_query_accel.  Weights stream from L2 as pre-permuted MFMA A-fragments (weights_pack.cpp).
+// The fp32 kernel uses no LDS beyond its control words: key points come through the scalar cache, weights stream from L2 as pre-permuted
+// MFMA A-fragments (weights_pack.cpp).  The split-bf16 kernel owns its CU's LDS: key points, the resident fragments of the last layers and
+// the ring the eight waves of a block share the streamed fragments through (see the LDS map below).  The 1-NN vertex index arrives from
+// vanerf_mesh_query_accel.  query_kernel<1, false, true> is the HOISTED split-bf16 kernel: three first layers start from the per-vertex
+// products of vertex_products.hip and run their per-sample k-steps only (layer_spec.h).
 //
 // Built with -ffp-contract=off: the integer-valued outputs (1-NN index) depend on fp32 compare
 // results and must match oracle/mesh_oracle.c bit for bit; fused multiply-adds are spelled fmaf().
@@ -81,6 +84,7 @@ struct QueryParams {
     unsigned* queue;            // work-queue head: next unclaimed 32-sample group (zero before the launch)
     unsigned long long* short_groups; // optional: += number of groups that took the all-invalid short path
     float wm1[4], hm1[4];             // (float)(W - 1), (float)(H - 1) of the image / tex / geo0 / geo1 maps (kept scalar: no per-lane copies)
+    const float* vp;                  // hoisted kernel: the table of per-vertex products (vertex_products.hip), else unused
     float *xs, *aux;                  // spill mode (training): X and auxiliary spills, [rows][npad] floats (layer_spec.h)
     long long npad;
 };
@@ -138,7 +142,9 @@ struct FragB { u32x4 hi, lo; }; // A fragments (hi and lo parts) of one 32-row o
 #define VANERF_LDS_FIRST (VANERF_RING ? 15 /* L_IBR */ : 13 /* L_HEAD1 */)
 #endif
 constexpr int LDS_FIRST = VANERF_LDS_FIRST;
-constexpr unsigned RES_BASE_DW = layer_offset_b(LDS_FIRST), RES_DW = layer_offset_b(NUM_LAYERS) - layer_offset_b(LDS_FIRST);
+// (HOIST: the hoisted stream of layer_spec.h -- three layers are shorter, so every offset, the ring's phases and the resident size differ)
+template <bool HOIST> constexpr unsigned RES_BASE_DW = layer_offset_b(LDS_FIRST, HOIST);
+template <bool HOIST> constexpr unsigned RES_DW = layer_offset_b(NUM_LAYERS, HOIST) - layer_offset_b(LDS_FIRST, HOIST);
 // Two waves per SIMD (VANERF_WAVES_PER_SIMD_B == 2: 8-wave blocks, 256 registers per wave): nothing long-lived may sit in registers -- the
 // lane half's key points live in LDS behind the resident fragments (one ds_read_b128 per key point and group), gathers are issued right
 // before their use (the partner wave hides their latency), rings are one step deep.
@@ -151,14 +157,20 @@ constexpr unsigned RING_PHASE_PIECES = 16u, RING_BYTES = RING ? 2u * RING_PHASE_
 constexpr unsigned LDS_KPT = 0u, LDS_CTRL = 2u * PE_KPT_PER_HALF * 16u, LDS_LAT0 = 768u, LDS_RING = 1024u, LDS_RES = RING ? LDS_RING + RING_BYTES : 1024u;
 // [768, 896): ibr_compress of an all-zero pooled latent (its bias through the same MFMA chain), [lane half][16 registers]: what every sample of an
 // all-invalid group gets from that layer -- computed once per block, read by the short path instead of 27 MFMAs per group
-constexpr unsigned DYN_LDS_BYTES = LDS_RES + RES_DW * 4u;
+template <bool HOIST> constexpr unsigned DYN_LDS_BYTES = LDS_RES + RES_DW<HOIST> * 4u;
 // The streamed part of the fragment stream (layers 0 .. LDS_FIRST-1) as 1 KB pieces (one (k-step, output block, hi | lo) fragment each = one
 // LDS-DMA wave instruction), in the order the layers consume them; a PHASE is 16 consecutive pieces.
-constexpr unsigned RING_PIECES = RES_BASE_DW / 256u, RING_PHASES = ((RING_PIECES + RING_PHASE_PIECES - 1u) / RING_PHASE_PIECES + 1u) / 2u * 2u;
+template <bool HOIST> constexpr unsigned RING_PIECES = RES_BASE_DW<HOIST> / 256u;
+// RING_PHASES is even (phase P lives in half P % 2, and phase 0 of the next round must not land on the half the last phase is read from).  When the
+// stream has an odd number of phases (the hoisted stream: 31) nobody reads the last, padding phase, so no read begins it: the kernel begins it by
+// hand behind the last streamed layer (ring_close), which is what issues phase 0 of the next round.
+template <bool HOIST> constexpr unsigned RING_STREAM_PHASES = (RING_PIECES<HOIST> + RING_PHASE_PIECES - 1u) / RING_PHASE_PIECES;
+template <bool HOIST> constexpr unsigned RING_PHASES = (RING_STREAM_PHASES<HOIST> + 1u) / 2u * 2u;
 static_assert(!RING || VANERF_WPB_B == 8, "the ring's DMA schedule deals 2 pieces of a phase to each of 8 waves");
-static_assert(!RING || RING_PHASES * RING_PHASE_PIECES * 256u <= layer_offset_b(NUM_LAYERS), "the last phase's DMA must stay inside the stream");
+static_assert(!RING || RING_PHASES<false> * RING_PHASE_PIECES * 256u <= layer_offset_b(NUM_LAYERS), "the last phase's DMA must stay inside the stream");
+static_assert(!RING || RING_PHASES<true> * RING_PHASE_PIECES * 256u <= layer_offset_b(NUM_LAYERS, true), "the last phase's DMA must stay inside the hoisted stream");
 static_assert(LDS_CTRL + 8u + 2u * 4u * VANERF_WPB_B <= LDS_LAT0 && LDS_LAT0 + 128u <= LDS_RING, "control words / constant latent overlap their neighbours");
-static_assert(DYN_LDS_BYTES <= 160u * 1024u, "key points + control words + resident fragments must fit the CU's 160 KB");
+static_assert(DYN_LDS_BYTES<false> <= 160u * 1024u && DYN_LDS_BYTES<true> <= DYN_LDS_BYTES<false>, "key points + control words + resident fragments must fit the CU's 160 KB");
 extern __shared__ __attribute__((aligned(16))) u32x4 s_dyn[];
 typedef __attribute__((address_space(3))) u32x4 lds_u32x4_t;
 typedef __attribute__((address_space(3))) unsigned lds_u32_t;
@@ -219,8 +231,9 @@ template <unsigned P> __device__ __forceinline__ void ring_dma(WRsrc rs, const L
                  : "s"(la.dma_lds), "s"(la.dma_src), "i"(lds_off), "i"(src_off), "v"(la.w[0]), "s"(rs)
                  : "memory");
 }
-template <unsigned P> __device__ __forceinline__ void phase_begin(WRsrc rs, const LAddr& la)
+template <bool HOIST, unsigned P> __device__ __forceinline__ void phase_begin(WRsrc rs, const LAddr& la)
 {
+    constexpr unsigned RING_PHASES = ::RING_PHASES<HOIST>;
 #if defined(VANERF_EXP_RING) && VANERF_EXP_RING == 1 // timing experiments (results may be wrong): 1 no lgkmcnt wait, 2 no barrier, 3 no DMA, 4 nothing
     if constexpr (P > 0) asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
     ring_dma<(P + 1u) % RING_PHASES>(rs, la);
@@ -239,14 +252,22 @@ template <unsigned P> __device__ __forceinline__ void phase_begin(WRsrc rs, cons
 #endif
 }
 
-// DW: dword offset of the block's hi part in the stream (the lo part follows 1 KB later); the lane's 16 bytes sit at lane * 16
-template <bool RES, unsigned DW> __device__ __forceinline__ FragB wload_blk(WRsrc rs, const LAddr& la)
+// behind the last streamed layer of a full round: begins the padding phase of a stream with an odd number of phases (see RING_PHASES)
+template <bool HOIST> __device__ __forceinline__ void ring_close(WRsrc rs, const LAddr& la)
 {
+    if constexpr (RING && RING_STREAM_PHASES<HOIST> % 2u == 1u) phase_begin<HOIST, RING_PHASES<HOIST> - 1u>(rs, la);
+}
+
+// DW: dword offset of the block's hi part in the stream (the lo part follows 1 KB later); the lane's 16 bytes sit at lane * 16
+template <bool HOIST, bool RES, unsigned DW> __device__ __forceinline__ FragB wload_blk(WRsrc rs, const LAddr& la)
+{
+    constexpr unsigned RING_PHASES = ::RING_PHASES<HOIST>, RES_BASE_DW = ::RES_BASE_DW<HOIST>;
+    [[maybe_unused]] constexpr unsigned RES_DW = ::RES_DW<HOIST>;
     FragB r;
     if constexpr (RING && !RES) { // streamed layer, through the ring
         constexpr unsigned q = DW / 256u; // piece index of the hi part
         static_assert(q % 2u == 0 && q + 1u < RING_PHASES * RING_PHASE_PIECES, "block fragments are two consecutive pieces inside the streamed part");
-        if constexpr (q % RING_PHASE_PIECES == 0) phase_begin<q / RING_PHASE_PIECES>(rs, la);
+        if constexpr (q % RING_PHASE_PIECES == 0) phase_begin<HOIST, q / RING_PHASE_PIECES>(rs, la);
         r.hi = lds_frag<LDS_RING + (q % (2u * RING_PHASE_PIECES)) * 1024u>(la);
         r.lo = lds_frag<LDS_RING + ((q + 1u) % (2u * RING_PHASE_PIECES)) * 1024u>(la);
         return r;
@@ -275,13 +296,13 @@ template <bool RES, unsigned DW> __device__ __forceinline__ FragB wload_blk(WRsr
 }
 
 // Block fragment i of a layer = (k-step i / NB, output block i % NB) lies i * 512 dwords into the layer's stream.
-template <int NB, int T, bool RES, unsigned SBASE_DW> __device__ __forceinline__ RingB<NB> ring_start_b(WRsrc rs, const LAddr& la)
+template <bool HOIST, int NB, int T, bool RES, unsigned SBASE_DW> __device__ __forceinline__ RingB<NB> ring_start_b(WRsrc rs, const LAddr& la)
 {
     constexpr int D = RingDepthB<NB>::value, S = (T + 7) / 8;
     RingB<NB> r;
     static_for<D>([&](auto ic) {
         constexpr int i = decltype(ic)::value;
-        if constexpr (i < S * NB) r.b[i] = wload_blk<RES, SBASE_DW + i * 512u>(rs, la);
+        if constexpr (i < S * NB) r.b[i] = wload_blk<HOIST, RES, SBASE_DW + i * 512u>(rs, la);
     });
     __builtin_amdgcn_sched_barrier(0x000F); // keep the ring fill where it is written: ahead of the previous layer's epilogue
     return r;
@@ -305,7 +326,7 @@ struct NoPre { template <class C> __device__ __forceinline__ void operator()(C) 
 // So: step s's MFMAs are cut into four chunks, after each chunk comes one pair-split of step s+1's operands (5 VALU), the re-load of
 // the consumed ring slot is issued before the first chunk, and a sched_barrier(0) after every chunk keeps that order.
 // (sched_group_barrier could request the same interleave, but its solver did not finish on this 10 k-instruction block in 15 min.)
-template <int NB, int T, bool RES, unsigned SBASE_DW, int PRODS = 3, class Op, class Pre = NoPre>
+template <bool HOIST, int NB, int T, bool RES, unsigned SBASE_DW, int PRODS = 3, class Op, class Pre = NoPre>
 __device__ __forceinline__ void run_layer_b(f32x16 (&acc)[NB], RingB<NB>& ring, WRsrc rs, const LAddr& la, Op&& operand,
                                             Pre&& pre = Pre{})
 {
@@ -343,7 +364,7 @@ __device__ __forceinline__ void run_layer_b(f32x16 (&acc)[NB], RingB<NB>& ring, 
                 if constexpr (m * NCH / (3 * NB) == c) {
                     if constexpr (pr == 0) {
                         a[ob] = ring.b[idx % D];
-                        if constexpr (idx + D < S * NB) ring.b[idx % D] = wload_blk<RES, SBASE_DW + (idx + D) * 512u>(rs, la);
+                        if constexpr (idx + D < S * NB) ring.b[idx % D] = wload_blk<HOIST, RES, SBASE_DW + (idx + D) * 512u>(rs, la);
                     }
                     if constexpr (pr == 0 || (pr == 1 && PRODS == 3) || (pr == 2 && PRODS >= 2)) {
                         const bf16x8 wh = __builtin_bit_cast(bf16x8, a[ob].hi), wl = __builtin_bit_cast(bf16x8, a[ob].lo);
@@ -392,13 +413,13 @@ template <int K> __device__ __forceinline__ void spill_aux(const LLane& la, floa
 template <int MODE> struct LaneSel { using type = LLane; };
 template <> struct LaneSel<1> { using type = LAddr; };
 __device__ __forceinline__ unsigned lane_of(const LLane& la) { return (unsigned)la.lane; }
-template <int MODE, int NB, int T, int L> __device__ __forceinline__ typename RingSel<MODE, NB>::type ring_start_m(WRsrc rs, const typename LaneSel<MODE>::type& la)
+template <int MODE, bool HOIST, int NB, int T, int L> __device__ __forceinline__ typename RingSel<MODE, NB>::type ring_start_m(WRsrc rs, const typename LaneSel<MODE>::type& la)
 {
     if constexpr (MODE == 0) return ring_start<NB, T>(rs, layer_offset(L), lane_of(la) * NB * 4u);
-    else return ring_start_b<NB, T, (L >= LDS_FIRST), layer_offset_b(L)>(rs, la);
+    else return ring_start_b<HOIST, NB, T, (L >= LDS_FIRST), layer_offset_b(L, HOIST)>(rs, la);
 }
 
-template <int MODE, int NB, int T, int L, class Op>
+template <int MODE, bool HOIST, int NB, int T, int L, class Op>
 __device__ __forceinline__ void run_layer_m(f32x16 (&acc)[NB], typename RingSel<MODE, NB>::type& ring, WRsrc rs, const typename LaneSel<MODE>::type& la, Op&& operand)
 {
     if constexpr (MODE == 0)
@@ -407,7 +428,7 @@ __device__ __forceinline__ void run_layer_m(f32x16 (&acc)[NB], typename RingSel<
             spill_x<L, decltype(tc)::value>(la, b); // (spill mode only)
             return b;
         });
-    else run_layer_b<NB, T, (L >= LDS_FIRST), layer_offset_b(L), (((VANERF_P1_MASK >> L) & 1) ? 1 : ((VANERF_P2_MASK >> L) & 1) ? 2 : 3)>(acc, ring, rs, la, static_cast<Op&&>(operand));
+    else run_layer_b<HOIST, NB, T, (L >= LDS_FIRST), layer_offset_b(L, HOIST), (((VANERF_P1_MASK >> L) & 1) ? 1 : ((VANERF_P2_MASK >> L) & 1) ? 2 : 3)>(acc, ring, rs, la, static_cast<Op&&>(operand));
 }
 
 // lane id from v_mbcnt, not from a register that would have to stay live (or be spilled) across the whole sample loop
@@ -558,7 +579,7 @@ __device__ __forceinline__ Projected project_and_mask(const VanerfFrame& F, floa
 // one GeoVisFusion scale (src/networks.py:83-94 / 96-104): gates, gated 2-layer MLP.
 //   HC = channels per lane half (32 for the 64-channel map, 4 for the 8-channel map), NBO = output blocks,
 //   NREG_MID = registers of the last hidden block that carry real channels
-template <int MODE, int HC, int NBO, int NREG_MID, int l_at_a>
+template <int MODE, bool HOIST, int HC, int NBO, int NREG_MID, int l_at_a>
 __device__ __forceinline__ void geo_scale(WRsrc W, int lane, const typename LaneSel<MODE>::type& la, typename RingSel<MODE, 1>::type& ring_at,
                                           float (&pix)[HC], float (&nn)[HC], float (&tw)[HC], float s0, float s1,
                                           f32x16 (&outacc)[NBO])
@@ -575,13 +596,13 @@ __device__ __forceinline__ void geo_scale(WRsrc W, int lane, const typename Lane
     };
     f32x16 at[1];
     zero<1>(at);
-    run_layer_m<MODE, 1, TIN, l_at_a>(at, ring_at, W, la, input);
-    auto r_gate = ring_start_m<MODE, 1, 6, l_at_a + 1>(W, la);
-    auto r_mid = ring_start_m<MODE, NBO, TIN, l_at_a + 2>(W, la);
+    run_layer_m<MODE, HOIST, 1, TIN, l_at_a>(at, ring_at, W, la, input);
+    auto r_gate = ring_start_m<MODE, HOIST, 1, 6, l_at_a + 1>(W, la);
+    auto r_mid = ring_start_m<MODE, HOIST, NBO, TIN, l_at_a + 2>(W, la);
     if constexpr (MODE == 0) relu<1>(at);
     f32x16 gate[1];
     zero<1>(gate);
-    run_layer_m<MODE, 1, 6, l_at_a + 1>(gate, r_gate, W, la, [&](auto tc) -> float { return lazy_act<MODE, ACT_RELU>(at[0][decltype(tc)::value]); });
+    run_layer_m<MODE, HOIST, 1, 6, l_at_a + 1>(gate, r_gate, W, la, [&](auto tc) -> float { return lazy_act<MODE, ACT_RELU>(at[0][decltype(tc)::value]); });
     // gates live in rows 0..2 = registers 0..2 of the h = 0 lanes
     const float a0 = __shfl(sigmoid_f(gate[0][0]), lane & 31);
     const float a1 = __shfl(sigmoid_f(gate[0][1]), lane & 31);
@@ -591,18 +612,71 @@ __device__ __forceinline__ void geo_scale(WRsrc W, int lane, const typename Lane
     for (int t = 0; t < HC; ++t) { pix[t] *= a0; nn[t] *= a1; tw[t] *= a2; }
     f32x16 mid[NBO];
     zero<NBO>(mid);
-    run_layer_m<MODE, NBO, TIN, l_at_a + 2>(mid, r_mid, W, la, input);
-    auto r_out = ring_start_m<MODE, NBO, TOUT, l_at_a + 3>(W, la);
+    run_layer_m<MODE, HOIST, NBO, TIN, l_at_a + 2>(mid, r_mid, W, la, input);
+    auto r_out = ring_start_m<MODE, HOIST, NBO, TOUT, l_at_a + 3>(W, la);
     if constexpr (MODE == 0) relu<NBO>(mid);
     zero<NBO>(outacc);
-    run_layer_m<MODE, NBO, TOUT, l_at_a + 3>(outacc, r_out, W, la,
+    run_layer_m<MODE, HOIST, NBO, TOUT, l_at_a + 3>(outacc, r_out, W, la,
                          [&](auto tc) -> float { constexpr int t = decltype(tc)::value; return lazy_act<MODE, ACT_RELU>(mid[t / 16][t % 16]); });
 }
 
-template <int MODE, bool SPILL = false>
+// Scale 0 of GeoVisFusion in the hoisted kernel.  The two vertex rows' share of both first layers comes from the table of per-vertex
+// products: `at` starts from A0[i] (registers 0..7, the rest of the block is rows >= 10), `mid` from a1 N0[i] + a2 T0[i] -- the gates scale the
+// products instead of the rows, W (a x) = a (W x) -- and the MFMAs run the 34 per-sample k-pairs [pix32 | (sdf, qvis) | (vis_nn, vis_tw)] only.
+template <int MODE>
+__device__ __forceinline__ void geo_scale0_vp(WRsrc W, int lane, const typename LaneSel<MODE>::type& la, typename RingSel<MODE, 1>::type& ring_at,
+                                              float (&pix)[32], const float (&a0s)[8], const float (&n0)[32], const float (&t0)[32], float s0, float s1,
+                                              f32x16 (&outacc)[2])
+{
+    constexpr int TIN = 32 + 2;
+    auto input = [&](auto tc) -> float {
+        constexpr int t = decltype(tc)::value;
+        if constexpr (t < 32) return pix[t];
+        else if constexpr (t == 32) return s0;
+        else return s1;
+    };
+    f32x16 at[1];
+    zero<1>(at);
+#pragma unroll
+    for (int r = 0; r < 8; ++r) at[0][r] = a0s[r];
+    run_layer_m<MODE, true, 1, TIN, L_GEO_AT0_A>(at, ring_at, W, la, input);
+    auto r_gate = ring_start_m<MODE, true, 1, 6, L_GEO_AT0_B>(W, la);
+    auto r_mid = ring_start_m<MODE, true, 2, TIN, L_GEO_ATED0_A>(W, la);
+    f32x16 gate[1];
+    zero<1>(gate);
+    run_layer_m<MODE, true, 1, 6, L_GEO_AT0_B>(gate, r_gate, W, la, [&](auto tc) -> float { return lazy_act<MODE, ACT_RELU>(at[0][decltype(tc)::value]); });
+    const float a0 = __shfl(sigmoid_f(gate[0][0]), lane & 31);
+    const float a1 = __shfl(sigmoid_f(gate[0][1]), lane & 31);
+    const float a2 = __shfl(sigmoid_f(gate[0][2]), lane & 31);
+    f32x16 mid[2];
+#pragma unroll
+    for (int t = 0; t < 32; ++t) { pix[t] *= a0; mid[t / 16][t % 16] = fmaf(a2, t0[t], a1 * n0[t]); }
+    run_layer_m<MODE, true, 2, TIN, L_GEO_ATED0_A>(mid, r_mid, W, la, input);
+    auto r_out = ring_start_m<MODE, true, 2, 32, L_GEO_ATED0_B>(W, la);
+    zero<2>(outacc);
+    run_layer_m<MODE, true, 2, 32, L_GEO_ATED0_B>(outacc, r_out, W, la,
+                         [&](auto tc) -> float { constexpr int t = decltype(tc)::value; return lazy_act<MODE, ACT_RELU>(mid[t / 16][t % 16]); });
+}
+
+// NB accumulator blocks straight from a table row in D-register order: 4 NB loads of 16 bytes
+template <int NB> __device__ __forceinline__ void load_acc(const float* __restrict__ table, unsigned elem_off, f32x16 (&acc)[NB])
+{
+#pragma unroll
+    for (int ob = 0; ob < NB; ++ob)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const float4 a = ld_off<float4>(table, (elem_off + 16u * ob + 4u * i) * 4u);
+            acc[ob][4 * i] = a.x; acc[ob][4 * i + 1] = a.y; acc[ob][4 * i + 2] = a.z; acc[ob][4 * i + 3] = a.w;
+        }
+}
+
+template <int MODE, bool SPILL = false, bool HOIST = false>
 __global__ __launch_bounds__(64 * WPB<MODE>, MODE == 1 ? VANERF_WAVES_PER_SIMD_B : (SPILL ? VANERF_WAVES_PER_SIMD_SPILL : VANERF_WAVES_PER_SIMD)) void query_kernel(const QueryParams P)
 {
     static_assert(!SPILL || MODE == 0, "the training spill runs on the fp32 kernel");
+    static_assert(!HOIST || MODE == 1, "only the split-bf16 kernel has a hoisted variant");
+    [[maybe_unused]] constexpr unsigned RES_BASE_DW = ::RES_BASE_DW<HOIST>, RES_DW = ::RES_DW<HOIST>;
+    constexpr int T_GEO0 = kT_b(L_GEO_AT0_A, HOIST), T_TEX_AT = kT_b(L_TEX_AT_A, HOIST);
     constexpr int WAVES_PER_BLOCK = WPB<MODE>, BLOCK = 64 * WAVES_PER_BLOCK;
 
     const int lane_k = threadIdx.x & 63;
@@ -678,11 +752,11 @@ __global__ __launch_bounds__(64 * WPB<MODE>, MODE == 1 ? VANERF_WAVES_PER_SIMD_B
     if constexpr (MODE == 1) { // the short path's constant latent (wave 0; the layer's fragments are resident by now)
         if (wv_u == 0u) {
             const LAddr la0 = make_laddr(lane, wv_u);
-            auto r0 = ring_start_m<MODE, 1, 65, L_IBR>(W, la0);
+            auto r0 = ring_start_m<MODE, HOIST, 1, 65, L_IBR>(W, la0);
             f32x16 lat0[1];
             zero<1>(lat0);
             const float one0 = (lane >> 5) ? 0.0f : 1.0f;
-            run_layer_m<MODE, 1, 65, L_IBR>(lat0, r0, W, la0, [&](auto tc) -> float { return decltype(tc)::value < 64 ? 0.0f : one0; });
+            run_layer_m<MODE, HOIST, 1, 65, L_IBR>(lat0, r0, W, la0, [&](auto tc) -> float { return decltype(tc)::value < 64 ? 0.0f : one0; });
             if ((lane & 31) == 0)
                 static_for<16>([&](auto rc) { constexpr int r = decltype(rc)::value; reinterpret_cast<lds_u32_t*>((size_t)LDS_LAT0)[(lane >> 5) * 16 + r] = __float_as_uint(lat0[0][r]); });
         }
@@ -791,15 +865,22 @@ __global__ __launch_bounds__(64 * WPB<MODE>, MODE == 1 ? VANERF_WAVES_PER_SIMD_B
         // ibr_compress) survives.  When ALL 32 samples of the wave are such samples, GeoVisFusion, mlp_geo.layers1 and the head
         // (82 % of the MFMAs) are skipped -- same bits, wave-uniform branch.  With real foreground masks most samples are.
         if (any_valid) {
-            auto r_at0 = ring_start_m<MODE, 1, 98, L_GEO_AT0_A>(W, la);
+            auto r_at0 = ring_start_m<MODE, HOIST, 1, T_GEO0, L_GEO_AT0_A>(W, la);
             f32x16 g64[2], g8[1];
             float pix8[4], nn8[4], tw8[4];
             {
                 float pix[32], nn[32], tw[32];
                 const Bilin b0 = bilin_setup(x, y, F.h0, F.w0, P.wm1[2], P.hm1[2]);
                 gather<8>(F.geo0, b0, 64, 32 * h, pix);
-                load_row<8>(F.vfeat0, (unsigned)(nn_idx * 64 + 32 * h), nn);
-                load_row<8>(F.vfeat0, (unsigned)(tw_idx * 64 + 32 * h), tw);
+                [[maybe_unused]] float a0s[8];
+                if constexpr (HOIST) { // the rows' products with the two first layers instead of the rows (nn = N0[i], tw = T0[i]: same registers)
+                    load_row<2>(P.vp + VP_A0, (unsigned)(nn_idx * (int)VP_A0_ROW + 8 * h), a0s);
+                    load_row<8>(P.vp + VP_N0, (unsigned)(nn_idx * (int)VP_N0_ROW + 32 * h), nn);
+                    load_row<8>(P.vp + VP_T0, (unsigned)(nn_idx * (int)VP_N0_ROW + 32 * h), tw);
+                } else {
+                    load_row<8>(F.vfeat0, (unsigned)(nn_idx * 64 + 32 * h), nn);
+                    load_row<8>(F.vfeat0, (unsigned)(tw_idx * 64 + 32 * h), tw);
+                }
                 auto geo1_gathers = [&]() {
                     const Bilin b1 = bilin_setup(x, y, F.h1, F.w1, P.wm1[3], P.hm1[3]);
                     gather<1>(F.geo1, b1, 8, 4 * h, pix8);
@@ -808,7 +889,8 @@ __global__ __launch_bounds__(64 * WPB<MODE>, MODE == 1 ? VANERF_WAVES_PER_SIMD_B
                 };
                 if constexpr (!(MODE == 1 && W2)) geo1_gathers();
                 STAMP(2); // geo gathers
-                geo_scale<MODE, 32, 2, 16, L_GEO_AT0_A>(W, lane, la, r_at0, pix, nn, tw, sc0, sc1, g64);
+                if constexpr (HOIST) geo_scale0_vp<MODE>(W, lane, la, r_at0, pix, a0s, nn, tw, sc0, sc1, g64);
+                else geo_scale<MODE, HOIST, 32, 2, 16, L_GEO_AT0_A>(W, lane, la, r_at0, pix, nn, tw, sc0, sc1, g64);
                 if constexpr (MODE == 1 && W2) geo1_gathers();
                 STAMP(3); // geo0 layers
             }
@@ -818,14 +900,14 @@ __global__ __launch_bounds__(64 * WPB<MODE>, MODE == 1 ? VANERF_WAVES_PER_SIMD_B
             WFrag<4> ring0[D0];
             RingB<4> ring0b;
             {
-                auto r_at1 = ring_start_m<MODE, 1, 14, L_GEO_AT1_A>(W, la);
+                auto r_at1 = ring_start_m<MODE, HOIST, 1, 14, L_GEO_AT1_A>(W, la);
                 if constexpr (MODE == 0) {
                     static_for<D0>([&](auto fc) { constexpr int f = decltype(fc)::value; ring0[f] = wload<4>(W, (base0 + f * 256) * 4u, v4); });
                 } else if constexpr (!W2) {
-                    if constexpr (MODE == 1) ring0b = ring_start_b<4, 180, false, layer_offset_b(L_MLP0)>(W, la);
+                    if constexpr (MODE == 1) ring0b = ring_start_b<HOIST, 4, 180, false, layer_offset_b(L_MLP0, HOIST)>(W, la);
                 }
-                geo_scale<MODE, 4, 1, 4, L_GEO_AT1_A>(W, lane, la, r_at1, pix8, nn8, tw8, sc0, sc1, g8);
-                if constexpr (MODE == 1 && W2) ring0b = ring_start_b<4, 180, false, layer_offset_b(L_MLP0)>(W, la);
+                geo_scale<MODE, HOIST, 4, 1, 4, L_GEO_AT1_A>(W, lane, la, r_at1, pix8, nn8, tw8, sc0, sc1, g8);
+                if constexpr (MODE == 1 && W2) ring0b = ring_start_b<HOIST, 4, 180, false, layer_offset_b(L_MLP0, HOIST)>(W, la);
                 STAMP(4); // geo1
             }
 
@@ -898,7 +980,7 @@ __global__ __launch_bounds__(64 * WPB<MODE>, MODE == 1 ? VANERF_WAVES_PER_SIMD_B
                         // 179 the bias.  A bf16 step takes 8 consecutive pairs, so key point i is computed right before the first step
                         // that needs it (at most two key points are live at a time).
                         float feat[PE_KPT_PER_HALF][PE_FEATS];
-                        run_layer_b<4, 180, false, layer_offset_b(L_MLP0), (((VANERF_P1_MASK >> L_MLP0) & 1) ? 1 : ((VANERF_P2_MASK >> L_MLP0) & 1) ? 2 : 3)>(a0, ring0b, W, la,
+                        run_layer_b<HOIST, 4, 180, false, layer_offset_b(L_MLP0, HOIST), (((VANERF_P1_MASK >> L_MLP0) & 1) ? 1 : ((VANERF_P2_MASK >> L_MLP0) & 1) ? 2 : 3)>(a0, ring0b, W, la,
                             [&](auto tc) -> float {
                                 constexpr int t = decltype(tc)::value;
                                 if constexpr (t < 147) return feat[t / 7][t % 7];
@@ -915,29 +997,29 @@ __global__ __launch_bounds__(64 * WPB<MODE>, MODE == 1 ? VANERF_WAVES_PER_SIMD_B
                     }
                 }
                 STAMP(5); // mlp0 (PE + geo64)
-                auto r1 = ring_start_m<MODE, 4, 65, L_MLP1>(W, la);
+                auto r1 = ring_start_m<MODE, HOIST, 4, 65, L_MLP1>(W, la);
                 if constexpr (MODE == 0) softplus<4>(a0);
                 f32x16 a1[4];
                 zero<4>(a1);
-                run_layer_m<MODE, 4, 65, L_MLP1>(a1, r1, W, la, [&](auto tc) -> float { return chain_sp(a0, tc, std::integral_constant<int, 64>{}); });
-                auto r2 = ring_start_m<MODE, 4, 69, L_MLP2>(W, la);
+                run_layer_m<MODE, HOIST, 4, 65, L_MLP1>(a1, r1, W, la, [&](auto tc) -> float { return chain_sp(a0, tc, std::integral_constant<int, 64>{}); });
+                auto r2 = ring_start_m<MODE, HOIST, 4, 69, L_MLP2>(W, la);
                 if constexpr (MODE == 0) softplus<4>(a1);
                 zero<4>(a0);
-                run_layer_m<MODE, 4, 69, L_MLP2>(a0, r2, W, la, [&](auto tc) -> float {
+                run_layer_m<MODE, HOIST, 4, 69, L_MLP2>(a0, r2, W, la, [&](auto tc) -> float {
                     constexpr int t = decltype(tc)::value;
                     if constexpr (t < 64) return lazy_act<MODE, ACT_SOFTPLUS>(a1[t / 16][t % 16]);
                     else if constexpr (t < 68) return g8[0][t - 64];
                     else return one_h0;
                 });
-                auto r3 = ring_start_m<MODE, 2, 61, L_MLP3>(W, la);
+                auto r3 = ring_start_m<MODE, HOIST, 2, 61, L_MLP3>(W, la);
                 if constexpr (MODE == 0) softplus<4>(a0);
                 zero<2>(xv);
-                run_layer_m<MODE, 2, 61, L_MLP3>(xv, r3, W, la, [&](auto tc) -> float { return chain_sp(a0, tc, std::integral_constant<int, 60>{}); });
+                run_layer_m<MODE, HOIST, 2, 61, L_MLP3>(xv, r3, W, la, [&](auto tc) -> float { return chain_sp(a0, tc, std::integral_constant<int, 60>{}); });
             }
             STAMP(6); // softplus x3 + mlp1..3
             if constexpr (!(MODE == 1 && W2)) tex_gathers();
             // ---- PoolModule mean/var over V = 1 views (src/utils.py:744-779, 854-880) --------------------------
-            auto rh0 = ring_start_m<MODE, 2, 65, L_HEAD0>(W, la);
+            auto rh0 = ring_start_m<MODE, HOIST, 2, 65, L_HEAD0>(W, la);
             if constexpr (MODE == 0)
                 static_for<32>([&](auto rc) { constexpr int r = decltype(rc)::value; spill_aux<AUX_XV + r>(la, xv[r / 16][r % 16]); });
     #pragma unroll
@@ -953,15 +1035,17 @@ __global__ __launch_bounds__(64 * WPB<MODE>, MODE == 1 ? VANERF_WAVES_PER_SIMD_B
             {
                 f32x16 m0[2], m1[2];
                 zero<2>(m0);
-                run_layer_m<MODE, 2, 65, L_HEAD0>(m0, rh0, W, la, [&](auto tc) -> float { return chain(pool, tc, std::integral_constant<int, 64>{}); });
-                auto rh1 = ring_start_m<MODE, 2, 33, L_HEAD1>(W, la);
+                run_layer_m<MODE, HOIST, 2, 65, L_HEAD0>(m0, rh0, W, la, [&](auto tc) -> float { return chain(pool, tc, std::integral_constant<int, 64>{}); });
+                auto rh1 = ring_start_m<MODE, HOIST, 2, 33, L_HEAD1>(W, la);
                 if constexpr (MODE == 0) softplus<2>(m0);
                 zero<2>(m1);
-                run_layer_m<MODE, 2, 33, L_HEAD1>(m1, rh1, W, la, [&](auto tc) -> float { return chain_sp(m0, tc, std::integral_constant<int, 32>{}); });
-                auto rh2 = ring_start_m<MODE, 1, 33, L_HEAD2>(W, la);
+                run_layer_m<MODE, HOIST, 2, 33, L_HEAD1>(m1, rh1, W, la, [&](auto tc) -> float { return chain_sp(m0, tc, std::integral_constant<int, 32>{}); });
+                auto rh2 = ring_start_m<MODE, HOIST, 1, 33, L_HEAD2>(W, la);
                 if constexpr (MODE == 0) softplus<2>(m1);
                 zero<1>(head);
-                run_layer_m<MODE, 1, 33, L_HEAD2>(head, rh2, W, la, [&](auto tc) -> float { return chain_sp(m1, tc, std::integral_constant<int, 32>{}); });
+                run_layer_m<MODE, HOIST, 1, 33, L_HEAD2>(head, rh2, W, la, [&](auto tc) -> float { return chain_sp(m1, tc, std::integral_constant<int, 32>{}); });
+                static_assert(LDS_FIRST == L_HEAD2 + 1 || !RING, "the ring is closed behind its last streamed layer");
+                if constexpr (MODE == 1) ring_close<HOIST>(W, la);
             }
         } else {
             if constexpr (!(MODE == 1 && W2)) tex_gathers();
@@ -976,14 +1060,14 @@ __global__ __launch_bounds__(64 * WPB<MODE>, MODE == 1 ? VANERF_WAVES_PER_SIMD_B
         typename RingSel<MODE, 3>::type r_ta;
         if (MODE == 1 && !any_valid) {
             // all-invalid group: the pooled latent is exactly zero, the layer returns its bias -- the block's constant (same chain, same bits)
-            r_ta = ring_start_m<MODE, 3, 49, L_TEX_AT_A>(W, la);
+            r_ta = ring_start_m<MODE, HOIST, 3, T_TEX_AT, L_TEX_AT_A>(W, la);
             if constexpr (MODE == 1)
                 static_for<16>([&](auto rc) { constexpr int r = decltype(rc)::value; lat[0][r] = __uint_as_float(reinterpret_cast<const lds_u32_t*>((size_t)LDS_LAT0)[h * 16 + r]); });
         } else {
-            auto r_ibr = ring_start_m<MODE, 1, 65, L_IBR>(W, la);
-            r_ta = ring_start_m<MODE, 3, 49, L_TEX_AT_A>(W, la);
+            auto r_ibr = ring_start_m<MODE, HOIST, 1, 65, L_IBR>(W, la);
+            r_ta = ring_start_m<MODE, HOIST, 3, T_TEX_AT, L_TEX_AT_A>(W, la);
             zero<1>(lat);
-            run_layer_m<MODE, 1, 65, L_IBR>(lat, r_ibr, W, la, [&](auto tc) -> float { return chain(pool, tc, std::integral_constant<int, 64>{}); });
+            run_layer_m<MODE, HOIST, 1, 65, L_IBR>(lat, r_ibr, W, la, [&](auto tc) -> float { return chain(pool, tc, std::integral_constant<int, 64>{}); });
         }
         STAMP(8); // ibr
         // ---- TexVisFusion per-sample part (src/networks.py:281-293) -----------------------------------------
@@ -1004,15 +1088,25 @@ __global__ __launch_bounds__(64 * WPB<MODE>, MODE == 1 ? VANERF_WAVES_PER_SIMD_B
                 else return t1;
             };
             auto from_ta = [&](auto& ta_) { return [&](auto tc) -> float { constexpr int t = decltype(tc)::value; return lazy_act<MODE, ACT_RELU>(ta_[t / 16][t % 16]); }; };
+            // hoisted kernel: the ungated first layer starts from P[i], the two vertex rows' share of it, and runs [query6 | latent12 | 2 visibility pairs]
+            auto tex_at_in = [&](auto tc) -> float {
+                constexpr int t = decltype(tc)::value;
+                if constexpr (!HOIST) return tex_in(tc);
+                else if constexpr (t < 6) return q[t];
+                else if constexpr (t < 18) return latg[t - 6];
+                else if constexpr (t == 18) return t0;
+                else return t1;
+            };
             f32x16 ta[3];
-            zero<3>(ta);
-            run_layer_m<MODE, 3, 49, L_TEX_AT_A>(ta, r_ta, W, la, tex_in);
-            auto r_tg = ring_start_m<MODE, 1, 48, L_TEX_AT_B>(W, la);
+            if constexpr (HOIST) load_acc<3>(P.vp + VP_P, (unsigned)(nn_idx * (int)VP_P_ROW + 48 * h), ta);
+            else zero<3>(ta);
+            run_layer_m<MODE, HOIST, 3, T_TEX_AT, L_TEX_AT_A>(ta, r_ta, W, la, tex_at_in);
+            auto r_tg = ring_start_m<MODE, HOIST, 1, 48, L_TEX_AT_B>(W, la);
             if constexpr (MODE == 0) relu<3>(ta);
             f32x16 tg[1];
             zero<1>(tg);
-            run_layer_m<MODE, 1, 48, L_TEX_AT_B>(tg, r_tg, W, la, from_ta(ta));
-            auto r_tb = ring_start_m<MODE, 3, 49, L_TEX_A>(W, la);
+            run_layer_m<MODE, HOIST, 1, 48, L_TEX_AT_B>(tg, r_tg, W, la, from_ta(ta));
+            auto r_tb = ring_start_m<MODE, HOIST, 3, 49, L_TEX_A>(W, la);
             // six gates: rows 0..3 -> h = 0 lanes regs 0..3, rows 4,5 -> h = 1 lanes regs 0,1
             float m0 = sigmoid_f(tg[0][0]), m1 = sigmoid_f(tg[0][1]), m2 = sigmoid_f(tg[0][2]), m3 = sigmoid_f(tg[0][3]);
             float o0 = __shfl_xor(m0, 32), o1 = __shfl_xor(m1, 32), o2 = __shfl_xor(m2, 32);
@@ -1033,11 +1127,11 @@ __global__ __launch_bounds__(64 * WPB<MODE>, MODE == 1 ? VANERF_WAVES_PER_SIMD_B
 #pragma unroll
             for (int r = 0; r < 12; ++r) latg[r] = lat[0][r] * glat;
             zero<3>(ta);
-            run_layer_m<MODE, 3, 49, L_TEX_A>(ta, r_tb, W, la, tex_in);
-            auto r_rgb = ring_start_m<MODE, 1, 48, L_TEX_B>(W, la);
+            run_layer_m<MODE, HOIST, 3, 49, L_TEX_A>(ta, r_tb, W, la, tex_in);
+            auto r_rgb = ring_start_m<MODE, HOIST, 1, 48, L_TEX_B>(W, la);
             if constexpr (MODE == 0) relu<3>(ta);
             zero<1>(rgb);
-            run_layer_m<MODE, 1, 48, L_TEX_B>(rgb, r_rgb, W, la, from_ta(ta));
+            run_layer_m<MODE, HOIST, 1, 48, L_TEX_B>(rgb, r_rgb, W, la, from_ta(ta));
         }
         STAMP(9); // tex
         // ---- eval_func (src/model.py:1140-1160): rows 0,1 of the head / 0..2 of the colour live in the h = 0 lanes ----
@@ -1073,6 +1167,15 @@ extern "C" int vanerf_query_samples(const VanerfWeights* w, const VanerfFrame* f
                                     const uint8_t* query_vis, const int32_t* knn_idx, const float* noise, const int32_t* order, int raw, int64_t n,
                                     float* out, uint8_t* valid, void* queue_word, void* stream)
 {
+    return vanerf_query_samples_vp(w, frame, pts, query_sdf, query_vis, knn_idx, noise, order, raw, n, out, valid, queue_word, nullptr, stream);
+}
+
+// vertex_products: the frame's table from vanerf_vertex_products (built with the same handle, after its last update), or NULL.  With the
+// table a bf16x3 handle runs the hoisted kernel on its hoisted stream; without it the launch is vanerf_query_samples'.
+extern "C" int vanerf_query_samples_vp(const VanerfWeights* w, const VanerfFrame* frame, const float* pts, const float* query_sdf,
+                                       const uint8_t* query_vis, const int32_t* knn_idx, const float* noise, const int32_t* order, int raw, int64_t n,
+                                       float* out, uint8_t* valid, void* queue_word, const float* vertex_products, void* stream)
+{
     return guarded([&] {
         if (n < 0) throw_error("vanerf_query_samples: n = %lld < 0", (long long)n);
         if (n == 0) return; // an empty batch is valid (and has null data pointers)
@@ -1084,8 +1187,11 @@ extern "C" int vanerf_query_samples(const VanerfWeights* w, const VanerfFrame* f
             throw_error("vanerf_query_samples: frame has a null pointer");
         if (f.h0 < 1 || f.w0 < 1 || f.h1 < 1 || f.w1 < 1 || f.ht < 1 || f.wt < 1 || f.hi < 1 || f.wi < 1)
             throw_error("vanerf_query_samples: feature-map sizes must be positive");
+        const bool hoist = vertex_products != nullptr;
+        if (hoist && (w->mode != 1 || !w->n_floats_h)) throw_error("vanerf_query_samples_vp: a table of vertex products needs a bf16x3 weight handle");
+        if (hoist && (reinterpret_cast<uintptr_t>(vertex_products) & 15u)) throw_error("vanerf_query_samples_vp: the table must be 16-byte aligned");
         QueryParams P;
-        P.f = f; P.w = w->dev; P.wbytes = (unsigned)(w->n_floats * sizeof(float)); P.pts = pts; P.qsdf = query_sdf; P.qvis = query_vis; P.noise = noise; P.knn_in = knn_idx; P.order = order; P.raw = raw;
+        P.f = f; P.w = hoist ? w->dev + w->n_floats : w->dev; P.wbytes = (unsigned)((hoist ? w->n_floats_h : w->n_floats) * sizeof(float)); P.vp = vertex_products; P.pts = pts; P.qsdf = query_sdf; P.qvis = query_vis; P.noise = noise; P.knn_in = knn_idx; P.order = order; P.raw = raw;
         P.n = n; P.out = out; P.valid = valid; P.stamps = nullptr; P.short_groups = w->stats;
         P.xs = nullptr; P.aux = nullptr; P.npad = 0;
         { const int ws[4] = {P.f.wi, P.f.wt, P.f.w0, P.f.w1}, hs[4] = {P.f.hi, P.f.ht, P.f.h0, P.f.h1};
@@ -1106,10 +1212,13 @@ extern "C" int vanerf_query_samples(const VanerfWeights* w, const VanerfFrame* f
         if (blocks > cap) blocks = cap;
         P.queue = static_cast<unsigned*>(queue_word); // the caller's word: no launch shares a queue head with another (any number in flight, any streams)
         HIP_CHECK(hipMemsetAsync(P.queue, 0, 8, (hipStream_t)stream));
-        if (w->mode == 1) {
+        if (w->mode == 1 && hoist) {
+            HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(query_kernel<1, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)DYN_LDS_BYTES<true>));
+            hipLaunchKernelGGL((query_kernel<1, false, true>), dim3((unsigned)blocks), dim3(64 * WPB<1>), DYN_LDS_BYTES<true>, (hipStream_t)stream, P);
+        } else if (w->mode == 1) {
             // the opt-in above 64 KB of dynamic LDS is per device: set on every call (cheap), as vanerf_mesh_query_accel does
-            HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(query_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)DYN_LDS_BYTES));
-            hipLaunchKernelGGL(query_kernel<1>, dim3((unsigned)blocks), dim3(64 * WPB<1>), DYN_LDS_BYTES, (hipStream_t)stream, P);
+            HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(query_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)DYN_LDS_BYTES<false>));
+            hipLaunchKernelGGL(query_kernel<1>, dim3((unsigned)blocks), dim3(64 * WPB<1>), DYN_LDS_BYTES<false>, (hipStream_t)stream, P);
         } else hipLaunchKernelGGL(query_kernel<0>, dim3((unsigned)blocks), dim3(64 * WPB<0>), 0, (hipStream_t)stream, P);
         HIP_CHECK(hipGetLastError());
     });
@@ -1136,7 +1245,7 @@ extern "C" int vanerf_query_forward_spill(const VanerfWeights* w, const VanerfFr
         QueryParams P;
         P.f = f; P.w = w->dev; P.wbytes = (unsigned)(w->n_floats * sizeof(float)); P.pts = pts; P.qsdf = query_sdf; P.qvis = query_vis; P.noise = nullptr; P.knn_in = knn_idx; P.order = nullptr; P.raw = 1;
         P.n = n; P.out = out_raw; P.valid = valid; P.stamps = nullptr; P.short_groups = nullptr;
-        P.xs = xs; P.aux = aux; P.npad = npad;
+        P.xs = xs; P.aux = aux; P.npad = npad; P.vp = nullptr;
         { const int ws[4] = {P.f.wi, P.f.wt, P.f.w0, P.f.w1}, hs[4] = {P.f.hi, P.f.ht, P.f.h0, P.f.h1};
           for (int i = 0; i < 4; ++i) { P.wm1[i] = (float)(ws[i] - 1); P.hm1[i] = (float)(hs[i] - 1); } }
         const long long ngroups = (n + 31) / 32;
@@ -1252,7 +1361,7 @@ extern "C" int vanerf_debug_query_stamps(const VanerfWeights* w, const VanerfFra
     return guarded([&] {
         QueryParams P;
         P.f = *frame; P.w = w->dev; P.wbytes = (unsigned)(w->n_floats * sizeof(float)); P.pts = pts; P.qsdf = query_sdf; P.qvis = query_vis; P.noise = nullptr; P.knn_in = knn_idx; P.order = nullptr; P.raw = 0;
-        P.n = n; P.out = out; P.valid = nullptr; P.stamps = stamps; P.short_groups = nullptr;
+        P.n = n; P.out = out; P.valid = nullptr; P.stamps = stamps; P.short_groups = nullptr; P.vp = nullptr;
         { const int ws[4] = {P.f.wi, P.f.wt, P.f.w0, P.f.w1}, hs[4] = {P.f.hi, P.f.ht, P.f.h0, P.f.h1};
           for (int i = 0; i < 4; ++i) { P.wm1[i] = (float)(ws[i] - 1); P.hm1[i] = (float)(hs[i] - 1); } }
         long long ngroups = (n + 31) / 32;
@@ -1264,8 +1373,8 @@ extern "C" int vanerf_debug_query_stamps(const VanerfWeights* w, const VanerfFra
         *n_waves = (int)blocks * wpb;
         P.queue = static_cast<unsigned*>(queue_word);
         HIP_CHECK(hipMemsetAsync(P.queue, 0, 8, (hipStream_t)stream));
-        if (stamps && w->mode == 1) HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(query_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)DYN_LDS_BYTES));
-        if (stamps && w->mode == 1) hipLaunchKernelGGL(query_kernel<1>, dim3((unsigned)blocks), dim3(64 * WPB<1>), DYN_LDS_BYTES, (hipStream_t)stream, P);
+        if (stamps && w->mode == 1) HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(query_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)DYN_LDS_BYTES<false>));
+        if (stamps && w->mode == 1) hipLaunchKernelGGL(query_kernel<1>, dim3((unsigned)blocks), dim3(64 * WPB<1>), DYN_LDS_BYTES<false>, (hipStream_t)stream, P);
         else if (stamps) hipLaunchKernelGGL(query_kernel<0>, dim3((unsigned)blocks), dim3(64 * WPB<0>), 0, (hipStream_t)stream, P);
         HIP_CHECK(hipGetLastError());
     });

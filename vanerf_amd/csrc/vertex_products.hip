@@ -1,0 +1,84 @@
+// vertex_products.hip -- the per-vertex half of three first layers, once per source frame (layer_spec.h: the hoisted bf16x3 stream).
+//
+// geo_vis_fusion.fconv_at.0 (196 -> 10), geo_vis_fusion.fconv_ated.0 (196 -> 64) and tex_vis_fusion.fconv_at.0 (96 -> 96)
+// (reference src/networks.py:86-93, 285-288) have no bias and nothing in front of their matrix product, and 128 / 128 / 58 of their input
+// channels are rows of the per-frame vertex tables selected by the sample's 1-NN vertex i and its twin tw(i) = (i + 779) mod 1558.  Their
+// share of the product is therefore one fixed vector per vertex and frame; query_kernel<1, hoisted> starts its accumulators from these rows
+// instead of spending 64 / 64 / 29 k-pairs per sample on them.  The second layer's rows are gated per sample (a1 nn, a2 twin):
+// W (a1 x) = a1 (W x), so its two halves are kept apart (N0, T0) and scaled in the kernel.
+//
+// Arithmetic: fp32, one thread per table element, one fmaf chain in ascending input-channel order (nearest vertex's columns, then the
+// twin's): the same bits on every build.  One launch, no allocation, no host synchronisation.
+#include "common.h"
+
+using namespace vanerf;
+
+namespace {
+
+static_assert(VP_NV == VANERF_NV, "the table is laid out for the two-hand mesh");
+constexpr unsigned VP_PER_VERTEX = VP_A0_ROW + 2u * VP_N0_ROW + VP_P_ROW;
+
+__device__ __forceinline__ float dot_chain(float acc, const float* __restrict__ w, const float* __restrict__ x, int n)
+{
+    for (int k = 0; k < n; ++k) acc = fmaf(w[k], x[k], acc);
+    return acc;
+}
+
+// wat [10][196], wated [64][196], wtex [96][96]: the layers' effective (= plain) weights
+__global__ __launch_bounds__(256) void vertex_products_kernel(const float* __restrict__ wat, const float* __restrict__ wated, const float* __restrict__ wtex,
+                                                              const float* __restrict__ vfeat0, const float* __restrict__ vfeat_tex, float* __restrict__ table)
+{
+    const unsigned idx = blockIdx.x * 256u + threadIdx.x;
+    if (idx >= VP_NV * VP_PER_VERTEX) return;
+    const unsigned i = idx / VP_PER_VERTEX, e = idx % VP_PER_VERTEX;
+    const unsigned tw = i >= VANERF_NV_HAND ? i - VANERF_NV_HAND : i + VANERF_NV_HAND;
+    // output row of element q of a row laid out [h][nb][nr registers]
+    auto out_row = [](unsigned q, unsigned nb, unsigned nr) {
+        const unsigned h = q / (nb * nr), ob = (q % (nb * nr)) / nr, r = q % nr;
+        return 32u * ob + (r & 3u) + 8u * (r >> 2) + 4u * h;
+    };
+    const float* x_nn = vfeat0 + 64u * i;
+    const float* x_tw = vfeat0 + 64u * tw;
+    if (e < VP_A0_ROW) {
+        const unsigned o = out_row(e, 1u, 8u);
+        float v = 0.0f;
+        if (o < 10u) v = dot_chain(dot_chain(0.0f, wat + 196u * o + 64u, x_nn, 64), wat + 196u * o + 128u, x_tw, 64);
+        table[VP_A0 + VP_A0_ROW * i + e] = v;
+    } else if (e < VP_A0_ROW + VP_N0_ROW) {
+        const unsigned q = e - VP_A0_ROW, o = out_row(q, 2u, 16u);
+        table[VP_N0 + VP_N0_ROW * i + q] = dot_chain(0.0f, wated + 196u * o + 64u, x_nn, 64);
+    } else if (e < VP_A0_ROW + 2u * VP_N0_ROW) {
+        const unsigned q = e - VP_A0_ROW - VP_N0_ROW, o = out_row(q, 2u, 16u);
+        table[VP_T0 + VP_N0_ROW * i + q] = dot_chain(0.0f, wated + 196u * o + 128u, x_tw, 64);
+    } else {
+        // TexVisFusion input [q11 | nn11 | tw11 | nn_gf18 | tw_gf18 | ...]; a vertex row is [img3 | tex8 | gf18 | 3 unused]
+        const unsigned q = e - VP_A0_ROW - 2u * VP_N0_ROW, o = out_row(q, 3u, 16u);
+        const float* w = wtex + 96u * o;
+        const float* t_nn = vfeat_tex + 32u * i;
+        const float* t_tw = vfeat_tex + 32u * tw;
+        float v = dot_chain(dot_chain(0.0f, w + 11, t_nn, 11), w + 33, t_nn + 11, 18);
+        v = dot_chain(dot_chain(v, w + 22, t_tw, 11), w + 51, t_tw + 11, 18);
+        table[VP_P + VP_P_ROW * i + q] = v;
+    }
+}
+
+} // namespace
+
+// Returns the number of floats the table takes when `table` is NULL, 0 after a launch, < 0 on error.
+extern "C" int vanerf_vertex_products(const VanerfWeights* w, const VanerfFrame* frame, float* table, int64_t cap_floats, void* stream)
+{
+    int size = 0;
+    const int rc = guarded([&] {
+        if (!table) { size = (int)VP_FLOATS; return; }
+        if (!w || !frame) throw_error("vanerf_vertex_products: null argument");
+        if (w->mode != 1 || !w->dev_eff) throw_error("vanerf_vertex_products: needs a bf16x3 weight handle (vanerf_weights_pack mode 1)");
+        if (!frame->vfeat0 || !frame->vfeat_tex) throw_error("vanerf_vertex_products: frame has a null pointer");
+        if (cap_floats < (int64_t)VP_FLOATS) throw_error("vanerf_vertex_products: room for %lld floats, %u needed", (long long)cap_floats, VP_FLOATS);
+        if (reinterpret_cast<uintptr_t>(table) & 15u) throw_error("vanerf_vertex_products: the table must be 16-byte aligned");
+        const unsigned n = VP_NV * VP_PER_VERTEX;
+        hipLaunchKernelGGL(vertex_products_kernel, dim3((n + 255u) / 256u), dim3(256), 0, (hipStream_t)stream, w->dev_eff + eff_layer_offset(L_GEO_AT0_A),
+                           w->dev_eff + eff_layer_offset(L_GEO_ATED0_A), w->dev_eff + eff_layer_offset(L_TEX_AT_A), frame->vfeat0, frame->vfeat_tex, table);
+        HIP_CHECK(hipGetLastError());
+    });
+    return rc != VANERF_OK ? rc : size;
+}

@@ -103,12 +103,12 @@ void emit(std::vector<float>& out, int layer, const Mat& m, const Pairs& pairs)
 
 // bf16x3 stream of one layer (layer_spec.h): element j of the 8-element fragment of lane (r, h) at step s is k-pair 8s + j.
 // Placement only: per 32-bit word of the stream two ids (the elements in its low and high half) and which bf16 part of them it holds.
-void emit_b_ids(std::vector<WordB>& out, int layer, const Mat& m, const Pairs& pairs)
+void emit_b_ids(std::vector<WordB>& out, int layer, const Mat& m, const Pairs& pairs, bool hoist)
 {
-    const int nb = kNB[layer], T = kT[layer], S = steps_b(layer);
+    const int nb = kNB[layer], T = kT_b(layer, hoist), S = steps_b(layer, hoist);
     if ((int)pairs.size() != T) throw_error("internal: layer %d has %d k-pairs, spec says %d", layer, (int)pairs.size(), T);
     size_t base = out.size();
-    out.resize(base + layer_dwords_b(layer), WordB{0, 0, 0});
+    out.resize(base + layer_dwords_b(layer, hoist), WordB{0, 0, 0});
     WordB* dst = out.data() + base;
     for (int s = 0; s < S; ++s)
         for (int ob = 0; ob < nb; ++ob)
@@ -130,11 +130,12 @@ void emit_b_ids(std::vector<WordB>& out, int layer, const Mat& m, const Pairs& p
 }
 
 // [pix | nn | twin] each `c` channels split in halves between the lane halves, then (sdf|qvis), (vis_nn|vis_twin)
-Pairs geo_input_pairs(int c)
+// (hoisted stream: the pixel feature and the scalar pairs only -- the vertex rows come from the table of per-vertex products)
+Pairs geo_input_pairs(int c, bool hoist = false)
 {
     Pairs p;
     int hc = c / 2;
-    for (int grp = 0; grp < 3; ++grp)
+    for (int grp = 0; grp < (hoist ? 1 : 3); ++grp)
         for (int t = 0; t < hc; ++t) p.emplace_back(grp * c + t, grp * c + hc + t);
     p.emplace_back(3 * c + 0, 3 * c + 1);
     p.emplace_back(3 * c + 2, 3 * c + 3);
@@ -142,11 +143,14 @@ Pairs geo_input_pairs(int c)
 }
 
 // TexVisFusion input (src/networks.py:284-286): [q11 | nn11 | tw11 | nn_gf18 | tw_gf18 | latent24 | qvis | vis_nn | vis_tw]
-Pairs tex_input_pairs()
+// (hoisted stream: without the two vertex rows, i.e. [query 6 | latent 12 | 2 visibility pairs])
+Pairs tex_input_pairs(bool hoist = false)
 {
     Pairs p;
-    for (int t = 0; t < 11; ++t) p.emplace_back(11 + t, 22 + t);  // h0: nearest vertex row, h1: twin vertex row
-    for (int t = 0; t < 18; ++t) p.emplace_back(33 + t, 51 + t);
+    if (!hoist) {
+        for (int t = 0; t < 11; ++t) p.emplace_back(11 + t, 22 + t);  // h0: nearest vertex row, h1: twin vertex row
+        for (int t = 0; t < 18; ++t) p.emplace_back(33 + t, 51 + t);
+    }
     for (int u = 0; u < 6; ++u) p.emplace_back(u, u < 5 ? 6 + u : ZERO); // query feature: h0 q[0..5], h1 q[6..10]
     chain(p, 1, 12, 69, 24);                                        // latent24 straight from the ibr accumulator
     p.emplace_back(93, 94);
@@ -159,11 +163,11 @@ Pairs tex_input_pairs()
 namespace {
 
 // k-pairs (input channel of lane half 0 / 1 per k-step) of every layer: structure only, no weights
-Pairs layer_pairs(int l)
+Pairs layer_pairs(int l, bool hoist = false)
 {
     Pairs p;
     switch (l) {
-    case L_GEO_AT0_A: case L_GEO_ATED0_A: return geo_input_pairs(64);
+    case L_GEO_AT0_A: case L_GEO_ATED0_A: return geo_input_pairs(64, hoist);
     case L_GEO_AT1_A: case L_GEO_ATED1_A: return geo_input_pairs(8);
     case L_GEO_AT0_B: case L_GEO_AT1_B: chain(p, 1, 6, 0, 10); return p;
     case L_GEO_ATED0_B: chain(p, 2, 16, 0, 64); return p;
@@ -179,7 +183,8 @@ Pairs layer_pairs(int l)
     case L_MLP3: chain(p, 4, 12, 0, 120); bias_pair(p); return p;
     case L_HEAD0: case L_IBR: chain(p, 2, 16, 0, 64); chain(p, 2, 16, 64, 64); bias_pair(p); return p; // [mean | var]
     case L_HEAD1: case L_HEAD2: chain(p, 2, 16, 0, 64); bias_pair(p); return p;
-    case L_TEX_AT_A: case L_TEX_A: return tex_input_pairs();
+    case L_TEX_AT_A: return tex_input_pairs(hoist);
+    case L_TEX_A: return tex_input_pairs();
     case L_TEX_AT_B: case L_TEX_B: chain(p, 3, 16, 0, 96); return p;
     }
     throw_error("internal: no layer %d", l);
@@ -304,7 +309,7 @@ const PackTables& pack_tables()
     static const PackTables tables = [] {
         PackTables t;
         std::vector<float> fwd, bwd;
-        std::vector<WordB> fwd_b;
+        std::vector<WordB> fwd_b, fwd_bh;
         for (int l = 0; l < NUM_LAYERS; ++l) {
             t.offs.off[l] = (unsigned)fwd.size();
             if (fwd.size() != layer_offset(l)) throw_error("internal: layer %d starts at %zu, layer_spec.h says %u", l, fwd.size(), layer_offset(l));
@@ -312,22 +317,27 @@ const PackTables& pack_tables()
             const Mat m = id_matrix(l);
             const Pairs p = layer_pairs(l);
             emit(fwd, l, m, p);
-            emit_b_ids(fwd_b, l, m, p);
+            emit_b_ids(fwd_b, l, m, p, false);
+            if (fwd_bh.size() != layer_offset_b(l, true)) throw_error("internal: layer %d (hoisted bf16x3) starts at %zu, layer_spec.h says %u", l, fwd_bh.size(), layer_offset_b(l, true));
+            emit_b_ids(fwd_bh, l, m, layer_pairs(l, true), true);
             emit_bwd(bwd, l, m, p);
         }
         // slack behind the last layer (prefetch rings never read past a layer's own steps, this is belt and braces)
         fwd.resize(fwd.size() + 2 * 64 * 4, 0.0f);
         bwd.resize(bwd.size() + 2 * 64 * 4, 0.0f);
         fwd_b.resize(fwd_b.size() + 2 * 64 * 4, WordB{0, 0, 0});
+        fwd_bh.resize(fwd_bh.size() + 2 * 64 * 4, WordB{0, 0, 0});
         t.fwd.assign(fwd.begin(), fwd.end());
         t.bwd.assign(bwd.begin(), bwd.end());
-        t.fwd_b.resize(2 * fwd_b.size());
-        for (size_t i = 0; i < fwd_b.size(); ++i) {
-            t.fwd_b[2 * i] = fwd_b[i].id0 | (fwd_b[i].part << 30);
-            t.fwd_b[2 * i + 1] = fwd_b[i].id1;
+        for (auto [src, dst] : {std::pair{&fwd_b, &t.fwd_b}, std::pair{&fwd_bh, &t.fwd_bh}}) {
+            dst->resize(2 * src->size());
+            for (size_t i = 0; i < src->size(); ++i) {
+                (*dst)[2 * i] = (*src)[i].id0 | ((*src)[i].part << 30);
+                (*dst)[2 * i + 1] = (*src)[i].id1;
+            }
         }
         t.n_eff = eff_offset(NUM_LAYERS);
-        for (const std::vector<int>* v : {&t.fwd, &t.bwd, &t.fwd_b})
+        for (const std::vector<int>* v : {&t.fwd, &t.bwd, &t.fwd_b, &t.fwd_bh})
             for (int id : *v)
                 if ((id & 0x3fffffff) > (int)t.n_eff) throw_error("internal: placement id %d beyond the %u effective weights", id, t.n_eff);
         return t;
@@ -337,21 +347,28 @@ const PackTables& pack_tables()
 
 void layer_sources(const VanerfWeightTable& w, LayerSrc out[NUM_LAYERS]) { sources(w, out); }
 
-void pack_weights_host(const VanerfWeightTable& w, std::vector<float>& out, LayerOffsets& offs, int mode, std::vector<float>* bwd)
+unsigned eff_layer_offset(int l) { return eff_offset(l); }
+
+void pack_weights_host(const VanerfWeightTable& w, std::vector<float>& out, LayerOffsets& offs, int mode, std::vector<float>* bwd, std::vector<float>* hoisted,
+                       std::vector<float>* eff_out)
 {
     const PackTables& t = pack_tables();
     std::vector<float> eff;
     fold_host(w, eff);
     auto value = [&](int id) { return id ? eff[(size_t)id - 1] : 0.0f; };
     for (int l = 0; l < NUM_LAYERS; ++l) offs.off[l] = mode ? layer_offset_b(l) : t.offs.off[l];
-    if (mode) {
-        const size_t n = t.fwd_b.size() / 2;
-        out.resize(n);
-        unsigned* dst = reinterpret_cast<unsigned*>(out.data());
+    auto place_b = [&](const std::vector<int>& tab, std::vector<float>& o) {
+        const size_t n = tab.size() / 2;
+        o.resize(n);
+        unsigned* dst = reinterpret_cast<unsigned*>(o.data());
         for (size_t i = 0; i < n; ++i) {
-            const int a = t.fwd_b[2 * i], part = (a >> 30) & 1;
-            dst[i] = (unsigned)bf16_part(value(a & 0x3fffffff), part) | ((unsigned)bf16_part(value(t.fwd_b[2 * i + 1]), part) << 16);
+            const int a = tab[2 * i], part = (a >> 30) & 1;
+            dst[i] = (unsigned)bf16_part(value(a & 0x3fffffff), part) | ((unsigned)bf16_part(value(tab[2 * i + 1]), part) << 16);
         }
+    };
+    if (hoisted) place_b(t.fwd_bh, *hoisted);
+    if (mode) {
+        place_b(t.fwd_b, out);
     } else {
         out.resize(t.fwd.size());
         for (size_t i = 0; i < out.size(); ++i) out[i] = value(t.fwd[i]);
@@ -360,6 +377,7 @@ void pack_weights_host(const VanerfWeightTable& w, std::vector<float>& out, Laye
         bwd->resize(t.bwd.size());
         for (size_t i = 0; i < bwd->size(); ++i) (*bwd)[i] = value(t.bwd[i]);
     }
+    if (eff_out) *eff_out = std::move(eff);
 }
 
 // slot -> input channel of layer l (2 T entries, slot 2 t + h): >= 0 channel of the reference's [out][in] matrix, -1 unused, -2 bias

@@ -78,6 +78,7 @@ struct DeviceTables {
     int* fwd = nullptr;
     int* bwd = nullptr;
     int* fwd_b = nullptr;
+    int* fwd_bh = nullptr;
 };
 const DeviceTables& device_tables(int device)
 {
@@ -96,6 +97,7 @@ const DeviceTables& device_tables(int device)
         };
         t.bwd = upload(p.bwd);
         t.fwd_b = upload(p.fwd_b);
+        t.fwd_bh = upload(p.fwd_bh);
         t.fwd = upload(p.fwd);
     }
     return t;
@@ -111,7 +113,8 @@ extern "C" int vanerf_weights_update(VanerfWeights* h, const VanerfWeightTable* 
         HIP_CHECK(hipGetDevice(&device));
         if (device != h->device) throw_error("vanerf_weights_update: handle packed on device %d, current device %d", h->device, device);
         const PackTables& p = pack_tables();
-        if (h->n_floats != (h->mode ? p.fwd_b.size() / 2 : p.fwd.size()) || (h->dev_bwd && h->n_floats_bwd != p.bwd.size()))
+        if (h->n_floats != (h->mode ? p.fwd_b.size() / 2 : p.fwd.size()) || (h->dev_bwd && h->n_floats_bwd != p.bwd.size()) ||
+            h->n_floats_h != (h->mode ? p.fwd_bh.size() / 2 : 0))
             throw_error("internal: handle and placement tables disagree on the stream sizes");
         FoldArgs a;
         layer_sources(*dev, a.l); // checks the pointers the layers need
@@ -120,10 +123,13 @@ extern "C" int vanerf_weights_update(VanerfWeights* h, const VanerfWeightTable* 
         hipStream_t s = (hipStream_t)stream;
         hipLaunchKernelGGL(fold_kernel, dim3(128, NUM_LAYERS), dim3(64), 0, s, a, h->dev_eff, sigmoid_beta_dev, h->dev_beta);
         const unsigned n = (unsigned)h->n_floats;
-        if (h->mode)
+        if (h->mode) {
             hipLaunchKernelGGL(place_b_kernel, dim3((n + 255) / 256), dim3(256), 0, s, reinterpret_cast<const int2*>(t.fwd_b), h->dev_eff,
                                reinterpret_cast<unsigned*>(h->dev), n);
-        else
+            const unsigned nh = (unsigned)h->n_floats_h; // the hoisted stream behind it
+            hipLaunchKernelGGL(place_b_kernel, dim3((nh + 255) / 256), dim3(256), 0, s, reinterpret_cast<const int2*>(t.fwd_bh), h->dev_eff,
+                               reinterpret_cast<unsigned*>(h->dev + h->n_floats), nh);
+        } else
             hipLaunchKernelGGL(place_f32_kernel, dim3((n + 255) / 256), dim3(256), 0, s, t.fwd, h->dev_eff, h->dev, n);
         if (h->dev_bwd) {
             const unsigned nb = (unsigned)h->n_floats_bwd;

@@ -6,6 +6,8 @@ TexVisFusion per-frame conv stack).  Every per-ray / per-sample operation runs i
 There is no CPU or eager fallback: every entry point requires CUDA(ROCm) tensors.
 """
 import ctypes
+import os
+import weakref
 from ctypes import byref, c_float, c_int64, c_uint, c_void_p
 
 import torch
@@ -124,6 +126,7 @@ class PackedWeights:
         self.device_index = torch.cuda.current_device() if torch.cuda.is_available() else None  # the handle lives on the device current at the pack
         self._beta = max(float(tab.sigmoid_beta), 2e-3)  # sdf_activation clamp (src/model.py:880)
         self._beta_src = None
+        self.version = 0  # bumped by update(): what was derived from the handle's weights (FrameData.vertex_products) is stale then
 
     @property
     def beta(self):
@@ -141,6 +144,7 @@ class PackedWeights:
             raise ValueError("sigmoid_beta: the device packer takes an fp32 device tensor")
         check(lib.vanerf_weights_update(self.handle, byref(tab), c_void_p(beta.data_ptr()), _stream()))
         self._beta_src = beta
+        self.version += 1
         return self
 
     def short_groups(self):
@@ -158,7 +162,7 @@ class PackedWeights:
 
 
 def stream_host(sd, which):
-    """Host-only packed stream `which` (0 fp32 forward, 1 bf16x3 forward, 2 backward) as raw int32 words (tests)."""
+    """Host-only packed stream `which` (0 fp32 forward, 1 bf16x3 forward, 2 backward, 3 hoisted bf16x3) as raw int32 words (tests)."""
     tab, keep = weight_table(sd)
     n = c_int64()
     check(lib.vanerf_weights_stream_host(byref(tab), which, None, 0, byref(n)))
@@ -168,7 +172,7 @@ def stream_host(sd, which):
 
 
 def stream_device(weights, which):
-    """The stream a handle holds on the device (0 forward of its mode, 2 backward), copied back, as raw int32 words (tests; blocking)."""
+    """The stream a handle holds on the device (0 forward of its mode, 2 backward, 3 hoisted bf16x3), copied back, as raw int32 words (tests; blocking)."""
     n = c_int64()
     check(lib.vanerf_weights_download(weights.handle, which, None, 0, byref(n)))
     out = torch.empty(n.value, dtype=torch.float32)
@@ -351,6 +355,103 @@ class FrameData:
         c.pe_scale = float(sp_args.get("scale", 1.0))
         c.pe_inv_2sigma2 = 1.0 / (2.0 * float(sp_args.get("sigma", 0.1)) ** 2)
         self.c = c
+        self._vertex_products = []  # [weakref to the PackedWeights, its version at the build, table, build stream, event after the build]
+
+    def vertex_products(self, weights):
+        """The frame's table of per-vertex products for a bf16x3 handle (vanerf_vertex_products): the share of three first layers that depends
+        only on the 1-NN vertex, which the hoisted kernel takes as its accumulators' initial values.  None for fp32 handles and under
+        VANERF_VERTEX_PRODUCTS=0 (the un-hoisted kernel, for A/B runs).  Built at the first pass -- the constructor cannot: it does not get the
+        geometry weights -- one launch on the current stream, kept per handle and rebuilt when PackedWeights.update changed the weights."""
+        if weights.mode != 1 or not vertex_products_enabled():
+            return None
+        self._vertex_products = [e for e in self._vertex_products if e[0]() is not None]
+        stream = torch.cuda.current_stream()
+        for e in self._vertex_products:
+            if e[0]() is weights:
+                if e[1] != weights.version:
+                    self._build_vertex_products(weights, e)
+                elif e[3] != stream:  # built on another stream: ordered behind the build, and the allocator told about the reader
+                    stream.wait_event(e[4])
+                    e[2].record_stream(stream)
+                return e[2]
+        n = int(lib.vanerf_vertex_products(None, None, None, 0, None))
+        e = [weakref.ref(weights), None, torch.empty(n, dtype=torch.float32, device=self.vfeat0.device), None, None]
+        self._build_vertex_products(weights, e)
+        self._vertex_products.append(e)
+        return e[2]
+
+    def _build_vertex_products(self, weights, e):
+        stream = torch.cuda.current_stream()
+        if e[3] is not None and e[3] != stream:
+            e[2].record_stream(stream)
+        rc = lib.vanerf_vertex_products(weights.handle, byref(self.c), _ptr(e[2], torch.float32), e[2].numel(), _stream())
+        if rc != 0:
+            check(rc)
+        e[1], e[3], e[4] = weights.version, stream, torch.cuda.Event()
+        e[4].record(stream)
+
+
+# What the table of per-vertex products holds, in the reference's own terms (vanerf_amd/csrc/layer_spec.h, vertex_products.hip).  Columns of the
+# three layers' [out][in] matrices that multiply rows of the per-frame vertex tables, in the reference's concatenation order:
+#   geo_vis_fusion.fconv_at.0 / fconv_ated.0: [pix64 | nn64 | twin64 | sdf | qvis | vis_nn | vis_tw]   (src/networks.py:86-93)
+#   tex_vis_fusion.fconv_at.0: [img3, tex8 | nn11 | twin11 | gf_nn18 | gf_twin18 | lat24 | qvis | vis_nn | vis_tw]   (src/networks.py:285-288)
+# and a vertex row of vfeat_tex is [img3 | tex8 | gf18 | 3 unused]: its first 11 channels go with the `nn11` / `twin11` columns, the next 18
+# with `gf_nn18` / `gf_twin18`.
+GEO_NN_COLS, GEO_TWIN_COLS = tuple(range(64, 128)), tuple(range(128, 192))
+TEX_NN_COLS = tuple(range(11, 22)) + tuple(range(33, 51))
+TEX_TWIN_COLS = tuple(range(22, 33)) + tuple(range(51, 69))
+VERTEX_PRODUCT_PARTS = (("A0", 10, 1, 8), ("N0", 64, 2, 16), ("T0", 64, 2, 16), ("P", 96, 3, 16))  # name, rows, output blocks, registers per block
+
+
+def twin_vertex(i):
+    return (i + NV_HAND) % NV
+
+
+def vertex_products_reference(w_at, w_ated, w_tex, vfeat0, vfeat_tex):
+    """A0 (NV,10), N0, T0 (NV,64), P (NV,96) as plain matrix products in the dtype of the arguments: what vanerf_vertex_products computes in fp32."""
+    tw = twin_vertex(torch.arange(NV, device=vfeat0.device))
+    nn_c, tw_c, tn_c, tt_c = (list(c) for c in (GEO_NN_COLS, GEO_TWIN_COLS, TEX_NN_COLS, TEX_TWIN_COLS))
+    return {"A0": vfeat0 @ w_at[:, nn_c].T + vfeat0[tw] @ w_at[:, tw_c].T,
+            "N0": vfeat0 @ w_ated[:, nn_c].T, "T0": vfeat0[tw] @ w_ated[:, tw_c].T,
+            "P": vfeat_tex[:, :29] @ w_tex[:, tn_c].T + vfeat_tex[tw, :29] @ w_tex[:, tt_c].T}
+
+
+def vertex_products_unpack(table):
+    """The flat table of vanerf_vertex_products -> {"A0": (NV,10), "N0": (NV,64), "T0": (NV,64), "P": (NV,96)} in output-row order, and the
+    largest magnitude among the padding entries (rows beyond a layer's outputs: must be 0).  A vertex's row of a part is laid out
+    [lane half h][block ob][register r] = output row 32 ob + (r & 3) + 8 (r >> 2) + 4 h."""
+    out, at, pad = {}, 0, 0.0
+    for name, rows, nb, nr in VERTEX_PRODUCT_PARTS:
+        width = 2 * nb * nr
+        part = table[at:at + NV * width].view(NV, 2, nb, nr)
+        at += NV * width
+        h, ob, r = torch.meshgrid(torch.arange(2), torch.arange(nb), torch.arange(nr), indexing="ij")
+        row = (32 * ob + (r & 3) + 8 * (r >> 2) + 4 * h).to(table.device)
+        flat = part.reshape(NV, width)
+        keep = (row < rows).reshape(-1)
+        res = torch.zeros(NV, rows, dtype=table.dtype, device=table.device)
+        res[:, row.reshape(-1)[keep]] = flat[:, keep]
+        assert int(keep.sum()) == rows
+        if (~keep).any():
+            pad = max(pad, float(flat[:, ~keep].abs().max()))
+        out[name] = res
+    assert at == table.numel()
+    return out, pad
+
+
+def build_vertex_products(weights, frame):
+    """A fresh table for (weights, frame) on the current stream (vanerf_vertex_products); FrameData.vertex_products keeps one per handle."""
+    n = int(lib.vanerf_vertex_products(None, None, None, 0, None))
+    table = torch.empty(n, dtype=torch.float32, device=frame.vfeat0.device)
+    rc = lib.vanerf_vertex_products(weights.handle, byref(frame.c), _ptr(table, torch.float32), n, _stream())
+    if rc != 0:
+        check(rc)
+    return table
+
+
+def vertex_products_enabled():
+    """VANERF_VERTEX_PRODUCTS=0 keeps every bf16x3 launch on the un-hoisted kernel (read at every pass)."""
+    return os.environ.get("VANERF_VERTEX_PRODUCTS", "1") != "0"
 
 
 # ------------------------------------------------------------------------------------------------
@@ -433,17 +534,20 @@ def query_order(frame, pts):
     return order
 
 
-def query_samples(weights, frame, pts, query_sdf, query_vis, knn_idx, noise=None, want_valid=False, raw=False, order=None):
+def query_samples(weights, frame, pts, query_sdf, query_vis, knn_idx, noise=None, want_valid=False, raw=False, order=None, vertex_products="auto"):
     """VANeRF.query + eval_func (src/model.py:748-957, 1140-1160): (N,3),(N,),(N,)u8,(N,)i32 -> (N,5) [alpha, sdf, r, g, b].
-    order: optional permutation from query_order (work order only; results are unchanged)."""
+    order: optional permutation from query_order (work order only; results are unchanged).
+    vertex_products: "auto" = the frame's table for this handle (FrameData.vertex_products: bf16x3 handles run the hoisted kernel), None = the
+    un-hoisted kernel, or a table from vanerf_vertex_products."""
+    vp = frame.vertex_products(weights) if isinstance(vertex_products, str) else vertex_products
     n = pts.shape[0]
     out = torch.empty(n, 5, dtype=torch.float32, device=pts.device)
     valid = torch.empty(n, dtype=torch.uint8, device=pts.device) if want_valid else None
     if order is not None and order.shape != (n,):
         raise ValueError("order must hold one index per sample")
-    check(lib.vanerf_query_samples(weights.handle, byref(frame.c), _ptr(pts, torch.float32), _ptr(query_sdf, torch.float32),
-                                   _ptr(query_vis, torch.uint8), _ptr(knn_idx, torch.int32), _ptr(noise, torch.float32), _ptr(order, torch.int32),
-                                   int(bool(raw)), n, _ptr(out), _ptr(valid), _ptr(_queue_word(pts.device)), _stream()))
+    check(lib.vanerf_query_samples_vp(weights.handle, byref(frame.c), _ptr(pts, torch.float32), _ptr(query_sdf, torch.float32),
+                                      _ptr(query_vis, torch.uint8), _ptr(knn_idx, torch.int32), _ptr(noise, torch.float32), _ptr(order, torch.int32),
+                                      int(bool(raw)), n, _ptr(out), _ptr(valid), _ptr(_queue_word(pts.device)), _ptr(vp, torch.float32), _stream()))
     return (out, valid) if want_valid else out
 
 
@@ -868,8 +972,9 @@ def render_pass_c(weights, frame, cam_tar, bounds, x0, y0, step, nx, ny, sample_
         setattr(o, k, _ptr(out.get(k)))
     nbytes = int(lib.vanerf_render_pass_scratch(R, Sc, Sf, d.fine, 2 if d.reuse_coarse and noise is not None else d.reuse_coarse))
     scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    check(lib.vanerf_render_pass(weights.handle, byref(frame.c), byref(frame.accel.c), _ptr(frame.verts3, f32), frame.verts3.shape[0],
-                                 _ptr(frame.faces, torch.int32), frame.faces.shape[0], byref(d), byref(o), _ptr(scratch), nbytes, _stream()))
+    check(lib.vanerf_render_pass_vp(weights.handle, byref(frame.c), byref(frame.accel.c), _ptr(frame.verts3, f32), frame.verts3.shape[0],
+                                    _ptr(frame.faces, torch.int32), frame.faces.shape[0], byref(d), byref(o), _ptr(scratch), nbytes,
+                                    _ptr(frame.vertex_products(weights), f32), _stream()))
     return out
 
 
@@ -916,9 +1021,9 @@ def render_pass_views(weights, frame, cam_tars, bounds, x0, y0, step, nx, ny, sa
         raise ValueError(f"{V} views of {nx} x {ny} rays at {Sc} + {Sf} samples: not a valid multi-view pass")
     if scratch is None:
         scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    check(lib.vanerf_render_pass_views(weights.handle, byref(frame.c), byref(frame.accel.c), _ptr(frame.verts3, f32), frame.verts3.shape[0],
-                                       _ptr(frame.faces, torch.int32), frame.faces.shape[0], byref(d), byref(o), _ptr(scratch, torch.uint8), scratch.numel(),
-                                       _stream()))
+    check(lib.vanerf_render_pass_views_vp(weights.handle, byref(frame.c), byref(frame.accel.c), _ptr(frame.verts3, f32), frame.verts3.shape[0],
+                                          _ptr(frame.faces, torch.int32), frame.faces.shape[0], byref(d), byref(o), _ptr(scratch, torch.uint8), scratch.numel(),
+                                          _ptr(frame.vertex_products(weights), f32), _stream()))
     return out
 
 
