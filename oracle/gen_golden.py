@@ -1,7 +1,8 @@
 """Generate the golden fixtures in tests/golden/ by RUNNING THE REFERENCE'S OWN CODE on CPU.
 
 Build-container only (needs /root/reference); never runs on the GPU box and is never imported by
-the product path.  Re-run with:  python -m oracle.gen_golden
+the product path.  Re-run with:  python -m oracle.gen_golden  (everything), or  python -m oracle.gen_golden --posed  (only the
+posed-source-camera fixtures of section x: tests/golden/*_posed.npz; no other file is written).
 
 What is pinned: every pure-torch function of the hot path (SpatialEncoder, feat_sample,
 ray_bbox_intersection, sdf_activation + rgba2out, importance_sample, GeoVisFusion,
@@ -67,7 +68,7 @@ def checksum(v):
     return torch.stack([v.sum(), v.abs().sum(), v[0], v[-1]])
 
 
-def main():
+def main(posed_only=False):
     os.makedirs(OUT, exist_ok=True)
     torch.set_num_threads(8)
     ref = import_reference()
@@ -98,6 +99,8 @@ def main():
     net = M.VANeRF(cfg).eval()
     # init_weights (src/model.py:660-698) as the reference leaves a fresh module after torch.manual_seed(0): a checksum of every entry
     # of the state_dict, and the encoders' feature maps of a seeded image with exactly these weights (sub-sampled values + checksums)
+    write = globals()["save"]
+    save = (lambda name, **arrs: write(name, **arrs) if name.endswith("_posed") else None) if posed_only else write  # (--posed: section x only)
     save("init_checksums", **{k: checksum(v) for k, v in net.state_dict().items()})
     img_e = torch.rand(1, 3, 256, 256, generator=torch.Generator().manual_seed(21))
     with torch.no_grad():
@@ -112,19 +115,72 @@ def main():
     assert not missing.unexpected_keys
     sd = {k: v.detach().clone() for k, v in net.state_dict().items()}
     # full key/shape inventory of the reference module (drop-in contract: checkpoints must load unchanged)
-    with open(os.path.join(OUT, "state_dict_keys.json"), "w") as f:
-        json.dump({k: list(v.shape) for k, v in sd.items()}, f, indent=0)
+    if not posed_only:
+        with open(os.path.join(OUT, "state_dict_keys.json"), "w") as f:
+            json.dump({k: list(v.shape) for k, v in sd.items()}, f, indent=0)
     # encoder outputs for the 256x256 source image (shape contract of attach_geo_feat / attach_tex_feat)
     with torch.no_grad():
         fg = net.attach_geo_feat(torch.rand(1, 3, 256, 256), return_val=True)
         ft = net.attach_tex_feat(torch.rand(1, 3, 256, 256), return_val=True)
-    with open(os.path.join(OUT, "encoder_shapes.json"), "w") as f:
-        json.dump({"feat_geo": [list(t.shape) for t in fg], "feat_tex": list(ft.shape)}, f)
+    if not posed_only:
+        with open(os.path.join(OUT, "encoder_shapes.json"), "w") as f:
+            json.dump({"feat_geo": [list(t.shape) for t in fg], "feat_tex": list(ft.shape)}, f)
     hot = {k: v for k, v in sd.items() if k.startswith(HOT_PREFIXES)}
     save("weights_hot", **hot)
     big = {k: v for k, v in sd.items() if k.startswith("tex_vis_fusion.") and k not in hot}
     save("weights_texframe_checksum", **{k: torch.stack([v.double().sum(), v.double().abs().sum(), v.flatten()[0].double(),
                                                           v.flatten()[-1].double()]) for k, v in big.items()})
+
+    # one whole pass of the reference -> tests/golden/<tag>.npz (sections viii and x)
+    def run_pass(frame, level, stride_xy, S, tag, keep_inter, gt=False):
+        calls.clear()
+        strd = torch.tensor([stride_xy], dtype=torch.float32)
+        extra = {}
+        if gt:  # GT gathers of src/model.py:1361-1418: a seeded target image and target mask
+            gg = torch.Generator().manual_seed(31)
+            hw = (int(frame["cam_tar"]["height"]), int(frame["cam_tar"]["width"]))
+            extra = dict(tar_img=torch.rand(1, 3, *hw, generator=gg), msk=torch.rand(1, *hw, generator=gg) > 0.5)
+        with torch.no_grad():
+            o = M.VANeRF.batch_render_pifu_nerf(net, frame["img_in"], frame["cam_in"], frame["hand_type"], frame["targets"], 1,
+                                                frame["cam_tar"], level, strd, extra.get("tar_img"), frame["feat_geo"], frame["feat_tex"], None,
+                                                copy.copy(frame["sp_data"]), None, fine=True, uniform=True, sample_per_ray_c=S,
+                                                sample_per_ray_f=S, src_foreground_mask=frame["src_foreground_mask"],
+                                                bounds=frame["bounds"], mask_at_box=None, **({"msk": extra["msk"]} if gt else {}))
+        keep = {k: o[k] for k in ("tex_fg", "depth", "alpha", "tex_fg_fine", "depth_fine", "alpha_fine", "sdf", "vert_vis")}
+        if gt:
+            keep.update(gt_tar_img_in=extra["tar_img"], gt_msk_in=extra["msk"], **{"gt_" + k: o[k] for k in ("tar_img", "tar_alpha", "input_mask", "img_in", "vis_img")})
+        if keep_inter:
+            keep.update(pts_coarse=calls[0]["points"], sdf_coarse=calls[0]["sdf"], vis_coarse=calls[0]["vis"],
+                        pts_fine=calls[1]["points"], sdf_fine=calls[1]["sdf"], vis_fine=calls[1]["vis"])
+        save(tag, level=level, stride_xy=np.asarray(stride_xy), S=S, **keep)
+        return o
+
+    def posed_fixtures():
+        """(x) The reference's own query and whole pass under a posed, off-centre source camera (synth.SOURCE_POSES["A"] on the seed-3 frame with
+        half the source view masked): tests/golden/query_posed.npz and pass_16x16_s16_posed.npz.  New files only; nothing else is rewritten."""
+        fr = synth.pose_source_camera(synth.make_frame(seed=3, tar_h=64, tar_w=64, half_mask=True), **synth.SOURCE_POSES["A"])
+        gq = torch.Generator().manual_seed(2)
+        v3 = fr["targets"]["vert_world"]
+        n = 2048 + 5  # the points of tests.test_hip_parity._points_near_mesh(frame, 2048 + 5, seed=2): near the mesh, off the image, on vertices
+        p = v3[0, torch.randint(0, 1558, (n,), generator=gq)] + 0.012 * torch.randn(n, 3, generator=gq)
+        p[: n // 16] += torch.tensor([0.5, 0.0, 0.0])
+        p[n // 16: n // 8] = v3[0, torch.randint(0, 1558, (n // 8 - n // 16,), generator=gq)]
+        p = p.contiguous()[None]
+        xy01, z01 = orc.source_vert_xyz01(v3, fr["cam_in"])
+        q_sdf, q_vis, vert_vis, _ = orc.cal_vis_sdf_batch(v3, fr["targets"]["face_world"].long(), p, xy01, z01)
+        view = torch.nn.functional.normalize(torch.ones_like(p), dim=-1)
+        with torch.no_grad():
+            out, valid = net.query(p, fr["cam_in"], fr["hand_type"], fr["targets"], fr["feat_geo"], fr["feat_tex"], vert_vis=vert_vis,
+                                   query_sdf=q_sdf, query_vis=q_vis, closest_face=None, n_views=1, view=view, nerf=True,
+                                   sp_data=copy.copy(fr["sp_data"]), tx_data={"img": fr["img_in"]}, n_pts_samples=1,  # (n is no multiple of 16)
+                                   src_foreground_mask=fr["src_foreground_mask"])
+        save("query_posed", pts=p, q_sdf=q_sdf, q_vis=q_vis, vert_vis=vert_vis, out=out, valid=valid, extrin=fr["cam_in"]["extrin"],
+             KRT=fr["cam_in"]["KRT"])
+        run_pass(fr, 3, [1, 2], 16, "pass_16x16_s16_posed", False)
+
+    if posed_only:
+        posed_fixtures()
+        return
 
     # ---- (i) SpatialEncoder + (ii) position_embedding -----------------------------------------
     g = torch.Generator().manual_seed(1)
@@ -235,30 +291,7 @@ def main():
     with torch.no_grad():
         save("ibr_head_v2", rgb_feats=rf, ray_diffs=rd, proj_mask=pm, out=net.mlp_tex(rf.clone(), rd, pm))
 
-    # ---- (viii) whole pass ------------------------------------------------------------------------
-    def run_pass(frame, level, stride_xy, S, tag, keep_inter, gt=False):
-        calls.clear()
-        strd = torch.tensor([stride_xy], dtype=torch.float32)
-        extra = {}
-        if gt:  # GT gathers of src/model.py:1361-1418: a seeded target image and target mask
-            gg = torch.Generator().manual_seed(31)
-            hw = (int(frame["cam_tar"]["height"]), int(frame["cam_tar"]["width"]))
-            extra = dict(tar_img=torch.rand(1, 3, *hw, generator=gg), msk=torch.rand(1, *hw, generator=gg) > 0.5)
-        with torch.no_grad():
-            o = M.VANeRF.batch_render_pifu_nerf(net, frame["img_in"], frame["cam_in"], frame["hand_type"], frame["targets"], 1,
-                                                frame["cam_tar"], level, strd, extra.get("tar_img"), frame["feat_geo"], frame["feat_tex"], None,
-                                                copy.copy(frame["sp_data"]), None, fine=True, uniform=True, sample_per_ray_c=S,
-                                                sample_per_ray_f=S, src_foreground_mask=frame["src_foreground_mask"],
-                                                bounds=frame["bounds"], mask_at_box=None, **({"msk": extra["msk"]} if gt else {}))
-        keep = {k: o[k] for k in ("tex_fg", "depth", "alpha", "tex_fg_fine", "depth_fine", "alpha_fine", "sdf", "vert_vis")}
-        if gt:
-            keep.update(gt_tar_img_in=extra["tar_img"], gt_msk_in=extra["msk"], **{"gt_" + k: o[k] for k in ("tar_img", "tar_alpha", "input_mask", "img_in", "vis_img")})
-        if keep_inter:
-            keep.update(pts_coarse=calls[0]["points"], sdf_coarse=calls[0]["sdf"], vis_coarse=calls[0]["vis"],
-                        pts_fine=calls[1]["points"], sdf_fine=calls[1]["sdf"], vis_fine=calls[1]["vis"])
-        save(tag, level=level, stride_xy=np.asarray(stride_xy), S=S, **keep)
-        return o
-
+    # ---- (viii) whole passes (run_pass above) ---------------------------------------------------------
     run_pass(frame, 4, [3, 5], 16, "pass_8x8_s16", True, gt=True)
     frame_b = synth.make_frame(seed=5, tar_h=64, tar_w=64, orbit_deg=70.0, half_mask=True)
     run_pass(frame_b, 3, [1, 2], 24, "pass_16x16_s24_bvv", False)
@@ -313,7 +346,9 @@ def main():
                                       sp_data=copy.copy(fr["sp_data"]), fine=True, uniform=True, sample_per_ray_c=8, sample_per_ray_f=8,
                                       src_foreground_mask=fr["src_foreground_mask"], bounds=fr["bounds"], mask_at_box=None)
     save("render_full_16x16", **{k: o[k] for k in ("tex_fg", "tex_fg_fine", "depth_fine", "alpha_fine", "sdf", "vert_xy")})
+    del net.attach_geo_feat, net.attach_tex_feat
+    posed_fixtures()
 
 
 if __name__ == "__main__":
-    main()
+    main(posed_only="--posed" in sys.argv[1:])

@@ -163,15 +163,12 @@ def _run(HB, R, env, pts, d, noise=None, d2=None, noise2=None, ws=None, oracle_n
 VARIANTS = {"d": (False, False), "d_noise": (True, False), "d_d2_noise": (True, True)}
 
 
-@pytest.mark.parametrize("variant", list(VARIANTS))
-def test_fused_backward_per_sample_against_fp64(env, variant):
-    """IG (all nine tensors), Ys (every layer), Xs (every slot) and the block's parameter gradients against fp64 autograd, sample by sample:
-    real rays at the training configuration (valid and invalid samples), points around both hands, and hand-placed points at the border of
-    the source view (eps band, pixel-weight ramp), at z = -1 and z = 1, at the foreground-mask edge; q_vis 0 and 1, nearest vertices on the
-    other hand and with vert_vis = 0.  eval_func's derivative inside the backward: d only, d + noise, d + d2 + noise + noise2 (the coarse
-    samples inside a fine batch).  Invalid samples: exact zeros in the geometry branch's IG and in the sdf / alpha rows of the head's Ys."""
+def check_block_against_fp64(env, pts, variant):
+    """One block of `pts` (n, 3) of env's frame through the fused backward against fp64 autograd, sample by sample, with this file's bounds:
+    IG (all nine tensors), Ys (every layer), Xs (every slot) and the block's parameter gradients (vanerf_weight_products); exact zeros where
+    the reference's are.  env = (HB, R, sd, frame, fdat, w0) as the fixture above builds it (tests/test_posed_source.py builds one around a
+    posed source camera).  Returns (valid, knn, q_vis, flip, worst = {tensor: (HB error, plain fp32 error)})."""
     HB, R, sd, frame, fdat, w0 = env
-    pts = _points(R, frame, fdat)
     n = pts.shape[0]
     g = torch.Generator().manual_seed(7)
     d, d2 = torch.randn(n, 5, generator=g), torch.randn(n, 5, generator=g)
@@ -180,11 +177,7 @@ def test_fused_backward_per_sample_against_fp64(env, variant):
     ws, ig, ref, flip, knn, q_vis, r32 = _run(HB, R, env, pts, d, noise if use_noise else None, d2 if use_d2 else None,
                                          noise2 if use_d2 else None)
     valid = ref["valid"]
-    nn_vis = fdat.vert_vis.cpu()[knn]
-    # the edges are there: 1-NN index bit-exact, both validities, both q_vis, the other hand, invisible nearest vertices
-    assert torch.equal(knn, orc.knn1(pts, frame["targets"]["vert_world"][0]))
-    assert 0.2 < valid.float().mean() < 0.9 and bool(q_vis.any()) and not bool(q_vis.all())
-    assert bool((knn >= orc.NUM_V).any()) and bool((knn < orc.NUM_V).any()) and bool((nn_vis == 0).any()) and bool((nn_vis[valid] == 0).any())
+    assert torch.equal(knn, orc.knn1(pts, frame["targets"]["vert_world"][0]))  # 1-NN index: bit-exact
     assert flip.float().mean() <= 0.01, f"{int(flip.sum())} of {n} samples took another ReLU branch in fp32"
     worst = {}
     # a. IG: the gradients of the gathered inputs
@@ -223,6 +216,23 @@ def test_fused_backward_per_sample_against_fp64(env, variant):
     print(f"[{variant}] n {n}, valid {valid.float().mean().item():.3f}, decision flips {int(flip.sum())} ({flip.float().mean().item():.2e})")
     for k, (e, e32) in worst.items():
         print(f"  {k:50s} HIP {e:.2e}  plain fp32 {e32:.2e}")
+    return valid, knn, q_vis, flip, worst
+
+
+@pytest.mark.parametrize("variant", list(VARIANTS))
+def test_fused_backward_per_sample_against_fp64(env, variant):
+    """IG (all nine tensors), Ys (every layer), Xs (every slot) and the block's parameter gradients against fp64 autograd, sample by sample:
+    real rays at the training configuration (valid and invalid samples), points around both hands, and hand-placed points at the border of
+    the source view (eps band, pixel-weight ramp), at z = -1 and z = 1, at the foreground-mask edge; q_vis 0 and 1, nearest vertices on the
+    other hand and with vert_vis = 0.  eval_func's derivative inside the backward: d only, d + noise, d + d2 + noise + noise2 (the coarse
+    samples inside a fine batch).  Invalid samples: exact zeros in the geometry branch's IG and in the sdf / alpha rows of the head's Ys."""
+    HB, R, sd, frame, fdat, w0 = env
+    pts = _points(R, frame, fdat)
+    valid, knn, q_vis, flip, _ = check_block_against_fp64(env, pts, variant)
+    nn_vis = fdat.vert_vis.cpu()[knn]
+    # the edges are there: both validities, both q_vis, the other hand, invisible nearest vertices
+    assert 0.2 < valid.float().mean() < 0.9 and bool(q_vis.any()) and not bool(q_vis.all())
+    assert bool((knn >= orc.NUM_V).any()) and bool((knn < orc.NUM_V).any()) and bool((nn_vis == 0).any()) and bool((nn_vis[valid] == 0).any())
 
 
 def test_noise_at_the_relu_kink_and_invalid_samples(env):

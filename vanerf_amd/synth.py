@@ -148,6 +148,34 @@ def make_frame(seed=0, tar_h=64, tar_w=64, src_hw=256, orbit_deg=8.0, device="cp
     return to_device(frame, device)
 
 
+def pose_source_camera(frame, yaw, pitch, roll, dist, focal_xy, princpt):
+    """A copy of `frame` whose SOURCE camera is posed and off-centre (make_frame's is the identity with the principal point at the image
+    centre and one focal length, which hides a transposed rotation, a dropped translation and an x/y swap): it looks at the mesh centre from
+    `dist` away, eye = centre + dist (sin yaw cos pitch, sin pitch, -cos yaw cos pitch), then rolls about its optical axis,
+    E = Rz(roll) @ look_at; angles in degrees, focal_xy = (fx, fy) and princpt = (cx, cy) in source pixels.  cam_in's KRT / K / Rt / extrin
+    and sp_data's extrin are replaced consistently; every other entry is shared with `frame` and the source view stays 256 x 256."""
+    dev = frame["cam_in"]["KRT"].device
+    centre = frame["targets"]["vert_world"][0].mean(0).cpu().numpy().astype(np.float64)
+    a, b, r = math.radians(yaw), math.radians(pitch), math.radians(roll)
+    eye = centre + dist * np.array([math.sin(a) * math.cos(b), math.sin(b), -math.cos(a) * math.cos(b)])
+    Rz = np.eye(4)
+    Rz[:2, :2] = [[math.cos(r), -math.sin(r)], [math.sin(r), math.cos(r)]]
+    E = torch.from_numpy((Rz @ look_at_extrinsic(eye, centre).astype(np.float64)).astype(np.float32))
+    K = torch.eye(4)
+    K[0, 0], K[1, 1] = float(focal_xy[0]), float(focal_xy[1])
+    K[0, 2], K[1, 2] = float(princpt[0]), float(princpt[1])
+    E, K = E.to(dev), K.to(dev)
+    out = dict(frame)
+    out["cam_in"] = dict(frame["cam_in"], KRT=(K @ E)[None], K=K[None], Rt=E[None, :3, :4], extrin=E[None])
+    out["sp_data"] = dict(frame["sp_data"], extrin=E[None].clone())
+    return out
+
+
+# the two posed source cameras of tests/test_posed_source.py and of the reference fixtures tests/golden/*_posed.npz (oracle/gen_golden.py)
+SOURCE_POSES = {"A": dict(yaw=25.0, pitch=-10.0, roll=12.0, dist=1.05, focal_xy=(1150.0, 1230.0), princpt=(101.0, 149.0)),
+                "B": dict(yaw=-40.0, pitch=20.0, roll=-35.0, dist=1.05, focal_xy=(1100.0, 1100.0), princpt=(140.0, 110.0))}
+
+
 def p3d_tar_cam(cam_tar):
     """targets['tar_cam'] in pytorch3d's convention, as the reference's dataset builds it from the OpenCV target camera
     (src/dataset.py:501-503): tar_R = (F R_cv)^T, tar_T = F t_cv with F = diag(-1, -1, 1); focal and principal point from K.
