@@ -163,11 +163,13 @@ def _run(HB, R, env, pts, d, noise=None, d2=None, noise2=None, ws=None, oracle_n
 VARIANTS = {"d": (False, False), "d_noise": (True, False), "d_d2_noise": (True, True)}
 
 
-def check_block_against_fp64(env, pts, variant):
+def check_block_against_fp64(env, pts, variant, zeros_exact=False):
     """One block of `pts` (n, 3) of env's frame through the fused backward against fp64 autograd, sample by sample, with this file's bounds:
     IG (all nine tensors), Ys (every layer), Xs (every slot) and the block's parameter gradients (vanerf_weight_products); exact zeros where
     the reference's are.  env = (HB, R, sd, frame, fdat, w0) as the fixture above builds it (tests/test_posed_source.py builds one around a
-    posed source camera).  Returns (valid, knn, q_vis, flip, worst = {tensor: (HB error, plain fp32 error)})."""
+    posed source camera; tests/test_weight_families.py around other weights).  zeros_exact: every parameter gradient that fp64 autograd gives
+    as an exact zero must be an exact zero (their number is returned as worst["exact zeros"]).
+    Returns (valid, knn, q_vis, flip, worst = {tensor: (HB error, plain fp32 error)})."""
     HB, R, sd, frame, fdat, w0 = env
     n = pts.shape[0]
     g = torch.Generator().manual_seed(7)
@@ -204,6 +206,7 @@ def check_block_against_fp64(env, pts, variant):
     # d. parameter gradients of the block (slot -> channel map, duplicated slots, weight-norm fold, biases)
     P = {k: v.cuda() for k, v in sd.items()}
     got = HB.parameter_gradients(ws, P)
+    n_zero = 0
     for spec in LAYER_PARAMS:
         for key in param_keys(spec):
             want = ref["d_params"][key]
@@ -211,11 +214,18 @@ def check_block_against_fp64(env, pts, variant):
             e32 = ((r32["d_params"][key].double() - want).abs().max() / want.abs().max()).item()
             worst["dP " + key] = (e, e32)
             assert e <= TOL + 3.0 * e32, (key, e, e32)
+            if zeros_exact:
+                zero = want == 0
+                assert torch.equal(got[key].cpu()[zero], torch.zeros(int(zero.sum()))), (key, int((got[key].cpu()[zero] != 0).sum()), int(zero.sum()))
+                n_zero += int(zero.sum())
     fc2 = got["tex_vis_fusion.fconv.2.weight"]
     assert torch.equal(fc2[3:], torch.zeros_like(fc2[3:]))
     print(f"[{variant}] n {n}, valid {valid.float().mean().item():.3f}, decision flips {int(flip.sum())} ({flip.float().mean().item():.2e})")
     for k, (e, e32) in worst.items():
         print(f"  {k:50s} HIP {e:.2e}  plain fp32 {e32:.2e}")
+    if zeros_exact:
+        worst["exact zeros"] = n_zero
+        print(f"  exact zeros among the parameter gradients: {n_zero}")
     return valid, knn, q_vis, flip, worst
 
 

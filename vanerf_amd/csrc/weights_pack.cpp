@@ -288,6 +288,7 @@ inline unsigned short bf16_rne(float f)
 {
     unsigned u;
     std::memcpy(&u, &f, 4);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return 0x7fc0; // NaN stays NaN (the rounding add would carry a full payload over into -0.0); torch's constant
     return (unsigned short)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
 }
 inline float bf16_to_f32(unsigned short b)

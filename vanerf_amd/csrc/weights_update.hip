@@ -55,6 +55,7 @@ __global__ void place_f32_kernel(const int* __restrict__ tab, const float* __res
 __device__ inline unsigned bf16_rne(float f)
 {
     const unsigned u = __float_as_uint(f);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return 0x7fc0u; // NaN stays NaN, as in weights_pack.cpp
     return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
 }
 __device__ inline unsigned bf16_part(float v, int part)

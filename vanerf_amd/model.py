@@ -26,6 +26,7 @@ import torch.nn.functional as thf
 
 from . import renderer as R
 from .losses import compute_error
+from .synth import PACKED_PREFIXES
 
 NUM_V = 779
 
@@ -314,20 +315,22 @@ class VANeRF(nn.Module):
 
     def _packed_for(self, slot, precision, sd, key):
         """The handle of `precision`, packed on first use and re-packed when a parameter changed: in place on the device when the parameters
-        live there (training: vanerf_weights_update, nothing blocks), through the host otherwise."""
+        live there (training: vanerf_weights_update, nothing blocks), through the host otherwise.  A held handle of the other mode (the
+        module's `precision` was changed since) is never re-used: vanerf_weights_update keeps the handle's mode, so a fresh pack replaces it."""
         held = getattr(self, slot, None)
         if held is not None and held[0] == key:
             return held[1]
         hot = {k: v for k, v in sd.items() if k.startswith(self._PACKED_PREFIXES)}
-        if held is not None and all(v.is_cuda and v.dtype == torch.float32 and v.is_contiguous() for v in hot.values()) \
-                and held[1].device_index == next(iter(hot.values())).device.index == torch.cuda.current_device():
+        same_mode = held is not None and held[1].mode == R.PRECISIONS[precision]
+        on_device = all(v.is_cuda and v.dtype == torch.float32 and v.is_contiguous() for v in hot.values())
+        if same_mode and on_device and held[1].device_index == next(iter(hot.values())).device.index == torch.cuda.current_device():
             w = held[1].update(sd)
         else:
             w = R.PackedWeights(sd, mode=precision)
         setattr(self, slot, (key, w))
         return w
 
-    _PACKED_PREFIXES = ("geo_vis_fusion.", "mlp_geo.", "ibr_compress_gfeat.", "tex_vis_fusion.fconv.", "tex_vis_fusion.fconv_at.", "sigmoid_beta")
+    _PACKED_PREFIXES = PACKED_PREFIXES  # (synth.py: the synthetic weight families rewrite exactly these entries)
 
     def packed_weights(self, precision=None):
         """MFMA-fragment copy of the per-sample weights, re-packed whenever a parameter changed (training steps, load_state_dict).

@@ -298,3 +298,141 @@ def make_ibr_weights(seed=0):
         sd[f"mlp_tex.{k}.weight"] = torch.randn(o, i, generator=g) * math.sqrt(2.0 / i)
         sd[f"mlp_tex.{k}.bias"] = torch.zeros(o)
     return sd
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# weight families: the same keys and shapes as make_full_weights, other kinds of numbers (tests/test_weight_families.py)
+# ---------------------------------------------------------------------------------------------------------------------
+# the state_dict entries the packed weight streams are built from (VANeRF._PACKED_PREFIXES is this tuple)
+PACKED_PREFIXES = ("geo_vis_fusion.", "mlp_geo.", "ibr_compress_gfeat.", "tex_vis_fusion.fconv.", "tex_vis_fusion.fconv_at.", "sigmoid_beta")
+WEIGHT_FAMILIES = ("wide", "ties", "sparse", "gains")
+WIDE_DECADES = 6.0
+# two planted magnitudes per row.  2^-130 (1 + 2^-4 + 2^-9): an fp32 subnormal; its high bf16 part is a bf16 subnormal (step 2^-133) and the
+# remainder lies below half a step, so its low part is +-0.  2^-121 (1 + 2^-4 + 2^-9): normal, high part 2^-121 + 2^-125 (step 2^-128), low
+# part 2^-130: a bf16 subnormal that is not zero -- a packer that flushes subnormals loses it.
+WIDE_TINY = (2.0 ** -130 * (1.0 + 2.0 ** -4 + 2.0 ** -9), 2.0 ** -121 * (1.0 + 2.0 ** -4 + 2.0 ** -9))
+SPARSE_ZERO_SHARE = 0.9
+GAINS_RANGE = (0.05, 30.0)
+GAINS_BETAS = (0.5, 0.02, 1e-3)  # by seed % 3; the last lies below sdf_activation's clamp (2e-3)
+_HEAD_BIAS = "mlp_geo.layers2.layers.2.linear.bias"
+# rad = W x + b of the density head re-centred per family and seed: minus the median of W x over the valid samples of the posed test
+# frame (fp64 oracle, 2 000 points near the mesh of pose A; tests/test_weight_families.py asserts the share of alpha > 0 this gives).
+# A seed without an entry is refused: its share of alpha > 0 is not assured until an entry is tuned for it.
+_HEAD_RAD_BIAS = {"wide": (0.9011, -0.2202, 0.0395), "ties": (-0.5902, 0.3138, 0.1246), "sparse": (-0.2520, 0.0704, 0.1943),
+                  "gains": (-3339.3, 2084.8, 1438.4)}
+
+
+def _family_matrices(sd):
+    """The packed entries that are matrices (conv / linear weights, weight-norm directions) and those that are biases."""
+    packed = [k for k in sd if k.startswith(PACKED_PREFIXES)]
+    return [k for k in packed if k.endswith(("weight", "weight_v"))], [k for k in packed if k.endswith("bias")]
+
+
+def _norm_as_packed(v):
+    """||v|| of every row as the packers compute it: the squares summed in double in index order, the root rounded to fp32."""
+    return v.double().pow(2).cumsum(1)[:, -1].sqrt().float()
+
+
+def sparse_zero_lines(shape, weight_norm):
+    """How many all-zero output rows / input columns the 'sparse' family gives a matrix: two of each; fewer rows where two would leave
+    nothing (one of 3 rows, none of 2), and no zero row in a weight-norm direction (its norm divides)."""
+    rows = 0 if weight_norm else max(0, min(2, shape[0] - 2))
+    return rows, 2
+
+
+def make_weight_family(name, seed=0, sigmoid_beta=None):
+    """make_full_weights(seed) with the entries of the packed streams (PACKED_PREFIXES) rewritten, same keys and shapes, fp32:
+
+    "wide"   magnitudes log-uniform over WIDE_DECADES decades within every matrix (|w| in [1e-6 s, s], the recipe's signs, s chosen to
+             keep the matrix's root mean square), two elements per row at +-WIDE_TINY: an fp32 subnormal, and a small normal number whose low bf16
+             part is a subnormal.
+    "ties"   every weight and bias snapped to a value whose bf16 rounding is a decision -- by element index mod 3: exactly half-way
+             between two bf16 neighbours (low half 0x8000; both parities of the lower neighbour occur); one fp32 ulp either side of such
+             a tie (0x7fff / 0x8001); a bf16 significand of all ones below a tie or above it (0x..7f8000 / 0x..7fffff), so that the
+             rounding carries into the next exponent.  Weight-norm rows are first scaled to the recipe's folded size and get
+             weight_g = ||v|| as the packers compute it: the fold multiplies by exactly 1 and the folded value is the snapped one.
+    "sparse" SPARSE_ZERO_SHARE exact zeros (an eighth of them -0.0), exactly sparse_zero_lines() all-zero output rows and input columns per
+             matrix (every other row and column keeps a value), the remaining values scaled by (1 - share)^-1/4 (half of what would keep the
+             variance: the fp32 oracle itself misses 1e-4 on rad at the full factor); half the biases 0.
+    "gains"  the recipe's matrices with weight_g log-uniform over GAINS_RANGE per row and sigmoid_beta = GAINS_BETAS[seed % 3] (or the
+             argument).
+    In every family the density head's second bias is re-centred (_HEAD_RAD_BIAS) so that alpha > 0 on a share of the samples."""
+    if name not in WEIGHT_FAMILIES:
+        raise ValueError(f"weight family must be one of {WEIGHT_FAMILIES}")
+    if not 0 <= seed < len(_HEAD_RAD_BIAS[name]):
+        raise ValueError(f"weight family {name!r} has a tuned density-head bias for seeds 0..{len(_HEAD_RAD_BIAS[name]) - 1} only")
+    sd = make_full_weights(seed)
+    g = torch.Generator().manual_seed(3000 + 10 * seed + WEIGHT_FAMILIES.index(name))
+    mats, biases = _family_matrices(sd)
+    for k in mats:
+        w = sd[k]
+        m = w.reshape(w.shape[0], -1).clone()
+        wn = k.endswith("weight_v")
+        if name == "wide":
+            s = m.pow(2).mean().sqrt() * math.sqrt(2.0 * WIDE_DECADES * math.log(10.0))  # E w^2 of the log-uniform law is s^2 / (2 D ln 10)
+            sign = torch.where(m < 0, -1.0, 1.0)
+            m = sign * s * 10.0 ** (-WIDE_DECADES * torch.rand(m.shape, generator=g))
+            rows = torch.arange(m.shape[0])
+            col = torch.randint(0, m.shape[1], (m.shape[0],), generator=g)
+            for c, tiny in ((col, WIDE_TINY[0]), ((col + 1 + torch.randint(0, m.shape[1] - 1, col.shape, generator=g)) % m.shape[1], WIDE_TINY[1])):
+                m[rows, c] = sign[rows, c] * tiny
+        elif name == "ties":
+            if wn:
+                m = m * (sd[k[:-1] + "g"].reshape(-1, 1) / m.norm(2, dim=1, keepdim=True))
+            m = _snap_to_ties(m)
+            if wn:
+                sd[k[:-1] + "g"] = _norm_as_packed(m).reshape(-1, 1)
+        elif name == "sparse":
+            keep = torch.rand(m.shape, generator=g) >= SPARSE_ZERO_SHARE
+            n_rows, n_cols = sparse_zero_lines(m.shape, wn)
+            rows = torch.randperm(m.shape[0], generator=g)[:n_rows]
+            cols = torch.randperm(m.shape[1], generator=g)[:n_cols]
+            keep[rows] = False
+            keep[:, cols] = False
+            # no other empty row or column (a weight-norm row must keep a norm; and the counts are then exact): one value put back
+            live_r = torch.ones(m.shape[0], dtype=torch.bool)
+            live_c = torch.ones(m.shape[1], dtype=torch.bool)
+            live_r[rows], live_c[cols] = False, False
+            live_r, live_c = live_r.nonzero().view(-1), live_c.nonzero().view(-1)
+            for r in live_r[~keep[live_r].any(1)]:
+                keep[r, live_c[torch.randint(0, live_c.numel(), (1,), generator=g)]] = True
+            for c in live_c[~keep[:, live_c].any(0)]:
+                keep[live_r[torch.randint(0, live_r.numel(), (1,), generator=g)], c] = True
+            zero = torch.where(torch.rand(m.shape, generator=g) < 0.125, -0.0, 0.0)
+            m = torch.where(keep, m * (1.0 - SPARSE_ZERO_SHARE) ** -0.25, zero)
+        sd[k] = m.reshape(w.shape).contiguous()
+    for k in biases:
+        if name == "ties":
+            sd[k] = _snap_to_ties(sd[k].reshape(1, -1)).reshape(-1)
+        elif name == "sparse":
+            b = sd[k].clone()
+            zero = torch.randperm(b.numel(), generator=g)[: (b.numel() + 1) // 2]
+            b[zero] = 0.0
+            b[zero[::4]] = -0.0
+            sd[k] = b
+    if name == "gains":
+        lo, hi = GAINS_RANGE
+        for k in [k for k in sd if k.endswith("weight_g")]:
+            sd[k] = lo * (hi / lo) ** torch.rand(sd[k].shape, generator=g)
+        sd["sigmoid_beta"] = torch.tensor([GAINS_BETAS[seed % 3] if sigmoid_beta is None else sigmoid_beta])
+    elif sigmoid_beta is not None:
+        sd["sigmoid_beta"] = torch.tensor([float(sigmoid_beta)])
+    head = sd[_HEAD_BIAS].clone()
+    head[1] = _HEAD_RAD_BIAS[name][seed]
+    sd[_HEAD_BIAS] = _snap_to_ties(head.reshape(1, -1)).reshape(-1) if name == "ties" else head
+    return sd
+
+
+def _snap_to_ties(m):
+    """fp32 values of (rows, n) -> a 'bf16 rounding is a decision' pattern just above the value cut to bf16 (kinds 0, 1) or just below its
+    power of two (kind 2: magnitudes shrink, activations stay in the recipe's range), by column index mod 3, and the row's parity for the
+    side: 0 an exact tie, 1 a tie -+ one fp32 ulp, 2 an all-ones bf16 significand at / above the tie (the rounding carries)."""
+    bits = m.contiguous().view(torch.int32).clone()
+    top = bits & ~0xffff  # sign, exponent and the seven significand bits a bf16 keeps (truncated)
+    tiny = (top & 0x7f800000) == 0
+    top = torch.where(tiny, (top & ~0x7fffffff) | 0x3c000000, top)  # (nothing smaller than 2^-7: zeros / subnormals have no tie to speak of)
+    kind = (torch.arange(m.shape[1]) % 3)[None].expand_as(bits)
+    side = ((torch.arange(m.shape[0])[:, None] + torch.arange(m.shape[1])[None] // 3) % 2).expand_as(bits)
+    low = torch.where(kind == 0, 0x8000, torch.where(kind == 1, torch.where(side == 0, 0x7fff, 0x8001), torch.where(side == 0, 0x8000, 0xffff)))
+    top = torch.where(kind == 2, (top - 0x00800000) | 0x007f0000, top)  # the binade below, all ones: rounds up to the value's own power of two
+    return (top | low.to(torch.int32)).view(torch.float32)
