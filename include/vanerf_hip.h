@@ -487,6 +487,47 @@ int64_t vanerf_mask_at_box_scratch(int V, int H, int W);
 int vanerf_mask_at_box(const float* cams, int V, int H, int W, const float bounds[6], uint8_t* mask, float* near, float* far, void* scratch,
                        int64_t scratch_bytes, float* out, void* stream);
 
+/* The learned surface as a triangle mesh.  The network predicts a residual on the MANO signed distance: with
+ * alpha = valid relu(rad) of eval_func (src/model.py:1140-1160) the composite turns f = alpha + mesh_sdf into a density (1480-1481), and the
+ * hand is the zero level set of f.  Four calls: points of a regular grid, f from the outputs of the two queries on them, and marching
+ * tetrahedra over the grid of scalars in two steps with one host read (the counts) between them.
+ *
+ * A grid is origin[3], spacing[3] (HOST, read before the call returns; finite, spacing > 0) and nx, ny, nz >= 2 points per axis with
+ * 7 nx ny nz < 2^31; point (x, y, z) has the linear index (z ny + y) nx + x and the position fmaf(index, spacing, origin) per axis: one
+ * rounding, the same expression in every call below.
+ *
+ *     vanerf_grid_points: pts[nz_out ny nx][3] (device) = the points of layers z0 ... z0 + nz_out - 1 (a slab of the grid; 0 <= z0,
+ *         z0 + nz_out <= nz).  One launch.
+ *     vanerf_field_values: f[n] = rgba[n][0] + mesh_sdf[n], with rgba[n][5] = [alpha, sdf, r, g, b] of a query with raw = 0 and mesh_sdf of
+ *         the mesh query; rgb[n][3] = rgba[n][2..4] unless NULL.  A non-finite sum is stored as it is.  All device pointers.  One launch.
+ *
+ * Marching tetrahedra over f[nz][ny][nx] (device), indexed and welded:
+ *     - a value counts as INSIDE iff f < iso; a non-finite f is read as +FLT_MAX (outside), so no NaN reaches an output;
+ *     - corners of a cell carry the code dx | dy << 1 | dz << 2; the cell is split into the six tetrahedra (0, e_a, e_a + e_b, 7) around its main
+ *       diagonal, one per order (a, b, c) of the axes.  The split is the same in every cell, so neighbours agree on the diagonals of their
+ *       common face and the surface is watertight; a tetrahedron with 1 or 3 corners inside gives one triangle, with 2 gives two;
+ *     - every grid point owns the seven edges towards the direction codes d = 1 ... 7 (+x, +y, +xy, +z, +xz, +yz, +xyz) that stay inside the
+ *       grid.  An edge with exactly one end inside carries one vertex at a + t (b - a), t = (iso - f_a) / (f_b - f_a) in fp32, a the owning
+ *       point (the end with the lower linear index); the result is clamped onto the edge, so a vertex lies on its grid edge exactly.
+ *       colors = rgb_a + t (rgb_b - rgb_a) with the same t;
+ *     - every triangle is wound so that its normal ((v1 - v0) x (v2 - v0)) points from inside to outside, towards growing f;
+ *     - vertices are numbered in the order (brick of 8 x 8 x 8 points, point in the brick, direction code), triangles in the order (brick,
+ *       cell in the brick, tetrahedron), by exclusive scans in a fixed order: no atomics, the same bits every call whatever scratch held.
+ *     vanerf_surface_count: -> counts[2] int64 (DEVICE) = {n_vertices, n_triangles}; the scanned offsets stay in scratch.  Two launches.
+ *     vanerf_surface_emit: with the same f, grid, iso and scratch, and n_verts / n_tris as read from counts: -> verts[n_verts][3],
+ *         colors[n_verts][3] (NULL: none; needs rgb[nz ny nx][3]), tris[n_tris][3] int32.  cap_verts / cap_tris: what the buffers hold; less
+ *         than the counts is an error, and nothing is written past them in any case.  n_verts = n_tris = 0 is a no-op.  One launch.
+ *     scratch: vanerf_surface_scratch(nx, ny, nz) bytes of device memory, 16-byte aligned (0: not a valid grid).  Every byte the calls read of
+ *         it is written by vanerf_surface_count first.
+ * All work goes to `stream`; no allocation, no host synchronisation.                                                                      */
+int vanerf_grid_points(const float origin[3], const float spacing[3], int nx, int ny, int nz, int z0, int nz_out, float* pts, void* stream);
+int vanerf_field_values(const float* rgba, const float* mesh_sdf, int64_t n, float* f, float* rgb, void* stream);
+int64_t vanerf_surface_scratch(int nx, int ny, int nz);
+int vanerf_surface_count(const float* f, int nx, int ny, int nz, float iso, void* scratch, int64_t scratch_bytes, int64_t* counts, void* stream);
+int vanerf_surface_emit(const float* f, const float* rgb, const float origin[3], const float spacing[3], int nx, int ny, int nz, float iso,
+                        const void* scratch, int64_t scratch_bytes, int64_t n_verts, int64_t n_tris, float* verts, float* colors, int32_t* tris,
+                        int64_t cap_verts, int64_t cap_tris, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -143,6 +143,12 @@ _SIGS = {
     "vanerf_image_metrics": (c_int, [_FP, _FP, _FP, _FP, c_int, c_int, c_int, c_double, c_int, c_void_p, c_int64, _FP, c_void_p]),
     "vanerf_mask_at_box_scratch": (c_int64, [c_int, c_int, c_int]),
     "vanerf_mask_at_box": (c_int, [_FP, c_int, c_int, c_int, POINTER(c_float), _FP, _FP, _FP, c_void_p, c_int64, _FP, c_void_p]),
+    "vanerf_grid_points": (c_int, [POINTER(c_float), POINTER(c_float), c_int, c_int, c_int, c_int, c_int, _FP, c_void_p]),
+    "vanerf_field_values": (c_int, [_FP, _FP, c_int64, _FP, _FP, c_void_p]),
+    "vanerf_surface_scratch": (c_int64, [c_int, c_int, c_int]),
+    "vanerf_surface_count": (c_int, [_FP, c_int, c_int, c_int, c_float, c_void_p, c_int64, _FP, c_void_p]),
+    "vanerf_surface_emit": (c_int, [_FP, _FP, POINTER(c_float), POINTER(c_float), c_int, c_int, c_int, c_float, c_void_p, c_int64, c_int64, c_int64,
+                                    _FP, _FP, _FP, c_int64, c_int64, c_void_p]),
 }
 EXPORTS = tuple(_SIGS)
 

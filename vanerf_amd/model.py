@@ -617,6 +617,14 @@ class VANeRF(nn.Module):
             outs.append(ret)
         return outs
 
+    @torch.no_grad()
+    def extract_surface(self, tr_batch, resolution=128, voxel_size=None, iso=0.0, colors=True, **kwargs):
+        """The learned hand surface of one frame as a triangle mesh on the device (vanerf_amd.surface.extract_surface):
+        the zero level set of alpha + mesh_sdf, the field the composite turns into a density.  tr_batch: the batch dict of device tensors the
+        render calls are fed from (im, cam, targets, sp_data, src_foreground_mask, dr_data)."""
+        from . import surface
+        return surface.extract_surface(self, tr_batch, resolution=resolution, voxel_size=voxel_size, iso=iso, colors=colors, **kwargs)
+
     def attach_autograd(self, out, img_in, feat_geo, feat_tex, targets, sp_data, fg_mask):
         """Replaces the differentiable entries of `out` (a batch_render_pifu_nerf result computed with _autograd=True) by tensors that
         carry the HIP values and, in backward, the gradients of vanerf_amd.torch_graph evaluated at the same samples (same points, same
