@@ -753,8 +753,8 @@ def test_full_view_properties(R, sd_full, precision):
     zf = full["z_fine"]
     assert (zf[:, 1:] >= zf[:, :-1]).all()  # sortedness
     assert (full["alpha_fine"] <= 1.0 + 1e-5).all() and (full["alpha_fine"] >= 0).all()
-    # determinism / idempotence: later launches give identical bits (the bf16 kernel was NOT reproducible with two waves per
-    # SIMD -- csrc/query_kernel.hip, VANERF_WAVES_PER_SIMD_B -- so this is checked more than once)
+    # determinism / idempotence: later launches give identical bits (an earlier build of the bf16 kernel at two waves per SIMD,
+    # with registers spilled to scratch, was NOT reproducible -- DESIGN.md section 6 -- so this is checked more than once)
     for _ in range(3):
         again = R.render_pass(w, fdat, frame["cam_tar"], frame["bounds"], 0, 0, 1, 334, 512, 64, 64)
         for k in ("color_fine", "depth_fine", "alpha_fine", "sdf", "color"):

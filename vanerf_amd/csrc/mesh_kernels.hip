@@ -270,31 +270,16 @@ __global__ __launch_bounds__(256) void knn1_kernel(const float4* __restrict__ ve
 //   * inside test: a G x G grid over the mesh's (y,z) extent lists the triangles whose (y,z) bounding box touches each
 //     cell; the +x ray of a point can only cross triangles of its own cell.
 // The structure is built per source frame by vanerf_mesh_accel_build (end of this file).
-#ifndef VANERF_MA_CL
-#define VANERF_MA_CL 4
-#endif
-constexpr int CL = VANERF_MA_CL; // triangles (and vertices) per cluster.  Measured on the benchmark view: 16 -> 6.35 ms, 8 -> 4.80, 4 -> 4.37
-                                 // (box tests are cheap since they are done per wave first; small clusters mean fewer per-triangle tests)
-#ifndef VANERF_MA_BLOCK
-#define VANERF_MA_BLOCK 1024 // one block per CU: 16 waves share the LDS copy of the vertex / box tables (53 KB for the two-hand mesh)
-#endif
-constexpr int MA_BLOCK = VANERF_MA_BLOCK;
+constexpr int CL = 4; // triangles (and vertices) per cluster.  Measured on the benchmark view: 16 -> 6.35 ms, 8 -> 4.80, 4 -> 4.37
+                      // (box tests are cheap since they are done per wave first; small clusters mean fewer per-triangle tests)
+constexpr int MA_BLOCK = 1024; // one block per CU: 16 waves share the LDS copy of the vertex / box tables (53 KB for the two-hand mesh)
 constexpr int MA_MAX_CLUSTERS = 4096;
 constexpr int MA_MAX_VCLUSTERS = 1024;
 // tile searches (below): clusters a wave's candidate list can hold, and the 64-candidate rounds that makes
-#ifndef VANERF_TL_LIST
-#define VANERF_TL_LIST 160 // measured on the benchmark view with the work queue: 64 -> 2.34 ms, 128 -> 2.00, 160 -> 1.93, 192 -> 1.95, 256 -> 2.16
-#endif
-constexpr int TL_LIST = VANERF_TL_LIST;
+constexpr int TL_LIST = 160; // measured on the benchmark view with the work queue: 64 -> 2.34 ms, 128 -> 2.00, 160 -> 1.93, 192 -> 1.95, 256 -> 2.16
 constexpr int TL_IT = TL_LIST * CL / 64;
-#ifndef VANERF_MA_ND
-#define VANERF_MA_ND 2
-#endif
-constexpr int ND_MAX = VANERF_MA_ND; // consecutive depths of a pixel tile a wave takes at once (template parameter ND of the kernel): one tile search, ND per-lane evaluations
-#ifndef VANERF_TL_CAND
-#define VANERF_TL_CAND 40
-#endif
-constexpr int TL_CAND = VANERF_TL_CAND; // triangles (9 floats + original index, padded to 12) a wave's candidate table holds
+constexpr int ND_MAX = 2; // consecutive depths of a pixel tile a wave takes at once (template parameter ND of the kernel): one tile search, ND per-lane evaluations
+constexpr int TL_CAND = 40; // triangles (9 floats + original index, padded to 12) a wave's candidate table holds
 static_assert(TL_LIST * CL % 64 == 0 && 64 % CL == 0 && MA_MAX_CLUSTERS <= 65536, "candidate lists hold 16-bit cluster ids in whole rounds of 64");
 
 // Diagnostic build only (-DVANERF_MESH_PHASES): s_memtime deltas per phase, summed over waves (tools/perf_mesh.py --phases)
@@ -335,12 +320,8 @@ __device__ __forceinline__ float box_dist2(f3 p, const float* b)
     return (dx * dx + dy * dy) + dz * dz;
 }
 
-#ifndef VANERF_MA_ATTR
-#define VANERF_MA_ATTR
-#endif
-
 template <int ND> // 1 or ND_MAX: small launches take one depth per item (twice the items: a launch of a few thousand items is bound by the latency of single items)
-__global__ __launch_bounds__(MA_BLOCK) VANERF_MA_ATTR void mesh_query_accel_kernel(const VanerfMeshAccel A, const float* __restrict__ V,
+__global__ __launch_bounds__(MA_BLOCK) void mesh_query_accel_kernel(const VanerfMeshAccel A, const float* __restrict__ V,
                                                                     const int32_t* __restrict__ F, const float* __restrict__ vert_vis,
                                                                     const float* __restrict__ P, long long n, float* __restrict__ sdf,
                                                                     uint8_t* __restrict__ vis, int32_t* __restrict__ face,
@@ -880,10 +861,7 @@ __global__ __launch_bounds__(MA_BLOCK) VANERF_MA_ATTR void mesh_query_accel_kern
                     K += __builtin_popcountll(m);
                 }
             }
-#ifndef VANERF_TL_KMAX
-#define VANERF_TL_KMAX 100000
-#endif
-            if (K > VANERF_TL_KMAX) return false; // (a tile on the surface: every triangle within 2 rho is a candidate; the per-lane search prunes those by each lane's own bound)
+            // (K <= TL_LIST * CL.  A tile on the surface: every triangle within 2 rho is a candidate; the per-lane search prunes those by each lane's own bound)
 #ifdef VANERF_MESH_PHASES
             if (lane == 0 && K > TL_CAND) ph[15] += 1; // more candidates than the table holds: evaluated in batches
             if (lane == 0) ph[11] += K; // per-lane evaluations of the tile search

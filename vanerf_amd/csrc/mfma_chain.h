@@ -59,9 +59,6 @@ template <int NB> __device__ __forceinline__ void mfma_step(f32x16 (&acc)[NB], c
 {
 #pragma unroll
     for (int ob = 0; ob < NB; ++ob) acc[ob] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.v[ob], b, acc[ob], 0, 0, 0);
-#ifdef VANERF_PIN_KSTEPS // experiment knob: forbid scheduling across k-steps
-    __builtin_amdgcn_sched_barrier(0);
-#endif
 }
 
 // The register ring of one layer's A fragments.  ring_start() issues the first D loads; it is called well before the layer

@@ -15,7 +15,7 @@
 //
 // Built with -ffp-contract=off: the integer-valued outputs (1-NN index) depend on fp32 compare
 // results and must match oracle/mesh_oracle.c bit for bit; fused multiply-adds are spelled fmaf().
-#include <cstdlib>
+#include <algorithm>
 #include <utility>
 
 #include "common.h"
@@ -27,26 +27,18 @@ using namespace vanerf_chain;
 
 namespace {
 
-// Waves per SIMD of the split-bf16 kernel: TWO (round 3), as one 8-wave block per CU that owns the CU's LDS.  One in-order wave per SIMD
-// issues at most one instruction every ~4 cycles, and a full 32-sample group is ~9 700 instructions around 990 MFMAs: the wave was
-// issue-bound at ~54 k cycles per group with NO fragment traffic at all (timing experiment VANERF_EXP_FRAG_SRC=2), against 31.7 k cycles of
-// matrix-pipe time.  A second wave fills the issue slots; it needs the kernel in 256 registers WITHOUT scratch (build.py fails a build
-// that spills): key points in LDS instead of 63 VGPRs, gathers issued where they are used, fragment rings one k-step deep and kept per
-// output block, LDS addresses formed from three window bases (see LAddr).  Round 1 had tried two waves with the 476-register kernel cut
-// to 256 by the compiler (155 VGPRs in scratch): results were not reproducible run to run; the scratch-free
-// build is bit-identical to the one-wave build and reproducible (tools/check_mode1_determinism.py).  VANERF_WAVES_PER_SIMD_B=1
-// VANERF_WPB_B=4 builds the round-2 configuration (one 4-wave block per CU, 512 registers per wave).
-#ifndef VANERF_WAVES_PER_SIMD_B
-#define VANERF_WAVES_PER_SIMD_B 2
-#endif
-#ifndef VANERF_WAVES_PER_SIMD
-#define VANERF_WAVES_PER_SIMD 2
-#endif
-#ifndef VANERF_WPB_B
-#define VANERF_WPB_B (VANERF_WAVES_PER_SIMD_B == 2 ? 8 : 4)
-#endif
-// waves per block: the fp32 kernel runs two 4-wave blocks per CU, the split-bf16 kernel ONE block per CU (it owns the CU's LDS)
-template <int MODE> constexpr int WPB = MODE == 1 ? VANERF_WPB_B : 4;
+// Waves per SIMD of the split-bf16 kernel: TWO, as one 8-wave block per CU that owns the CU's LDS.  One in-order wave per SIMD
+// issues at most one instruction every ~4 cycles, and a full 32-sample group is ~9 700 instructions around 990 MFMAs: alone, the wave was
+// issue-bound at ~54 k cycles per group with NO fragment traffic at all, against 31.7 k cycles of matrix-pipe time ("Round 3:
+// what the kernel is now").  A second wave fills the issue slots; it needs the kernel in 256 registers WITHOUT scratch (build.py fails a
+// build that spills): key points in LDS instead of 63 VGPRs, gathers issued where they are used, fragment rings kept per output block and
+// at most two blocks deep, LDS addresses formed from three window bases (see LAddr).  Cut to 256 registers by the compiler instead, the
+// kernel put 155 VGPRs in scratch and its results were not reproducible run to run; this build is reproducible
+// (tools/check_mode1_determinism.py).
+constexpr int WAVES_PER_SIMD = 2;       // query_kernel<0> and query_kernel<1>
+constexpr int WAVES_PER_SIMD_SPILL = 1; // the spill build takes the whole register file: at 256 registers it goes to scratch
+// waves per block: the fp32 kernel runs two 4-wave blocks per CU, the split-bf16 kernel ONE 8-wave block per CU (it owns the CU's LDS)
+template <int MODE> constexpr int WPB = MODE == 1 ? 8 : 4;
 
 // Diagnostic build only (-DVANERF_STAMPS): per-phase s_memtime deltas summed per wave into QueryParams::stamps.
 // No stamp executes in the product build; stamp values never reach an output element.
@@ -95,35 +87,6 @@ struct QueryParams {
 // k-pairs of the fp32 ordering, so the accumulator -> operand chaining of layer_spec.h is unchanged.  Measured against the fp32
 // oracle the dropped W_lo X_lo term and the 16-bit operands cost 1.2e-5 absolute on the outputs (the fp32-MFMA path: 9e-6).
 // ---------------------------------------------------------------------------------------------
-// ring depths (steps in flight) for layers with 4/3, 1 and 2 output blocks.  With the pinned software pipeline of run_layer_b, measured in
-// one session: (2,4,2) 8.16-8.23 ms, (2,3,2) 8.22, (2,2,2) 8.24, (1,4,2) 8.25, (3,6,3) 8.32, (1,2,1) 8.33, (4,8,4) +4 %, (5,8,4) +8 %:
-// two k-steps ahead cover the L2 latency, deeper rings only add loads in flight
-// experiment knobs: bit L set = layer L runs with one product (W_hi X_hi) / two products (W_hi X_hi + W_lo X_hi: activations rounded to bf16)
-#ifndef VANERF_P1_MASK
-#define VANERF_P1_MASK 0
-#endif
-#ifndef VANERF_P2_MASK
-#define VANERF_P2_MASK 0
-#endif
-#ifndef VANERF_CHUNKS
-#define VANERF_CHUNKS 4
-#endif
-// ring depth in BLOCK fragments (one (hi, lo) pair = 8 registers, 2 KB of stream) for layers with 4, 3, 2 and 1 output blocks.
-// One wave per SIMD, fragments from L2: two k-steps ahead (4 for the one-block layers) cover the latency (measured in steps, one session:
-// (2,4,2) 8.16-8.23 ms, (2,2,2) 8.24, (1,4,2) 8.25, (3,6,3) 8.32, (4,8,4) +4 %).  Two waves per SIMD, fragments from the LDS ring: two blocks
-// ahead (one for the one-block layers) -- 4 / 3 / 2 / 2 blocks measured the same 5.42 ms with 15 more registers, 6 / 4 spill.
-#ifndef VANERF_DB4
-#define VANERF_DB4 (VANERF_WAVES_PER_SIMD_B == 2 ? 2 : 8)
-#endif
-#ifndef VANERF_DB3
-#define VANERF_DB3 (VANERF_WAVES_PER_SIMD_B == 2 ? 2 : 6)
-#endif
-#ifndef VANERF_DB2
-#define VANERF_DB2 (VANERF_WAVES_PER_SIMD_B == 2 ? 2 : 4)
-#endif
-#ifndef VANERF_DB1
-#define VANERF_DB1 (VANERF_WAVES_PER_SIMD_B == 2 ? 1 : 4)
-#endif
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 
@@ -131,30 +94,19 @@ struct FragB { u32x4 hi, lo; }; // A fragments (hi and lo parts) of one 32-row o
 
 // Fragments of the LAST layers of the stream stay resident in LDS for the whole launch (split-bf16 kernel: one block per CU, persistent):
 // every group needs them -- the all-invalid groups need nothing else -- and the CU's vector-memory path (L1: 64 B per clock) is what the
-// fragment stream loads most (72 % of its cycles, profiles/r02_a_*): ds_read_b128 has four times that width and a fifth of the latency.
-// Layers VANERF_LDS_FIRST .. NUM_LAYERS-1 are copied once per block: head1, head2, ibr_compress and the four TexVisFusion layers = 156 KB.
-// Two-wave build: the layers in front of the resident ones are SHARED through an LDS ring (below), so only ibr_compress and the four
-// TexVisFusion layers (126 KB: what the all-invalid groups need) stay resident and 32 KB go to the ring.
-#ifndef VANERF_RING
-#define VANERF_RING (VANERF_WAVES_PER_SIMD_B == 2 ? 1 : 0)
-#endif
-#ifndef VANERF_LDS_FIRST
-#define VANERF_LDS_FIRST (VANERF_RING ? 15 /* L_IBR */ : 13 /* L_HEAD1 */)
-#endif
-constexpr int LDS_FIRST = VANERF_LDS_FIRST;
+// fragment stream loads most (profiles/r02_a_*): ds_read_b128 has four times that width and a fifth of the latency.
+// Layers LDS_FIRST .. NUM_LAYERS-1 are copied once per block: ibr_compress and the four TexVisFusion layers (126 KB: what the all-invalid
+// groups need).  The layers in front of them are SHARED by the block's waves through an LDS ring of 32 KB (below).
+constexpr int LDS_FIRST = L_IBR;
 // (HOIST: the hoisted stream of layer_spec.h -- three layers are shorter, so every offset, the ring's phases and the resident size differ)
 template <bool HOIST> constexpr unsigned RES_BASE_DW = layer_offset_b(LDS_FIRST, HOIST);
 template <bool HOIST> constexpr unsigned RES_DW = layer_offset_b(NUM_LAYERS, HOIST) - layer_offset_b(LDS_FIRST, HOIST);
-// Two waves per SIMD (VANERF_WAVES_PER_SIMD_B == 2: 8-wave blocks, 256 registers per wave): nothing long-lived may sit in registers -- the
-// lane half's key points live in LDS behind the resident fragments (one ds_read_b128 per key point and group), gathers are issued right
-// before their use (the partner wave hides their latency), rings are one step deep.
-constexpr bool W2 = VANERF_WAVES_PER_SIMD_B == 2;
+// (The key points live in LDS because 256 registers per wave hold nothing long-lived: one ds_read_b128 per key point and group.)
 // LDS map of the split-bf16 kernel (all of it in the dynamic region, which then starts at LDS address 0: no static __shared__ in this kernel):
-//   [0, 672)      the 42 key points as float4 (two-wave build)            [672, 768)  control words: s_base[2], s_valid[2][waves per block]
-//   [1024, 1024 + 32 KB)     fragment ring (two-wave build)               [LDS_RES, LDS_RES + RES_DW * 4)  resident fragments
-constexpr bool RING = VANERF_RING != 0;
-constexpr unsigned RING_PHASE_PIECES = 16u, RING_BYTES = RING ? 2u * RING_PHASE_PIECES * 1024u : 0u; // two halves of one 16 KB phase each
-constexpr unsigned LDS_KPT = 0u, LDS_CTRL = 2u * PE_KPT_PER_HALF * 16u, LDS_LAT0 = 768u, LDS_RING = 1024u, LDS_RES = RING ? LDS_RING + RING_BYTES : 1024u;
+//   [0, 672)      the 42 key points as float4                              [672, 768)  control words: s_base[2], s_valid[2][waves per block]
+//   [1024, 1024 + 32 KB)     fragment ring                                 [LDS_RES, LDS_RES + RES_DW * 4)  resident fragments
+constexpr unsigned RING_PHASE_PIECES = 16u, RING_BYTES = 2u * RING_PHASE_PIECES * 1024u; // two halves of one 16 KB phase each
+constexpr unsigned LDS_KPT = 0u, LDS_CTRL = 2u * PE_KPT_PER_HALF * 16u, LDS_LAT0 = 768u, LDS_RING = 1024u, LDS_RES = LDS_RING + RING_BYTES;
 // [768, 896): ibr_compress of an all-zero pooled latent (its bias through the same MFMA chain), [lane half][16 registers]: what every sample of an
 // all-invalid group gets from that layer -- computed once per block, read by the short path instead of 27 MFMAs per group
 template <bool HOIST> constexpr unsigned DYN_LDS_BYTES = LDS_RES + RES_DW<HOIST> * 4u;
@@ -166,11 +118,11 @@ template <bool HOIST> constexpr unsigned RING_PIECES = RES_BASE_DW<HOIST> / 256u
 // hand behind the last streamed layer (ring_close), which is what issues phase 0 of the next round.
 template <bool HOIST> constexpr unsigned RING_STREAM_PHASES = (RING_PIECES<HOIST> + RING_PHASE_PIECES - 1u) / RING_PHASE_PIECES;
 template <bool HOIST> constexpr unsigned RING_PHASES = (RING_STREAM_PHASES<HOIST> + 1u) / 2u * 2u;
-static_assert(!RING || VANERF_WPB_B == 8, "the ring's DMA schedule deals 2 pieces of a phase to each of 8 waves");
-static_assert(!RING || RING_PHASES<false> * RING_PHASE_PIECES * 256u <= layer_offset_b(NUM_LAYERS), "the last phase's DMA must stay inside the stream");
-static_assert(!RING || RING_PHASES<true> * RING_PHASE_PIECES * 256u <= layer_offset_b(NUM_LAYERS, true), "the last phase's DMA must stay inside the hoisted stream");
-static_assert(LDS_CTRL + 8u + 2u * 4u * VANERF_WPB_B <= LDS_LAT0 && LDS_LAT0 + 128u <= LDS_RING, "control words / constant latent overlap their neighbours");
-static_assert(DYN_LDS_BYTES<false> <= 160u * 1024u && DYN_LDS_BYTES<true> <= DYN_LDS_BYTES<false>, "key points + control words + resident fragments must fit the CU's 160 KB");
+static_assert(WPB<1> == 8, "the ring's DMA schedule deals 2 pieces of a phase to each of 8 waves");
+static_assert(RING_PHASES<false> * RING_PHASE_PIECES * 256u <= layer_offset_b(NUM_LAYERS), "the last phase's DMA must stay inside the stream");
+static_assert(RING_PHASES<true> * RING_PHASE_PIECES * 256u <= layer_offset_b(NUM_LAYERS, true), "the last phase's DMA must stay inside the hoisted stream");
+static_assert(LDS_CTRL + 8u + 2u * 4u * WPB<1> <= LDS_LAT0 && LDS_LAT0 + 128u <= LDS_RING, "control words / constant latent overlap their neighbours");
+static_assert(DYN_LDS_BYTES<false> <= 160u * 1024u && DYN_LDS_BYTES<true> <= DYN_LDS_BYTES<false>, "key points + control words + ring + resident fragments must fit the CU's 160 KB");
 extern __shared__ __attribute__((aligned(16))) u32x4 s_dyn[];
 typedef __attribute__((address_space(3))) u32x4 lds_u32x4_t;
 typedef __attribute__((address_space(3))) unsigned lds_u32_t;
@@ -179,7 +131,7 @@ typedef __attribute__((address_space(3))) unsigned lds_u32_t;
 // re-made opaque at the top of every round (LAddr), and every access names its window and its offset inside it.
 struct LAddr {
     unsigned w[3];
-    unsigned dma_lds, dma_src;  // (ring build) the wave's LDS-DMA destination / stream offset inside a phase, wave-uniform
+    unsigned dma_lds, dma_src;  // the wave's LDS-DMA destination / stream offset inside a phase, wave-uniform
 };
 __device__ __forceinline__ LAddr make_laddr(int lane, unsigned wv_uniform = 0u)
 {
@@ -196,10 +148,12 @@ template <unsigned BYTE> __device__ __forceinline__ u32x4 lds_frag(const LAddr& 
     return *reinterpret_cast<const lds_u32x4_t*>((size_t)(a.w[BYTE >> 16] + (BYTE & 0xffffu)));
 }
 __device__ __forceinline__ lds_u32_t* lds_ctrl() { return reinterpret_cast<lds_u32_t*>((size_t)LDS_CTRL); }
-template <int NB> struct RingDepthB { static constexpr int value = NB == 1 ? VANERF_DB1 : NB == 2 ? VANERF_DB2 : NB == 3 ? VANERF_DB3 : VANERF_DB4; };
+// ring depth in BLOCK fragments (one (hi, lo) pair = 8 registers, 2 KB of stream): two blocks ahead, one for the one-block layers -- 4 / 3 / 2 / 2
+// blocks (for layers with 4 / 3 / 2 / 1 output blocks) measured the same 5.42 ms with 15 more registers, 6 / 4 spill
+template <int NB> struct RingDepthB { static constexpr int value = NB == 1 ? 1 : 2; };
 template <int NB> struct RingB { FragB b[RingDepthB<NB>::value]; };
 
-// ---- the fragment ring (two-wave build) ---------------------------------------------------------------------------------------------
+// ---- the fragment ring ---------------------------------------------------------------------------------------------------------------
 // The eight waves of the block walk the same fragment stream one round at a time.  Fetched by every wave for itself, the stream is 8 x 516 KB
 // per round through the CU's 64 B / clock vector-memory path: 65 % busy, the largest share of what the waves wait for (profiles/r03_a_*).
 // Instead phase P (16 KB) is brought into one half of a 32 KB LDS ring ONCE -- every wave issues two `buffer_load_dwordx4 ... lds` (LDS-DMA:
@@ -210,19 +164,10 @@ template <int NB> struct RingB { FragB b[RingDepthB<NB>::value]; };
 //     issue the DMA of phase P + 1     into the half phase P - 1 occupied
 // The last phase issues phase 0 of the NEXT full round, the top-of-round barrier (every wave has passed a vmcnt(0) before its stores) stands in
 // for phase_begin<0>, and rounds that take the all-invalid path touch neither half: half 0 holds phase 0 whenever a round starts.
-// vmcnt(0) is exact here: in the two-wave build gathers are issued where they are consumed, nothing else is in flight inside the layer stack.
+// vmcnt(0) is exact here: gathers are issued where they are consumed, nothing else is in flight inside the layer stack.
 template <unsigned P> __device__ __forceinline__ void ring_dma(WRsrc rs, const LAddr& la) // this wave's two pieces of phase P -> half P % 2
 {
     constexpr unsigned lds_off = (P % 2u) * RING_PHASE_PIECES * 1024u, src_off = P * RING_PHASE_PIECES * 1024u;
-#if defined(VANERF_EXP_RING) && (VANERF_EXP_RING == 5 || VANERF_EXP_RING == 7)
-    unsigned soff5;
-    asm volatile("s_add_u32 m0, %1, %3\n\ts_add_u32 %0, %2, %4\n\ts_nop 0\n\t"
-                 "buffer_load_dwordx4 %5, %6, %0 offen lds\n\tbuffer_load_dwordx4 %5, %6, %0 offen offset:1024 lds"
-                 : "=&s"(soff5)
-                 : "s"(la.dma_lds), "s"(la.dma_src), "i"(lds_off), "i"(src_off), "v"(la.w[0]), "s"(rs)
-                 : "memory");
-    return;
-#endif
     unsigned keep, soff;
     // M0 = LDS destination (written and used in ONE statement: hipcc owns M0 everywhere else); one wait state between its write and the DMA
     asm volatile("s_mov_b32 %0, m0\n\ts_add_u32 m0, %2, %4\n\ts_add_u32 %1, %3, %5\n\ts_nop 0\n\t"
@@ -234,64 +179,32 @@ template <unsigned P> __device__ __forceinline__ void ring_dma(WRsrc rs, const L
 template <bool HOIST, unsigned P> __device__ __forceinline__ void phase_begin(WRsrc rs, const LAddr& la)
 {
     constexpr unsigned RING_PHASES = ::RING_PHASES<HOIST>;
-#if defined(VANERF_EXP_RING) && VANERF_EXP_RING == 1 // timing experiments (results may be wrong): 1 no lgkmcnt wait, 2 no barrier, 3 no DMA, 4 nothing
-    if constexpr (P > 0) asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
-    ring_dma<(P + 1u) % RING_PHASES>(rs, la);
-#elif defined(VANERF_EXP_RING) && VANERF_EXP_RING == 2
-    if constexpr (P > 0) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    ring_dma<(P + 1u) % RING_PHASES>(rs, la);
-#elif defined(VANERF_EXP_RING) && VANERF_EXP_RING == 3
-    if constexpr (P > 0) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-#elif defined(VANERF_EXP_RING) && VANERF_EXP_RING == 4
-#elif defined(VANERF_EXP_RING) && VANERF_EXP_RING == 7
-    if constexpr (P > 0) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    ring_dma<(P + 1u) % RING_PHASES>(rs, la);
-#else
     if constexpr (P > 0) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
     ring_dma<(P + 1u) % RING_PHASES>(rs, la);
-#endif
 }
 
 // behind the last streamed layer of a full round: begins the padding phase of a stream with an odd number of phases (see RING_PHASES)
 template <bool HOIST> __device__ __forceinline__ void ring_close(WRsrc rs, const LAddr& la)
 {
-    if constexpr (RING && RING_STREAM_PHASES<HOIST> % 2u == 1u) phase_begin<HOIST, RING_PHASES<HOIST> - 1u>(rs, la);
+    if constexpr (RING_STREAM_PHASES<HOIST> % 2u == 1u) phase_begin<HOIST, RING_PHASES<HOIST> - 1u>(rs, la);
 }
 
 // DW: dword offset of the block's hi part in the stream (the lo part follows 1 KB later); the lane's 16 bytes sit at lane * 16
 template <bool HOIST, bool RES, unsigned DW> __device__ __forceinline__ FragB wload_blk(WRsrc rs, const LAddr& la)
 {
     constexpr unsigned RING_PHASES = ::RING_PHASES<HOIST>, RES_BASE_DW = ::RES_BASE_DW<HOIST>;
-    [[maybe_unused]] constexpr unsigned RES_DW = ::RES_DW<HOIST>;
+    static_assert(RES == (DW >= RES_BASE_DW), "a layer's fragments are either resident or streamed through the ring: nothing is fetched per wave");
     FragB r;
-    if constexpr (RING && !RES) { // streamed layer, through the ring
+    if constexpr (RES) { // resident layer
+        r.hi = lds_frag<LDS_RES + (DW - RES_BASE_DW) * 4u>(la);
+        r.lo = lds_frag<LDS_RES + (DW - RES_BASE_DW + 256u) * 4u>(la);
+    } else { // streamed layer, through the ring
         constexpr unsigned q = DW / 256u; // piece index of the hi part
         static_assert(q % 2u == 0 && q + 1u < RING_PHASES * RING_PHASE_PIECES, "block fragments are two consecutive pieces inside the streamed part");
         if constexpr (q % RING_PHASE_PIECES == 0) phase_begin<HOIST, q / RING_PHASE_PIECES>(rs, la);
         r.hi = lds_frag<LDS_RING + (q % (2u * RING_PHASE_PIECES)) * 1024u>(la);
         r.lo = lds_frag<LDS_RING + ((q + 1u) % (2u * RING_PHASE_PIECES)) * 1024u>(la);
-        return r;
     }
-    if constexpr (RES) { // resident layer: the same fragments from LDS
-        r.hi = lds_frag<LDS_RES + (DW - RES_BASE_DW) * 4u>(la);
-        r.lo = lds_frag<LDS_RES + (DW - RES_BASE_DW + 256u) * 4u>(la);
-        return r;
-    }
-#if defined(VANERF_EXP_FRAG_SRC) && VANERF_EXP_FRAG_SRC == 1 // timing experiment, wrong results: every fragment from LDS (wrapped into the resident region)
-    r.hi = lds_frag<LDS_RES + (DW % RES_DW) * 4u>(la);
-    r.lo = lds_frag<LDS_RES + ((DW + 256u) % RES_DW) * 4u>(la);
-    return r;
-#elif defined(VANERF_EXP_FRAG_SRC) && VANERF_EXP_FRAG_SRC == 2 // timing experiment, wrong results: no fragment traffic at all (stale registers)
-    {
-        const unsigned vb = la.w[0];
-        u32x4 a = {vb, vb + 1u, vb + 2u, vb + 3u}, b = {vb + 4u, vb + 5u, vb + 6u, vb + 7u};
-        asm volatile("" : "+v"(a), "+v"(b));
-        r.hi = a; r.lo = b;
-        return r;
-    }
-#endif
-    r.hi = __builtin_amdgcn_raw_buffer_load_b128(rs, la.w[0], DW * 4u, 0);
-    r.lo = __builtin_amdgcn_raw_buffer_load_b128(rs, la.w[0], (DW + 256u) * 4u, 0);
     return r;
 }
 
@@ -318,7 +231,7 @@ struct NoPre { template <class C> __device__ __forceinline__ void operator()(C) 
 
 // pre(integral_constant<int, s>) runs before the operands of bf16 step s are gathered (lazy producers, e.g. the positional encoding).
 //
-// Software pipeline, written out and pinned.  One wave per SIMD issues in order: a bf16 32x32x16 MFMA costs the wave ~16 issue cycles
+// Software pipeline, written out and pinned.  A wave issues in order: a bf16 32x32x16 MFMA costs the wave ~16 issue cycles
 // and then runs 34 cycles beside whatever the wave issues next, so up to ~4 VALU instructions per MFMA are free -- IF they stand
 // between the MFMAs (tools/probe_bf16_valu.hip).  Left to itself the machine scheduler emits the 3*NB MFMAs of a k-step back to
 // back (the wave sits in MFMA issue) and then the operand split of the next step (the matrix pipe idles), and it sinks every ring
@@ -326,12 +239,12 @@ struct NoPre { template <class C> __device__ __forceinline__ void operator()(C) 
 // So: step s's MFMAs are cut into four chunks, after each chunk comes one pair-split of step s+1's operands (5 VALU), the re-load of
 // the consumed ring slot is issued before the first chunk, and a sched_barrier(0) after every chunk keeps that order.
 // (sched_group_barrier could request the same interleave, but its solver did not finish on this 10 k-instruction block in 15 min.)
-template <bool HOIST, int NB, int T, bool RES, unsigned SBASE_DW, int PRODS = 3, class Op, class Pre = NoPre>
+template <bool HOIST, int NB, int T, bool RES, unsigned SBASE_DW, class Op, class Pre = NoPre>
 __device__ __forceinline__ void run_layer_b(f32x16 (&acc)[NB], RingB<NB>& ring, WRsrc rs, const LAddr& la, Op&& operand,
                                             Pre&& pre = Pre{})
 {
     constexpr int D = RingDepthB<NB>::value, S = (T + 7) / 8;
-    constexpr int NCH = VANERF_CHUNKS; // chunks a step's MFMAs are cut into (4 / NCH operand pairs of the next step are split after each)
+    constexpr int NCH = 4; // chunks a step's MFMAs are cut into (one of the four operand pairs of the next step is split after each)
     // hi = bf16(x) (round to nearest even), lo = bf16(x - hi) for operand pair i of step s: 6 VALU -- v_cvt_pk, v_lshlrev, v_and, two
     // v_sub_f32, v_cvt_pk (no packed f32 math: a v_pk_add_f32 beside MFMAs costs more than the two scalar ops it replaces, and the file
     // is built with -fno-slp-vectorize for the same reason).  The empty asm keeps the packed hi opaque: without it the compiler
@@ -344,7 +257,7 @@ __device__ __forceinline__ void run_layer_b(f32x16 (&acc)[NB], RingB<NB>& ring, 
         unsigned hpk = pack_bf16(x0, x1);
         asm("" : "+v"(hpk));
         bh[i] = hpk;
-        if constexpr (PRODS == 3) bl[i] = pack_bf16(x0 - __uint_as_float(hpk << 16), x1 - __uint_as_float(hpk & 0xffff0000u));
+        bl[i] = pack_bf16(x0 - __uint_as_float(hpk << 16), x1 - __uint_as_float(hpk & 0xffff0000u));
     };
     u32x4 bh, bl;
     pre(std::integral_constant<int, 0>{});
@@ -366,15 +279,13 @@ __device__ __forceinline__ void run_layer_b(f32x16 (&acc)[NB], RingB<NB>& ring, 
                         a[ob] = ring.b[idx % D];
                         if constexpr (idx + D < S * NB) ring.b[idx % D] = wload_blk<HOIST, RES, SBASE_DW + (idx + D) * 512u>(rs, la);
                     }
-                    if constexpr (pr == 0 || (pr == 1 && PRODS == 3) || (pr == 2 && PRODS >= 2)) {
-                        const bf16x8 wh = __builtin_bit_cast(bf16x8, a[ob].hi), wl = __builtin_bit_cast(bf16x8, a[ob].lo);
-                        acc[ob] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pr == 2 ? wl : wh, pr == 1 ? xl : xh, acc[ob], 0, 0, 0);
-                    }
+                    const bf16x8 wh = __builtin_bit_cast(bf16x8, a[ob].hi), wl = __builtin_bit_cast(bf16x8, a[ob].lo);
+                    acc[ob] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pr == 2 ? wl : wh, pr == 1 ? xl : xh, acc[ob], 0, 0, 0);
                 }
             });
             if constexpr (s + 1 < S) {
                 if constexpr (c == 0) pre(std::integral_constant<int, s + 1>{});
-                static_for<4 / NCH>([&](auto pc) { split_pair(std::integral_constant<int, s + 1>{}, std::integral_constant<int, c * (4 / NCH) + decltype(pc)::value>{}, nh, nl); });
+                split_pair(std::integral_constant<int, s + 1>{}, cc, nh, nl);
             }
             __builtin_amdgcn_sched_barrier(0);
         });
@@ -407,9 +318,6 @@ template <int K> __device__ __forceinline__ void spill_aux(const LLane& la, floa
 {
     if (la.on) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), la.aux, la.voff, (unsigned)(2 * K) * la.row4, 0);
 }
-#ifndef VANERF_WAVES_PER_SIMD_SPILL
-#define VANERF_WAVES_PER_SIMD_SPILL 1
-#endif
 template <int MODE> struct LaneSel { using type = LLane; };
 template <> struct LaneSel<1> { using type = LAddr; };
 __device__ __forceinline__ unsigned lane_of(const LLane& la) { return (unsigned)la.lane; }
@@ -428,7 +336,7 @@ __device__ __forceinline__ void run_layer_m(f32x16 (&acc)[NB], typename RingSel<
             spill_x<L, decltype(tc)::value>(la, b); // (spill mode only)
             return b;
         });
-    else run_layer_b<HOIST, NB, T, (L >= LDS_FIRST), layer_offset_b(L, HOIST), (((VANERF_P1_MASK >> L) & 1) ? 1 : ((VANERF_P2_MASK >> L) & 1) ? 2 : 3)>(acc, ring, rs, la, static_cast<Op&&>(operand));
+    else run_layer_b<HOIST, NB, T, (L >= LDS_FIRST), layer_offset_b(L, HOIST)>(acc, ring, rs, la, static_cast<Op&&>(operand));
 }
 
 // lane id from v_mbcnt, not from a register that would have to stay live (or be spilled) across the whole sample loop
@@ -440,7 +348,7 @@ __device__ __forceinline__ int lane_id_fresh()
 }
 
 
-// Barriers of the block's four waves.  block_barrier_lds: LDS writes before it are visible after it (s_waitcnt lgkmcnt(0) + s_barrier; NOT
+// Barriers of the block's waves.block_barrier_lds: LDS writes before it are visible after it (s_waitcnt lgkmcnt(0) + s_barrier; NOT
 // __syncthreads(), whose workgroup-scope release also drains vmcnt -- the fragment prefetch and the stores of the previous group are in flight here).
 __device__ __forceinline__ void block_barrier_lds() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 // (More barriers inside a round were measured and lost: four rendezvous points in the layer stack cost 3.4 % -- 6.62 -> 6.84 ms.)
@@ -671,7 +579,7 @@ template <int NB> __device__ __forceinline__ void load_acc(const float* __restri
 }
 
 template <int MODE, bool SPILL = false, bool HOIST = false>
-__global__ __launch_bounds__(64 * WPB<MODE>, MODE == 1 ? VANERF_WAVES_PER_SIMD_B : (SPILL ? VANERF_WAVES_PER_SIMD_SPILL : VANERF_WAVES_PER_SIMD)) void query_kernel(const QueryParams P)
+__global__ __launch_bounds__(64 * WPB<MODE>, SPILL ? WAVES_PER_SIMD_SPILL : WAVES_PER_SIMD) void query_kernel(const QueryParams P)
 {
     static_assert(!SPILL || MODE == 0, "the training spill runs on the fp32 kernel");
     static_assert(!HOIST || MODE == 1, "only the split-bf16 kernel has a hoisted variant");
@@ -680,16 +588,11 @@ __global__ __launch_bounds__(64 * WPB<MODE>, MODE == 1 ? VANERF_WAVES_PER_SIMD_B
     constexpr int WAVES_PER_BLOCK = WPB<MODE>, BLOCK = 64 * WAVES_PER_BLOCK;
 
     const int lane_k = threadIdx.x & 63;
-    [[maybe_unused]] const int lane = lane_k, j = lane & 31, h = lane >> 5; // (shadowed inside the sample loop)
+    [[maybe_unused]] const int lane = lane_k, j = lane & 31; // (shadowed inside the sample loop)
     [[maybe_unused]] const long long wave = (long long)blockIdx.x * WAVES_PER_BLOCK + (threadIdx.x >> 6); // STAMPS builds
     const long long ngroups = (P.n + 31) / 32;
     const VanerfFrame& F = P.f;
-#ifdef VANERF_EXP_SHARE_BOUND // timing experiment, wrong results: only wave 0 of a block fetches fragments (zero-record descriptor: the others' loads return 0 without traffic)
-    const unsigned wbytes_eff = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) == 0 ? P.wbytes : 0u;
-#else
-    const unsigned wbytes_eff = P.wbytes;
-#endif
-    const WRsrc W = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(P.w), 0, wbytes_eff, 0x00020000); // kernarg-derived: wave-uniform
+    const WRsrc W = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(P.w), 0, P.wbytes, 0x00020000); // kernarg-derived: wave-uniform
     [[maybe_unused]] WRsrc xs_rs = W, aux_rs = W; // spill mode: the two spills as buffers of their exact sizes (the host checks they stay below 4 GB)
     if constexpr (SPILL) {
         xs_rs = __builtin_amdgcn_make_buffer_rsrc(P.xs, 0, (unsigned)(X_ROWS * 4ll * P.npad), 0x00020000);
@@ -702,19 +605,12 @@ __global__ __launch_bounds__(64 * WPB<MODE>, MODE == 1 ? VANERF_WAVES_PER_SIMD_B
     asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(rt0)::"memory");
     asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_prev)::"memory");
 #endif
-    // split-bf16 kernel (one wave per SIMD, 512 registers): the lane half's 21 key points stay in registers for the whole launch
-    // (63 VGPRs) -- per-group scalar loads of them exposed their latency 21 times per group with no second wave to hide it
-    [[maybe_unused]] float kpx[PE_KPT_PER_HALF], kpy[PE_KPT_PER_HALF], kpz[PE_KPT_PER_HALF];
-    if constexpr (MODE == 1 && W2) {
+    if constexpr (MODE == 1) { // split-bf16 kernel: the key points into LDS, once (the fp32 kernel reads them through the scalar cache)
         if (threadIdx.x < 2 * PE_KPT_PER_HALF) s_dyn[LDS_KPT / 16 + threadIdx.x] = reinterpret_cast<const u32x4*>(F.kpt_cam)[threadIdx.x];
-    } else if constexpr (MODE == 1) {
-        const float4* __restrict__ kpl = reinterpret_cast<const float4*>(F.kpt_cam) + (h ? PE_KPT_PER_HALF : 0);
-#pragma unroll
-        for (int i = 0; i < PE_KPT_PER_HALF; ++i) { const float4 k = kpl[i]; kpx[i] = k.x; kpy[i] = k.y; kpz[i] = k.z; }
     }
     unsigned short_groups = 0;
     // The six per-sample inputs of a group are fetched one group ahead (its index is known from the early claim): their HBM latency
-    // is otherwise the first thing a group waits for, and a single wave per SIMD (bf16 kernel) has nobody to hide it.
+    // is otherwise the first thing a group waits for.
     struct SampleIn { float px, py, pz, sdf; int knn; unsigned char vis; };
     auto fetch = [&](unsigned grp, int j) {
         const long long sr = (long long)grp * 32 + j;
@@ -725,10 +621,10 @@ __global__ __launch_bounds__(64 * WPB<MODE>, MODE == 1 ? VANERF_WAVES_PER_SIMD_B
         in.sdf = P.qsdf[sc]; in.knn = P.knn_in[sc]; in.vis = P.qvis[sc];
         return in;
     };
-    // Work distribution.  A block claims FOUR consecutive 32-sample groups per round from a device-scope counter (wave w takes group
-    // base + w) and its waves meet at one barrier per round: they walk the weight stream together, so three of the four fetches of every
-    // fragment hit the CU's L1 instead of L2 (launch 7.6 -> 6.8 ms; with per-wave claims the waves drift apart and every wave streams the
-    // 660 KB from L2 on its own).  The claim for round r + 2 is issued at the start of round r (thread 0) and published through LDS at the
+    // Work distribution.  A block claims one 32-sample group per wave and round from a device-scope counter (wave w takes group
+    // base + w) and its waves meet at one barrier per round: they walk the weight stream together -- in the fp32 kernel three of the four
+    // fetches of every fragment hit the CU's L1 instead of L2 (launch 7.6 -> 6.8 ms; with per-wave claims the waves drift apart and every wave
+    // streams the 660 KB from L2 on its own), in the split-bf16 kernel the eight waves share one copy in the LDS ring.  The claim for round r + 2 is issued at the start of round r (thread 0) and published through LDS at the
     // start of round r + 1: no wave waits for the atomic.  The same barrier makes the "no valid sample" decision block-uniform, which is what
     // allows barriers inside the layer stack.  Every block leaves the loop once the counter passes ngroups: the grid always drains.
     // control words in LDS: fp32 kernel static, split-bf16 kernel inside its dynamic region (see the LDS map above)
@@ -739,14 +635,13 @@ __global__ __launch_bounds__(64 * WPB<MODE>, MODE == 1 ? VANERF_WAVES_PER_SIMD_B
     [[maybe_unused]] const unsigned wv_u = (unsigned)__builtin_amdgcn_readfirstlane((int)wv); // the same in a scalar register
     unsigned pending = 0, par = 1;
     if (threadIdx.x == 0) s_base(0) = atomicAdd(P.queue, (unsigned)WAVES_PER_BLOCK);
-    if constexpr (MODE == 1) { // resident fragments: one copy per block (the launch is persistent: 256 blocks x 156 KB from L2, once)
+    if constexpr (MODE == 1) { // resident fragments: one copy per block (the launch is persistent: 256 blocks x 126 KB from L2, once)
         const u32x4* __restrict__ src = reinterpret_cast<const u32x4*>(P.w) + RES_BASE_DW / 4;
         for (unsigned i = threadIdx.x; i < RES_DW / 4; i += BLOCK) s_dyn[LDS_RES / 16 + i] = src[i];
-        if constexpr (RING) { // phase 0 of the ring, once: every full round re-issues it for its successor (see phase_begin)
-            const LAddr la0 = make_laddr(lane, wv_u);
-            ring_dma<0>(W, la0);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
+        // phase 0 of the ring, once: every full round re-issues it for its successor (see phase_begin)
+        const LAddr la0 = make_laddr(lane, wv_u);
+        ring_dma<0>(W, la0);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
     __syncthreads();
     if constexpr (MODE == 1) { // the short path's constant latent (wave 0; the layer's fragments are resident by now)
@@ -836,8 +731,9 @@ __global__ __launch_bounds__(64 * WPB<MODE>, MODE == 1 ? VANERF_WAVES_PER_SIMD_B
 
         STAMP(1); // 1-NN
         // ---- GeoVisFusion (src/networks.py:75-106) ---------------------------------------------------------
-        // Every layer's fragment ring is started ahead of the previous layer's epilogue (see ring_start); the gathers of the
-        // second scale and of the texture branch are issued here too, so their L2 latency hides behind the first layers.
+        // Every layer's fragment ring is started ahead of the previous layer's epilogue (see ring_start).  The fp32 kernel issues the gathers
+        // of the second scale and of the texture branch early, so that their L2 latency hides behind the layers in front of them; the
+        // split-bf16 kernel has no registers to park them in and issues them where they are consumed (the partner wave hides the latency).
         [[maybe_unused]] const unsigned v4 = (unsigned)lane * 16u; // byte offset of the lane in a 4-block fp32 fragment
         // chain operand: register r of block b of a previous accumulator array, then the bias step
         auto chain = [&](auto& src, auto tc, auto nsteps) -> float {
@@ -852,7 +748,7 @@ __global__ __launch_bounds__(64 * WPB<MODE>, MODE == 1 ? VANERF_WAVES_PER_SIMD_B
         };
         float row[32]; // h = 0: nearest vertex [img3|tex8|gf18], h = 1: twin vertex
         float qi[4], qt[8];
-        auto tex_gathers = [&]() { // issued ~2 layers before the texture branch needs them
+        auto tex_gathers = [&]() {
             load_row<8>(F.vfeat_tex, (unsigned)((h ? tw_idx : nn_idx) * 32), row);
             gather<1>(F.img, bi, 4, 0, qi);
             const Bilin bt = bilin_setup(x, y, F.ht, F.wt, P.wm1[1], P.hm1[1]);
@@ -887,11 +783,11 @@ __global__ __launch_bounds__(64 * WPB<MODE>, MODE == 1 ? VANERF_WAVES_PER_SIMD_B
                     load_row<1>(F.vfeat1, (unsigned)(nn_idx * 8 + 4 * h), nn8);
                     load_row<1>(F.vfeat1, (unsigned)(tw_idx * 8 + 4 * h), tw8);
                 };
-                if constexpr (!(MODE == 1 && W2)) geo1_gathers();
+                if constexpr (MODE == 0) geo1_gathers();
                 STAMP(2); // geo gathers
                 if constexpr (HOIST) geo_scale0_vp<MODE>(W, lane, la, r_at0, pix, a0s, nn, tw, sc0, sc1, g64);
                 else geo_scale<MODE, HOIST, 32, 2, 16, L_GEO_AT0_A>(W, lane, la, r_at0, pix, nn, tw, sc0, sc1, g64);
-                if constexpr (MODE == 1 && W2) geo1_gathers();
+                if constexpr (MODE == 1) geo1_gathers();
                 STAMP(3); // geo0 layers
             }
             // mlp0's ring (7 x dwordx4) starts before the small second scale runs
@@ -903,11 +799,9 @@ __global__ __launch_bounds__(64 * WPB<MODE>, MODE == 1 ? VANERF_WAVES_PER_SIMD_B
                 auto r_at1 = ring_start_m<MODE, HOIST, 1, 14, L_GEO_AT1_A>(W, la);
                 if constexpr (MODE == 0) {
                     static_for<D0>([&](auto fc) { constexpr int f = decltype(fc)::value; ring0[f] = wload<4>(W, (base0 + f * 256) * 4u, v4); });
-                } else if constexpr (!W2) {
-                    if constexpr (MODE == 1) ring0b = ring_start_b<HOIST, 4, 180, false, layer_offset_b(L_MLP0, HOIST)>(W, la);
                 }
                 geo_scale<MODE, HOIST, 4, 1, 4, L_GEO_AT1_A>(W, lane, la, r_at1, pix8, nn8, tw8, sc0, sc1, g8);
-                if constexpr (MODE == 1 && W2) ring0b = ring_start_b<HOIST, 4, 180, false, layer_offset_b(L_MLP0, HOIST)>(W, la);
+                if constexpr (MODE == 1) ring0b = ring_start_b<HOIST, 4, 180, false, layer_offset_b(L_MLP0, HOIST)>(W, la);
                 STAMP(4); // geo1
             }
 
@@ -930,11 +824,10 @@ __global__ __launch_bounds__(64 * WPB<MODE>, MODE == 1 ? VANERF_WAVES_PER_SIMD_B
                     auto pe_features = [&](int i, float (&feat)[PE_FEATS]) {
                         // fp32 kernel: key points through the scalar cache (wave-uniform addresses), selected per lane half
                         float kx, ky, kz;
-                        if constexpr (MODE == 1 && W2) {
+                        if constexpr (MODE == 1) {
                             const u32x4 k = *reinterpret_cast<const lds_u32x4_t*>((size_t)(kp_lds + 16u * i));
                             kx = __uint_as_float(k.x); ky = __uint_as_float(k.y); kz = __uint_as_float(k.z);
-                        } else if constexpr (MODE == 1) { kx = kpx[i]; ky = kpy[i]; kz = kpz[i]; }
-                        else {
+                        } else {
                             const float4 k0 = kpg[i], k1 = kpg[PE_KPT_PER_HALF + i];
                             kx = h ? k1.x : k0.x; ky = h ? k1.y : k0.y; kz = h ? k1.z : k0.z;
                         }
@@ -980,7 +873,7 @@ __global__ __launch_bounds__(64 * WPB<MODE>, MODE == 1 ? VANERF_WAVES_PER_SIMD_B
                         // 179 the bias.  A bf16 step takes 8 consecutive pairs, so key point i is computed right before the first step
                         // that needs it (at most two key points are live at a time).
                         float feat[PE_KPT_PER_HALF][PE_FEATS];
-                        run_layer_b<HOIST, 4, 180, false, layer_offset_b(L_MLP0, HOIST), (((VANERF_P1_MASK >> L_MLP0) & 1) ? 1 : ((VANERF_P2_MASK >> L_MLP0) & 1) ? 2 : 3)>(a0, ring0b, W, la,
+                        run_layer_b<HOIST, 4, 180, false, layer_offset_b(L_MLP0, HOIST)>(a0, ring0b, W, la,
                             [&](auto tc) -> float {
                                 constexpr int t = decltype(tc)::value;
                                 if constexpr (t < 147) return feat[t / 7][t % 7];
@@ -1017,7 +910,7 @@ __global__ __launch_bounds__(64 * WPB<MODE>, MODE == 1 ? VANERF_WAVES_PER_SIMD_B
                 run_layer_m<MODE, HOIST, 2, 61, L_MLP3>(xv, r3, W, la, [&](auto tc) -> float { return chain_sp(a0, tc, std::integral_constant<int, 60>{}); });
             }
             STAMP(6); // softplus x3 + mlp1..3
-            if constexpr (!(MODE == 1 && W2)) tex_gathers();
+            if constexpr (MODE == 0) tex_gathers(); // ~2 layers before the texture branch needs them
             // ---- PoolModule mean/var over V = 1 views (src/utils.py:744-779, 854-880) --------------------------
             auto rh0 = ring_start_m<MODE, HOIST, 2, 65, L_HEAD0>(W, la);
             if constexpr (MODE == 0)
@@ -1044,16 +937,16 @@ __global__ __launch_bounds__(64 * WPB<MODE>, MODE == 1 ? VANERF_WAVES_PER_SIMD_B
                 if constexpr (MODE == 0) softplus<2>(m1);
                 zero<1>(head);
                 run_layer_m<MODE, HOIST, 1, 33, L_HEAD2>(head, rh2, W, la, [&](auto tc) -> float { return chain_sp(m1, tc, std::integral_constant<int, 32>{}); });
-                static_assert(LDS_FIRST == L_HEAD2 + 1 || !RING, "the ring is closed behind its last streamed layer");
+                static_assert(LDS_FIRST == L_HEAD2 + 1, "the ring is closed behind its last streamed layer");
                 if constexpr (MODE == 1) ring_close<HOIST>(W, la);
             }
         } else {
-            if constexpr (!(MODE == 1 && W2)) tex_gathers();
+            if constexpr (MODE == 0) tex_gathers();
             zero<4>(pool);
             zero<1>(head);
         }
         if (!wave_valid && lane == 0 && g < ngroups) ++short_groups; // counted by the wave's own samples (what bench.py prices), not by the block's path
-        if constexpr (MODE == 1 && W2) tex_gathers();
+        if constexpr (MODE == 1) tex_gathers();
         STAMP(7); // pool + head
         // ---- ibr_compress_gfeat 128 -> 24 (src/model.py:921) ------------------------------------------------
         f32x16 lat[1];
@@ -1135,9 +1028,9 @@ __global__ __launch_bounds__(64 * WPB<MODE>, MODE == 1 ? VANERF_WAVES_PER_SIMD_B
         }
         STAMP(9); // tex
         // ---- eval_func (src/model.py:1140-1160): rows 0,1 of the head / 0..2 of the colour live in the h = 0 lanes ----
-        // ring build: the DMA this wave issued in the round's last phase (phase 0 of the next full round) has landed before the wave reaches
+        // split-bf16 kernel: the DMA this wave issued in the round's last phase (phase 0 of the next full round) has landed before the wave reaches
         // the next top-of-round barrier -- waited for here, ahead of the stores, where nothing younger is in flight
-        if constexpr (MODE == 1 && RING) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if constexpr (MODE == 1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         if (live && h == 0) {
             float rad = head[0][1];
             if (P.noise) rad += P.noise[s];
@@ -1161,6 +1054,59 @@ __global__ __launch_bounds__(64 * WPB<MODE>, MODE == 1 ? VANERF_WAVES_PER_SIMD_B
 #endif
 }
 
+// ---- what the launch entries share: argument checks, the QueryParams of a launch, grid sizing, the launch itself ----
+void check_queue_word(const char* who, const void* queue_word)
+{
+    if (!queue_word || (reinterpret_cast<uintptr_t>(queue_word) & 7u)) throw_error("%s: queue_word must be 8 bytes of device memory, 8-byte aligned", who);
+}
+void check_frame_pointers(const char* who, const VanerfFrame& f)
+{
+    if (!f.geo0 || !f.geo1 || !f.tex || !f.img || !f.mask || !f.verts || !f.vfeat0 || !f.vfeat1 || !f.vfeat_tex || !f.vert_vis || !f.kpt_cam)
+        throw_error("%s: frame has a null pointer", who);
+}
+
+// The parameters every launch has; what only some have (noise, order, valid, stamps, short_groups, vp, the spills) starts out absent.
+QueryParams query_params(const VanerfFrame& f, const float* stream_w, size_t stream_floats, const float* pts, const float* query_sdf,
+                         const uint8_t* query_vis, const int32_t* knn_idx, int raw, int64_t n, float* out)
+{
+    QueryParams P = {};
+    P.f = f; P.w = stream_w; P.wbytes = (unsigned)(stream_floats * sizeof(float));
+    P.pts = pts; P.qsdf = query_sdf; P.qvis = query_vis; P.knn_in = knn_idx; P.raw = raw; P.n = n; P.out = out;
+    const int ws[4] = {f.wi, f.wt, f.w0, f.w1}, hs[4] = {f.hi, f.ht, f.h0, f.h1};
+    for (int i = 0; i < 4; ++i) { P.wm1[i] = (float)(ws[i] - 1); P.hm1[i] = (float)(hs[i] - 1); }
+    return P;
+}
+
+// One instantiation of query_kernel and the shape of its launch.  Blocks per CU follow from the kernel's waves per SIMD (four SIMDs per CU):
+// fp32 two 4-wave blocks -- fp32 MFMA and fp32 VALU do not overlap on gfx950 (tools/probe_mfma_valu.hip: every VALU instruction adds its issue
+// cycles to the MFMA time), so the second wave does not hide VALU work behind MFMAs; what it hides is load latency and the in-order issue gaps
+// of its partner --, split-bf16 ONE 8-wave block (it owns the CU's LDS), spill build one 4-wave block (it takes the whole register file).
+struct QueryLaunch { void (*kernel)(QueryParams); int wpb, blocks_per_cu; unsigned lds_bytes; };
+template <int MODE, bool SPILL = false, bool HOIST = false> QueryLaunch query_launch()
+{
+    return {query_kernel<MODE, SPILL, HOIST>, WPB<MODE>, (SPILL ? WAVES_PER_SIMD_SPILL : WAVES_PER_SIMD) * 4 / WPB<MODE>, MODE == 1 ? DYN_LDS_BYTES<HOIST> : 0u};
+}
+
+// persistent grid: one block per WPB groups, at most what the device holds at once (the blocks claim their groups from the queue word)
+long long query_blocks(const QueryLaunch& L, int64_t n)
+{
+    const long long ngroups = (n + 31) / 32;
+    int dev = 0, cus = 256;
+    HIP_CHECK(hipGetDevice(&dev));
+    HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    return std::min<long long>((ngroups + L.wpb - 1) / L.wpb, (long long)cus * L.blocks_per_cu);
+}
+
+void launch_query(const QueryLaunch& L, long long blocks, QueryParams& P, void* queue_word, void* stream)
+{
+    P.queue = static_cast<unsigned*>(queue_word); // the caller's word: no launch shares a queue head with another (any number in flight, any streams)
+    HIP_CHECK(hipMemsetAsync(P.queue, 0, 8, (hipStream_t)stream));
+    // the opt-in above 64 KB of dynamic LDS is per device: set on every call (cheap), as vanerf_mesh_query_accel does
+    if (L.lds_bytes) HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(L.kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds_bytes));
+    hipLaunchKernelGGL(L.kernel, dim3((unsigned)blocks), dim3(64 * L.wpb), L.lds_bytes, (hipStream_t)stream, P);
+    HIP_CHECK(hipGetLastError());
+}
+
 } // namespace
 
 extern "C" int vanerf_query_samples(const VanerfWeights* w, const VanerfFrame* frame, const float* pts, const float* query_sdf,
@@ -1180,47 +1126,19 @@ extern "C" int vanerf_query_samples_vp(const VanerfWeights* w, const VanerfFrame
         if (n < 0) throw_error("vanerf_query_samples: n = %lld < 0", (long long)n);
         if (n == 0) return; // an empty batch is valid (and has null data pointers)
         if (!w || !w->dev || !frame || !pts || !query_sdf || !query_vis || !knn_idx || !out) throw_error("vanerf_query_samples: null argument");
-        if (!queue_word || (reinterpret_cast<uintptr_t>(queue_word) & 7u)) throw_error("vanerf_query_samples: queue_word must be 8 bytes of device memory, 8-byte aligned");
+        check_queue_word("vanerf_query_samples", queue_word);
         if ((n + 31) / 32 >= 0xffffff00LL) throw_error("vanerf_query_samples: n = %lld too large for one launch", (long long)n);
         const VanerfFrame& f = *frame;
-        if (!f.geo0 || !f.geo1 || !f.tex || !f.img || !f.mask || !f.verts || !f.vfeat0 || !f.vfeat1 || !f.vfeat_tex || !f.vert_vis || !f.kpt_cam)
-            throw_error("vanerf_query_samples: frame has a null pointer");
+        check_frame_pointers("vanerf_query_samples", f);
         if (f.h0 < 1 || f.w0 < 1 || f.h1 < 1 || f.w1 < 1 || f.ht < 1 || f.wt < 1 || f.hi < 1 || f.wi < 1)
             throw_error("vanerf_query_samples: feature-map sizes must be positive");
         const bool hoist = vertex_products != nullptr;
         if (hoist && (w->mode != 1 || !w->n_floats_h)) throw_error("vanerf_query_samples_vp: a table of vertex products needs a bf16x3 weight handle");
         if (hoist && (reinterpret_cast<uintptr_t>(vertex_products) & 15u)) throw_error("vanerf_query_samples_vp: the table must be 16-byte aligned");
-        QueryParams P;
-        P.f = f; P.w = hoist ? w->dev + w->n_floats : w->dev; P.wbytes = (unsigned)((hoist ? w->n_floats_h : w->n_floats) * sizeof(float)); P.vp = vertex_products; P.pts = pts; P.qsdf = query_sdf; P.qvis = query_vis; P.noise = noise; P.knn_in = knn_idx; P.order = order; P.raw = raw;
-        P.n = n; P.out = out; P.valid = valid; P.stamps = nullptr; P.short_groups = w->stats;
-        P.xs = nullptr; P.aux = nullptr; P.npad = 0;
-        { const int ws[4] = {P.f.wi, P.f.wt, P.f.w0, P.f.w1}, hs[4] = {P.f.hi, P.f.ht, P.f.h0, P.f.h1};
-          for (int i = 0; i < 4; ++i) { P.wm1[i] = (float)(ws[i] - 1); P.hm1[i] = (float)(hs[i] - 1); } }
-       
-        long long ngroups = (n + 31) / 32;
-        const int wpb = w->mode == 1 ? WPB<1> : WPB<0>;
-        long long blocks = (ngroups + wpb - 1) / wpb;
-        int dev = 0, cus = 256;
-        HIP_CHECK(hipGetDevice(&dev));
-        HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-        // Two 4-wave blocks per CU = two waves per SIMD (256 VGPRs each).  fp32 MFMA and fp32 VALU do not overlap on gfx950
-        // (tools/probe_mfma_valu.hip: every VALU instruction adds its issue cycles to the MFMA time), so the second wave does not
-        // hide VALU work behind MFMAs; what it hides is load latency and the in-order issue gaps of its partner.
-        int per_cu = w->mode == 1 ? VANERF_WAVES_PER_SIMD_B * 4 / WPB<1> : 2;
-        if (const char* e = getenv("VANERF_BLOCKS_PER_CU")) per_cu = atoi(e) > 0 ? atoi(e) : 2; // experiment knob
-        long long cap = (long long)cus * per_cu;
-        if (blocks > cap) blocks = cap;
-        P.queue = static_cast<unsigned*>(queue_word); // the caller's word: no launch shares a queue head with another (any number in flight, any streams)
-        HIP_CHECK(hipMemsetAsync(P.queue, 0, 8, (hipStream_t)stream));
-        if (w->mode == 1 && hoist) {
-            HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(query_kernel<1, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)DYN_LDS_BYTES<true>));
-            hipLaunchKernelGGL((query_kernel<1, false, true>), dim3((unsigned)blocks), dim3(64 * WPB<1>), DYN_LDS_BYTES<true>, (hipStream_t)stream, P);
-        } else if (w->mode == 1) {
-            // the opt-in above 64 KB of dynamic LDS is per device: set on every call (cheap), as vanerf_mesh_query_accel does
-            HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(query_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)DYN_LDS_BYTES<false>));
-            hipLaunchKernelGGL(query_kernel<1>, dim3((unsigned)blocks), dim3(64 * WPB<1>), DYN_LDS_BYTES<false>, (hipStream_t)stream, P);
-        } else hipLaunchKernelGGL(query_kernel<0>, dim3((unsigned)blocks), dim3(64 * WPB<0>), 0, (hipStream_t)stream, P);
-        HIP_CHECK(hipGetLastError());
+        QueryParams P = query_params(f, hoist ? w->dev + w->n_floats : w->dev, hoist ? w->n_floats_h : w->n_floats, pts, query_sdf, query_vis, knn_idx, raw, n, out);
+        P.noise = noise; P.order = order; P.valid = valid; P.short_groups = w->stats; P.vp = vertex_products;
+        const QueryLaunch L = w->mode == 1 && hoist ? query_launch<1, false, true>() : w->mode == 1 ? query_launch<1>() : query_launch<0>();
+        launch_query(L, query_blocks(L, n), P, queue_word, stream);
     });
 }
 
@@ -1234,30 +1152,17 @@ extern "C" int vanerf_query_forward_spill(const VanerfWeights* w, const VanerfFr
         if (n <= 0) throw_error("vanerf_query_forward_spill: n = %lld", (long long)n);
         if (!w || !w->dev || w->mode != 0) throw_error("vanerf_query_forward_spill: needs an fp32 weight handle (vanerf_weights_pack mode 0)");
         if (!frame || !pts || !query_sdf || !query_vis || !knn_idx || !out_raw || !xs || !aux) throw_error("vanerf_query_forward_spill: null argument");
-        if (!queue_word || (reinterpret_cast<uintptr_t>(queue_word) & 7u)) throw_error("vanerf_query_forward_spill: queue_word must be 8 bytes of device memory, 8-byte aligned");
+        check_queue_word("vanerf_query_forward_spill", queue_word);
         if (npad < n || npad % 32 != 0) throw_error("vanerf_query_forward_spill: npad = %lld must be a multiple of 32 and >= n = %lld", (long long)npad, (long long)n);
         if ((long long)X_ROWS * 4 * npad >= (long long)SPILL_OFF)
             throw_error("vanerf_query_forward_spill: a block of %lld samples spills more than 4 GB (the kernels address the spills with 32-bit offsets): at most %lld",
                         (long long)npad, (long long)SPILL_OFF / (4 * X_ROWS) / 32 * 32);
         const VanerfFrame& f = *frame;
-        if (!f.geo0 || !f.geo1 || !f.tex || !f.img || !f.mask || !f.verts || !f.vfeat0 || !f.vfeat1 || !f.vfeat_tex || !f.vert_vis || !f.kpt_cam)
-            throw_error("vanerf_query_forward_spill: frame has a null pointer");
-        QueryParams P;
-        P.f = f; P.w = w->dev; P.wbytes = (unsigned)(w->n_floats * sizeof(float)); P.pts = pts; P.qsdf = query_sdf; P.qvis = query_vis; P.noise = nullptr; P.knn_in = knn_idx; P.order = nullptr; P.raw = 1;
-        P.n = n; P.out = out_raw; P.valid = valid; P.stamps = nullptr; P.short_groups = nullptr;
-        P.xs = xs; P.aux = aux; P.npad = npad; P.vp = nullptr;
-        { const int ws[4] = {P.f.wi, P.f.wt, P.f.w0, P.f.w1}, hs[4] = {P.f.hi, P.f.ht, P.f.h0, P.f.h1};
-          for (int i = 0; i < 4; ++i) { P.wm1[i] = (float)(ws[i] - 1); P.hm1[i] = (float)(hs[i] - 1); } }
-        const long long ngroups = (n + 31) / 32;
-        long long blocks = (ngroups + WPB<0> - 1) / WPB<0>;
-        int dev = 0, cus = 256;
-        HIP_CHECK(hipGetDevice(&dev));
-        HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-        if (blocks > (long long)cus * VANERF_WAVES_PER_SIMD_SPILL) blocks = (long long)cus * VANERF_WAVES_PER_SIMD_SPILL; // one 4-wave block per CU (the spill build takes the whole register file: at 256 registers it goes to scratch)
-        P.queue = static_cast<unsigned*>(queue_word);
-        HIP_CHECK(hipMemsetAsync(P.queue, 0, 8, (hipStream_t)stream));
-        hipLaunchKernelGGL((query_kernel<0, true>), dim3((unsigned)blocks), dim3(64 * WPB<0>), 0, (hipStream_t)stream, P);
-        HIP_CHECK(hipGetLastError());
+        check_frame_pointers("vanerf_query_forward_spill", f);
+        QueryParams P = query_params(f, w->dev, w->n_floats, pts, query_sdf, query_vis, knn_idx, 1, n, out_raw);
+        P.valid = valid; P.xs = xs; P.aux = aux; P.npad = npad;
+        const QueryLaunch L = query_launch<0, true>();
+        launch_query(L, query_blocks(L, n), P, queue_word, stream);
     });
 }
 
@@ -1359,24 +1264,12 @@ extern "C" int vanerf_debug_query_stamps(const VanerfWeights* w, const VanerfFra
                                          const uint8_t* query_vis, const int32_t* knn_idx, int64_t n, float* out, unsigned long long* stamps, int* n_waves, void* queue_word, void* stream)
 {
     return guarded([&] {
-        QueryParams P;
-        P.f = *frame; P.w = w->dev; P.wbytes = (unsigned)(w->n_floats * sizeof(float)); P.pts = pts; P.qsdf = query_sdf; P.qvis = query_vis; P.noise = nullptr; P.knn_in = knn_idx; P.order = nullptr; P.raw = 0;
-        P.n = n; P.out = out; P.valid = nullptr; P.stamps = stamps; P.short_groups = nullptr; P.vp = nullptr;
-        { const int ws[4] = {P.f.wi, P.f.wt, P.f.w0, P.f.w1}, hs[4] = {P.f.hi, P.f.ht, P.f.h0, P.f.h1};
-          for (int i = 0; i < 4; ++i) { P.wm1[i] = (float)(ws[i] - 1); P.hm1[i] = (float)(hs[i] - 1); } }
-        long long ngroups = (n + 31) / 32;
-        const int wpb = w->mode == 1 ? WPB<1> : WPB<0>;
-        long long blocks = (ngroups + wpb - 1) / wpb;
-        long long capd = w->mode == 1 ? 256LL * VANERF_WAVES_PER_SIMD_B * 4 / WPB<1> : 512;
-        if (const char* e = getenv("VANERF_BLOCKS_PER_CU")) capd = 256LL * (atoi(e) > 0 ? atoi(e) : 2);
-        if (blocks > capd) blocks = capd;
-        *n_waves = (int)blocks * wpb;
-        P.queue = static_cast<unsigned*>(queue_word);
-        HIP_CHECK(hipMemsetAsync(P.queue, 0, 8, (hipStream_t)stream));
-        if (stamps && w->mode == 1) HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(query_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)DYN_LDS_BYTES<false>));
-        if (stamps && w->mode == 1) hipLaunchKernelGGL(query_kernel<1>, dim3((unsigned)blocks), dim3(64 * WPB<1>), DYN_LDS_BYTES<false>, (hipStream_t)stream, P);
-        else if (stamps) hipLaunchKernelGGL(query_kernel<0>, dim3((unsigned)blocks), dim3(64 * WPB<0>), 0, (hipStream_t)stream, P);
-        HIP_CHECK(hipGetLastError());
+        QueryParams P = query_params(*frame, w->dev, w->n_floats, pts, query_sdf, query_vis, knn_idx, 0, n, out);
+        P.stamps = stamps;
+        const QueryLaunch L = w->mode == 1 ? query_launch<1>() : query_launch<0>();
+        const long long blocks = query_blocks(L, n);
+        *n_waves = (int)blocks * L.wpb;
+        if (stamps) launch_query(L, blocks, P, queue_word, stream); // (without a table: the caller asks how many waves there will be)
     });
 }
 #endif

@@ -7,8 +7,6 @@
 // atomics (a contended LDS atomic costs cycles, not a trip to the memory side), and flushes the slice once with global atomics.
 #include <algorithm>
 
-#include <cstdlib>
-
 #include "common.h"
 
 using namespace vanerf;
@@ -173,7 +171,7 @@ void scatter_rows(const int32_t* idx, const float* w, const float* g, int64_t g_
         // blocks = chunks x slices: 4 096 samples per chunk for a whole training patch (~5e5 samples), but never fewer than ~512 blocks' worth of
         // work in flight -- the fused backward calls this once per block of 65 536 samples, where 16 chunks x 4 slices left three quarters of the chip idle
         int chunks = (int)((n + 4095) / 4096);
-        static const int fill_blocks = [] { const char* e = getenv("VANERF_SCATTER_FILL"); return e ? atoi(e) : 256; }(); // (256 / 512 / 1024 blocks' worth measured: 12.2 / 12.6 / 12.6 ms of the step's fused stage)
+        constexpr int fill_blocks = 256; // (256 / 512 / 1024 blocks' worth measured: 12.2 / 12.6 / 12.6 ms of the step's fused stage)
         const int fill = (int)std::min<long long>((n + 511) / 512, fill_blocks / slices > 0 ? fill_blocks / slices : 1);
         if (chunks < fill) chunks = fill;
         if (chunks > 1024 / slices) chunks = 1024 / slices > 0 ? 1024 / slices : 1;
