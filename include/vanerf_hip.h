@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define VANERF_ABI_VERSION 10
+#define VANERF_ABI_VERSION 11
 
 #define VANERF_OK 0
 #define VANERF_EINVAL (-22)
@@ -117,7 +117,7 @@ int vanerf_weights_short_groups(const VanerfWeights* w, uint64_t* count);
 int vanerf_weights_pack_host(const VanerfWeightTable* w, float* out, int64_t cap, int64_t* n_out, unsigned* offsets);
 /* Host-only view of any stream a handle can carry: which = 0 the fp32 forward stream, 1 the bf16x3 forward stream (32-bit words of two bf16
  * each, copied raw), 2 the transposed fp32 stream of the fused backward pass, 3 the hoisted bf16x3 stream a bf16x3 handle carries behind
- * stream 1 (what vanerf_query_samples_vp runs on: three first layers packed with their per-sample k-pairs only).  out[cap] or NULL: the size. */
+ * stream 1 (what vanerf_query_samples runs on when it is given vertex_products: three first layers packed with their per-sample k-pairs only).  out[cap] or NULL: the size. */
 int vanerf_weights_stream_host(const VanerfWeightTable* w, int which, float* out, int64_t cap, int64_t* n_out);
 /* The streams a handle holds on the device, copied back to host memory (blocking; for tests of vanerf_weights_update): which = 0 the forward
  * stream of the handle's mode, 2 the backward stream (fp32 handles only), 3 the hoisted bf16x3 stream (bf16x3 handles only).                     */
@@ -229,10 +229,14 @@ int vanerf_knn1(const float* verts4, int nv, const float* pts, int64_t n, int32_
  *     order[N] or NULL: a permutation of 0..N-1 from vanerf_query_order; slot k of the launch then works on sample order[k].  Inputs are
  *         read and outputs written at the sample's own index either way: the results do not depend on `order`, only the time does.
  *     raw = 0 -> out[N][5] = [alpha, sdf, r, g, b] (eval_func applied);  raw = 1 -> [sdf_pred, rad, r, g, b] as VANeRF.query returns
- *     valid[N] (u8, may be NULL)                                                                                          */
+ *     valid[N] (u8, may be NULL)
+ *     vertex_products: the frame's table from vanerf_vertex_products below (built with the same handle, after its last update), or NULL.  With the
+ *         table a bf16x3 handle runs the hoisted kernel: it starts the three layers' accumulators from the gathered table rows and runs their
+ *         per-sample k-steps only (outputs within 1e-5 of the un-hoisted kernel's: summation order).  NULL selects the un-hoisted kernel.       */
 int vanerf_query_samples(const VanerfWeights* w, const VanerfFrame* frame, const float* pts, const float* query_sdf,
                          const uint8_t* query_vis, const int32_t* knn_idx, const float* noise, const int32_t* order, int raw, int64_t n,
-                         float* out, uint8_t* valid, void* queue_word /* as for vanerf_mesh_query_accel */, void* stream);
+                         float* out, uint8_t* valid, void* queue_word /* as for vanerf_mesh_query_accel */, const float* vertex_products,
+                         void* stream);
 
 /* The per-vertex half of three first layers, once per source frame (bf16x3 handles).  geo_vis_fusion.fconv_at.0, geo_vis_fusion.fconv_ated.0 and
  * tex_vis_fusion.fconv_at.0 (src/networks.py:86-93, 285-288) multiply, per sample, rows of the frame's vertex tables that depend only on the
@@ -241,11 +245,6 @@ int vanerf_query_samples(const VanerfWeights* w, const VanerfFrame* frame, const
  * `stream` into table[cap_floats] (16-byte aligned; no allocation, no host synchronisation), returns 0; < 0: error.  The table belongs to
  * (handle contents, frame): rebuild it after vanerf_weights_update -- the library keeps no cache.                                          */
 int vanerf_vertex_products(const VanerfWeights* w, const VanerfFrame* frame, float* table, int64_t cap_floats, void* stream);
-/* vanerf_query_samples with that table: the hoisted bf16x3 kernel starts the three layers' accumulators from the gathered table rows and runs
- * their per-sample k-steps only (outputs within 1e-5 of vanerf_query_samples': summation order).  vertex_products == NULL is vanerf_query_samples. */
-int vanerf_query_samples_vp(const VanerfWeights* w, const VanerfFrame* frame, const float* pts, const float* query_sdf,
-                            const uint8_t* query_vis, const int32_t* knn_idx, const float* noise, const int32_t* order, int raw, int64_t n,
-                            float* out, uint8_t* valid, void* queue_word, const float* vertex_products, void* stream);
 
 /* Validity partition for vanerf_query_samples: order[N] = the samples whose projection hits the source view and its foreground mask
  * (src/model.py:780-803), in their order, then the others, in their order.  A 32-sample group of vanerf_query_samples in which no sample
@@ -255,28 +254,25 @@ int vanerf_query_order(const VanerfFrame* frame, const float* pts, int64_t n, in
                        void* stream);
 int64_t vanerf_query_order_scratch(int64_t n);
 
-/* a16  sdf_activation + rgba2out (src/model.py:879-882, 1464-1494):
- *     rgba[R][S][5], z[R][S], mesh_sdf[R][S] -> color[R][3], depth[R], alpha[R], sdf[R], contrib[R][S] (may be NULL)      */
-int vanerf_composite(const float* rgba, const float* z, const float* mesh_sdf, int R, int S, float beta,
-                     float* color, float* depth, float* alpha, float* sdf, float* contrib, void* stream);
-
-/* a16 + a18  Fine composite that re-uses the coarse evaluations: sample i of ray r is coarse sample src[r][i] (>= 0) or
- *     importance sample ~src[r][i] (< 0), in the merged depth order z_fine[R][Sc+Sn] produced by vanerf_importance_merge.
- *     Identical bits to vanerf_composite on a re-evaluated (R, Sc+Sn) batch (the networks are per-sample pure functions). */
-int vanerf_composite_merged(const float* rgba_c, const float* mesh_sdf_c, int Sc, const float* rgba_n, const float* mesh_sdf_n,
-                            int Sn, const int32_t* src, const float* z_fine, int R, float beta, float* color, float* depth,
-                            float* alpha, float* sdf, float* contrib, void* stream);
-/* Either composite with sigmoid_beta read from the weight handle's device copy (what vanerf_render_pass does; after vanerf_weights_update the host
- * never sees the value): rgba_n == NULL composites the Sa samples per ray of one table, otherwise [table | rgba_n table] in merged order (src).   */
-/* eval_func (src/model.py:1140-1160) on raw outputs of vanerf_query_samples(raw = 1): [sdf_pred, rad, r, g, b] -> [alpha, sdf, r, g, b] with the validity
- * flags and optional per-sample noise, the arithmetic of the kernel's own epilogue (same bits).  src == NULL: R x Sa entries of table a, noise[i] per entry;
- * otherwise noise[r][p] belongs to position p of ray r's merged order and src names the entry (>= 0 table a, < 0 entry ~src of table b), each written once.
- * The outputs may be the raw tables themselves.  With training noise a pass evaluates the networks once per point and runs this once per set of draws.     */
-int vanerf_eval_func(const float* raw_a, const uint8_t* valid_a, const float* raw_b, const uint8_t* valid_b, const int32_t* src, const float* noise,
-                     int Sa, int Sb, int R, float invalid_sdf, float* rgba_a, float* rgba_b, void* stream);
+/* a16  sdf_activation + rgba2out (src/model.py:879-882, 1464-1494), with S = Sa samples per ray of one table (rgba_n == NULL; mesh_sdf_n, Sn, src ignored):
+ *     rgba[R][S][5], z[R][S], mesh_sdf[R][S] -> color[R][3], depth[R], alpha[R], sdf[R], contrib[R][S] (may be NULL)
+ * a16 + a18  or, with a second table, the fine composite that re-uses the coarse evaluations: S = Sa + Sn, sample i of ray r is entry src[r][i] (>= 0)
+ *     of rgba[R][Sa][5] / mesh_sdf[R][Sa] (the coarse samples) or entry ~src[r][i] (< 0) of rgba_n[R][Sn][5] / mesh_sdf_n[R][Sn] (the importance
+ *     samples), in the merged depth order z[R][Sa+Sn] produced by vanerf_importance_merge.  Identical bits to the one-table form on a
+ *     re-evaluated (R, Sa+Sn) batch (the networks are per-sample pure functions).
+ * beta: sigmoid_beta by value (> 0; clamped to >= 2e-3).  vanerf_composite_handle is the same call with sigmoid_beta read from the weight handle's
+ * device copy instead (what vanerf_render_pass does; after vanerf_weights_update the host never sees the value).                               */
+int vanerf_composite(const float* rgba, const float* z, const float* mesh_sdf, int Sa, const float* rgba_n, const float* mesh_sdf_n, int Sn,
+                     const int32_t* src, int R, float beta, float* color, float* depth, float* alpha, float* sdf, float* contrib, void* stream);
 int vanerf_composite_handle(const VanerfWeights* w, const float* rgba, const float* z, const float* mesh_sdf, int Sa, const float* rgba_n,
                             const float* mesh_sdf_n, int Sn, const int32_t* src, int R, float* color, float* depth, float* alpha, float* sdf,
                             float* contrib, void* stream);
+/* eval_func (src/model.py:1140-1160) on raw outputs of vanerf_query_samples(raw = 1): [sdf_pred, rad, r, g, b] -> [alpha, sdf, r, g, b] with the validity
+ * flags and optional per-sample noise, the arithmetic of the kernel's own epilogue (same bits).  src == NULL: R x Sa entries of table a, noise[i] per entry;
+ * otherwise noise[r][p] belongs to position p of ray r's merged order and src names the entry (>= 0 table a, < 0 entry ~src of table b), each written once.
+ * The outputs may be the raw tables themselves (rgba_a == raw_a, rgba_b == raw_b: every entry is read, then written, by one thread).  With training noise a pass evaluates the networks once per point and runs this once per set of draws.     */
+int vanerf_eval_func(const float* raw_a, const uint8_t* valid_a, const float* raw_b, const uint8_t* valid_b, const int32_t* src, const float* noise,
+                     int Sa, int Sb, int R, float invalid_sdf, float* rgba_a, float* rgba_b, void* stream);
 /* Training: the backward of either composite (reference: autograd through rgba2out / sdf_activation, src/model.py:1464-1494, 879-882), tables and src as
  * vanerf_composite_handle.  g_color [R][3], g_depth, g_alpha, g_sdf [R]: gradients with respect to the composite's outputs (any may be NULL = 0);
  * d_rgba [R][Sa][5] (and d_rgba_n [R][Sn][5]): gradient with respect to every table entry (each is written once), d_beta [R] or NULL: the rays' shares
@@ -340,14 +336,10 @@ typedef struct {               /* all device pointers; R = nx * ny */
 
 /* reuse_coarse: 0, 1 as VanerfPassDesc.reuse_coarse; 2 = re-use under per-sample noise (desc->reuse_coarse with noise_c given: more temporaries) */
 int64_t vanerf_render_pass_scratch(int n_rays, int Sc, int Sf, int fine, int reuse_coarse);
+/* vertex_products: the frame's table of vanerf_vertex_products for the pass's per-sample launches, or NULL (as vanerf_query_samples) */
 int vanerf_render_pass(const VanerfWeights* w, const VanerfFrame* frame, const VanerfMeshAccel* accel, const float* verts, int nv,
                        const int32_t* faces, int nf, const VanerfPassDesc* desc, const VanerfPassOut* out, void* scratch, int64_t scratch_bytes,
-                       void* stream);
-
-/* ... with the frame's table of vanerf_vertex_products for the pass's per-sample launches (NULL: vanerf_render_pass itself) */
-int vanerf_render_pass_vp(const VanerfWeights* w, const VanerfFrame* frame, const VanerfMeshAccel* accel, const float* verts, int nv,
-                          const int32_t* faces, int nf, const VanerfPassDesc* desc, const VanerfPassOut* out, void* scratch, int64_t scratch_bytes,
-                          const float* vertex_products, void* stream);
+                       const float* vertex_products, void* stream);
 
 /* One pass over n_views target views of the same source frame that share a pixel grid (the frames of an orbit, the views of a validation step):
  * the kernels of vanerf_render_pass once over n_views * nx * ny rays instead of n_views times over nx * ny.  Behind the ray setup nothing
@@ -370,11 +362,7 @@ typedef struct {
 int64_t vanerf_render_pass_views_scratch(int n_views, int rays_per_view, int Sc, int Sf, int fine, int reuse_coarse); /* 0: bad arguments */
 int vanerf_render_pass_views(const VanerfWeights* w, const VanerfFrame* frame, const VanerfMeshAccel* accel, const float* verts, int nv,
                              const int32_t* faces, int nf, const VanerfViewsDesc* desc, const VanerfPassOut* out, void* scratch,
-                             int64_t scratch_bytes, void* stream);
-
-int vanerf_render_pass_views_vp(const VanerfWeights* w, const VanerfFrame* frame, const VanerfMeshAccel* accel, const float* verts, int nv,
-                                const int32_t* faces, int nf, const VanerfViewsDesc* desc, const VanerfPassOut* out, void* scratch,
-                                int64_t scratch_bytes, const float* vertex_products /* as vanerf_render_pass_vp */, void* stream);
+                             int64_t scratch_bytes, const float* vertex_products /* as vanerf_render_pass */, void* stream);
 
 /* Training step, backward of the row gathers (bilinear taps of feat_sample, src/utils.py:136-151; nearest / twin vertex rows of KNN_vis,
  * src/networks.py:27-33):  table[idx[i]][0..C) += w[i] * g[i][0..C)  for i < n  (w may be NULL = 1; rows outside [0, R) are ignored).

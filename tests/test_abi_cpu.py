@@ -25,13 +25,16 @@ def test_exports_match_header(ffi):
     assert declared == set(ffi.EXPORTS)
     for name in declared:
         assert hasattr(ffi.lib, name), name
-    assert ffi.lib.vanerf_abi_version() == ffi.ABI_VERSION == 10
+    assert ffi.lib.vanerf_abi_version() == ffi.ABI_VERSION == 11
 
 
 def test_error_convention(ffi):
     # null arguments: negative return code + message, no exception across the ABI, no GPU touched
-    rc = ffi.lib.vanerf_composite(None, None, None, 4, 4, 0.1, None, None, None, None, None, None)
+    rc = ffi.lib.vanerf_composite(None, None, None, 4, None, None, 0, None, 4, 0.1, None, None, None, None, None, None)
     assert rc == -22 and b"null" in ffi.lib.vanerf_last_error()
+    p = ctypes.c_void_p(8)
+    rc = ffi.lib.vanerf_composite(p, p, p, 4, p, p, 4, None, 4, 0.1, p, p, p, p, None, None)  # the merged form: a second table without src
+    assert rc == -22 and b"second table" in ffi.lib.vanerf_last_error()
     rc = ffi.lib.vanerf_knn1(ctypes.c_void_p(8), 0, ctypes.c_void_p(8), 1, ctypes.c_void_p(8), None)
     assert rc == -22 and b"nv=0" in ffi.lib.vanerf_last_error()
     assert ffi.lib.vanerf_knn1(None, 4, None, 0, None, None) == 0  # an empty batch is valid

@@ -1151,6 +1151,45 @@ def test_eval_func_kernel_against_the_formula(R):
     assert lib.vanerf_eval_func(P(raw_a), P(val_a), None, None, P(src), P(noise_m), Sa, Sb, rays, inv, P(out_a), None, st) < 0  # merged order without table b
 
 
+def test_eval_func_in_place_equals_out_of_place(R):
+    """vanerf_eval_func with its outputs on top of its inputs (rgba_a = raw_a, rgba_b = raw_b: what the header allows and the noisy pass does with
+    its second table) gives the bits of the call with separate output tables.  8 rays of 5 + 3 entries -- both tables, both signs of src, more
+    entries per ray than either table holds -- every ray naming each entry of both tables once, a draw per position, valid and invalid entries in
+    both tables; and the form without an origin map (8 x 5 entries of table a)."""
+    import ctypes
+    from vanerf_amd._ffi import lib, check
+    g = torch.Generator(device="cuda").manual_seed(11)
+    rays, Sa, Sb, inv = 8, 5, 3, 0.0125
+    P = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
+    st = R._stream()
+    raw_a = torch.randn(rays, Sa, 5, device="cuda", generator=g)
+    raw_b = torch.randn(rays, Sb, 5, device="cuda", generator=g)
+    val_a = (torch.rand(rays, Sa, device="cuda", generator=g) > 0.4).to(torch.uint8)
+    val_b = (torch.rand(rays, Sb, device="cuda", generator=g) > 0.4).to(torch.uint8)
+    for v in (val_a, val_b):  # both values in both tables, whatever was drawn
+        v[0, 0], v[0, 1] = 0, 1
+    perm = torch.argsort(torch.rand(rays, Sa + Sb, device="cuda", generator=g), dim=1)
+    src = torch.where(perm < Sa, perm, -(perm - Sa) - 1).to(torch.int32).contiguous()
+    ids = torch.where(src >= 0, src, Sa + ~src).long()
+    assert torch.equal(ids.sort(1)[0], torch.arange(Sa + Sb, device="cuda").expand(rays, -1))  # each entry of both tables once per ray
+    noise = torch.randn(rays, Sa + Sb, device="cuda", generator=g) * 0.5
+    # merged order
+    out_a, out_b = torch.full_like(raw_a, float("nan")), torch.full_like(raw_b, float("nan"))
+    check(lib.vanerf_eval_func(P(raw_a), P(val_a), P(raw_b), P(val_b), P(src), P(noise), Sa, Sb, rays, inv, P(out_a), P(out_b), st))
+    in_a, in_b = raw_a.clone(), raw_b.clone()
+    check(lib.vanerf_eval_func(P(in_a), P(val_a), P(in_b), P(val_b), P(src), P(noise), Sa, Sb, rays, inv, P(in_a), P(in_b), st))
+    assert not torch.isnan(out_a).any() and not torch.isnan(out_b).any()
+    assert torch.equal(in_a, out_a) and torch.equal(in_b, out_b)
+    assert not torch.equal(out_a, raw_a) and not torch.equal(out_b, raw_b)  # (the call did something)
+    # no origin map: entry i of table a with draw i
+    noise_a = noise[:, :Sa].contiguous()
+    out = torch.full_like(raw_a, float("nan"))
+    check(lib.vanerf_eval_func(P(raw_a), P(val_a), None, None, None, P(noise_a), Sa, 0, rays, inv, P(out), None, st))
+    in_a = raw_a.clone()
+    check(lib.vanerf_eval_func(P(in_a), P(val_a), None, None, None, P(noise_a), Sa, 0, rays, inv, P(in_a), None, st))
+    assert not torch.isnan(out).any() and torch.equal(in_a, out)
+
+
 def test_scatter_add_rows(R):
     """vanerf_scatter_add_rows (backward of the row gathers of a training step) against torch.index_add_: tables of 1 024 x 64, 16 384 x 8 and
     1 558 x 29 rows x channels, heavy index duplication, optional per-sample weights, out-of-range rows ignored, accumulation into a non-zero table."""

@@ -36,7 +36,7 @@ def test_new_entry_points_are_exported_and_declared(ffi):
         assert name in ffi.EXPORTS and hasattr(ffi.lib, name)
         assert f"{name}(" in header
     assert "VanerfViewsDesc" in header and hasattr(ffi, "VanerfViewsDesc")
-    assert ffi.ABI_VERSION == 10 and ffi.lib.vanerf_abi_version() == 10 and "#define VANERF_ABI_VERSION 10" in header  # additive: no bump
+    assert ffi.ABI_VERSION == 11 and ffi.lib.vanerf_abi_version() == 11 and "#define VANERF_ABI_VERSION 11" in header
 
 
 def test_views_scratch_size(ffi):
@@ -93,7 +93,7 @@ def test_render_pass_views_rejects_bad_arguments(ffi):
 
     def call(d, w=p, o=out, scratch=p, nbytes=0):
         return lib.vanerf_render_pass_views(w, ctypes.byref(frame), ctypes.byref(accel), p, 4, p, 4, ctypes.byref(d) if d is not None else None,
-                                            ctypes.byref(o), scratch, nbytes, None)
+                                            ctypes.byref(o), scratch, nbytes, None, None)
 
     assert call(desc(), w=None) == -22 and b"null" in lib.vanerf_last_error()
     assert call(None) == -22 and b"null" in lib.vanerf_last_error()

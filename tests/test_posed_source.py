@@ -110,7 +110,7 @@ def test_per_frame_tables(R, sd_full, pose):
 @pytest.mark.parametrize("kernel", list(KERNELS))
 @pytest.mark.parametrize("pose", [p for p, _ in POSES])
 def test_query_samples_on_posed_cameras(R, sd_full, pose, kernel):
-    """vanerf_query_samples (fp32, bf16x3) and the hoisted vanerf_query_samples_vp (bf16x3) against the fp64 oracle.  First the inputs are
+    """vanerf_query_samples (fp32, bf16x3) and its hoisted form with vertex_products (bf16x3) against the fp64 oracle.  First the inputs are
     proved safe: in fp64 no point lies within 1e-5 of a validity decision (|x|, |y| <= 1.01, z >= -1, fg > 0.1), so none is excluded and the
     validity flags must be equal."""
     c = _case(R, sd_full, pose)

@@ -241,7 +241,7 @@ def test_a_changed_weight_rebuilds_the_table(R):
 
 @pytest.mark.gpu
 def test_one_call_pass_with_the_table_equals_the_python_sequence(R, sd_full):
-    """vanerf_render_pass_vp against renderer.render_pass with the same table: 16 x 16 rays, 16 + 16 samples, every output bit for bit -- and
+    """vanerf_render_pass with vertex_products against renderer.render_pass with the same table: 16 x 16 rays, 16 + 16 samples, every output bit for bit -- and
     the table is in use (VANERF_VERTEX_PRODUCTS=0 gives the un-hoisted bits, which differ)."""
     import os
     frame = synth.make_frame(seed=3, tar_h=64, tar_w=64)
@@ -269,7 +269,7 @@ def test_one_call_pass_with_the_table_equals_the_python_sequence(R, sd_full):
 
 @pytest.mark.gpu
 def test_multi_view_pass_with_the_table_equals_single_passes(R, sd_full):
-    """vanerf_render_pass_views_vp: 2 views of 40 x 20 rays in one pass hold, view after view, the bits of the single-view passes."""
+    """vanerf_render_pass_views with vertex_products: 2 views of 40 x 20 rays in one pass hold, view after view, the bits of the single-view passes."""
     from vanerf_amd.model import get_360cameras
     from vanerf_amd.novel_views import camera_to_cam_tar
     frame = synth.make_frame(seed=3, tar_h=64, tar_w=64)

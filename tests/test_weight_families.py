@@ -392,7 +392,7 @@ def test_device_packer_equals_the_host_packer_on_every_family(R, name, precision
 @pytest.mark.parametrize("kernel", ["fp32", "bf16x3", "bf16x3_hoisted"])
 @pytest.mark.parametrize("name", FAMILIES)
 def test_forward_kernels_on_every_family(R, name, kernel):
-    """vanerf_query_samples (fp32, bf16x3) and the hoisted vanerf_query_samples_vp on N_POINTS points of pose A against the fp64 oracle: equal
+    """vanerf_query_samples (fp32, bf16x3) and its hoisted form with vertex_products on N_POINTS points of pose A against the fp64 oracle: equal
     validity flags and 1-NN indices; wide / ties / sparse within 1e-4 and the sigma check of tests/test_posed_source.py; gains within the bar
     computed from the oracle alone, sigma with each sigmoid_beta of the family as the handle clamps it."""
     from tests.test_posed_source import _run_kernel, _within_the_bar

@@ -1,4 +1,4 @@
-"""Times vanerf_importance_merge + vanerf_composite_merged at several samples-per-ray counts (171 008 rays)."""
+"""Times vanerf_importance_merge + the two-table vanerf_composite at several samples-per-ray counts (171 008 rays)."""
 import sys
 import torch
 sys.path.insert(0, ".")

@@ -12,7 +12,7 @@ from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VANERF_HIP_LIB") or os.path.join(_HERE, "lib", "libvanerf_hip.so")  # the override is for A/B runs of kernel builds (tools/)
-ABI_VERSION = 10
+ABI_VERSION = 11
 NUM_LAYERS = 20
 
 if not os.path.exists(LIB_PATH):
@@ -103,9 +103,8 @@ _SIGS = {
     "vanerf_mesh_query_accel": (c_int, [POINTER(VanerfMeshAccel), _FP, c_int, _FP, c_int, _FP, _FP, c_int64, _FP, _FP, _FP, _FP, c_int, c_int, c_int,
                                         _FP, c_void_p]),
     "vanerf_knn1": (c_int, [_FP, c_int, _FP, c_int64, _FP, c_void_p]),
-    "vanerf_query_samples": (c_int, [c_void_p, POINTER(VanerfFrame), _FP, _FP, _FP, _FP, _FP, _FP, c_int, c_int64, _FP, _FP, _FP, c_void_p]),
+    "vanerf_query_samples": (c_int, [c_void_p, POINTER(VanerfFrame), _FP, _FP, _FP, _FP, _FP, _FP, c_int, c_int64, _FP, _FP, _FP, _FP, c_void_p]),
     "vanerf_vertex_products": (c_int, [c_void_p, POINTER(VanerfFrame), _FP, c_int64, c_void_p]),
-    "vanerf_query_samples_vp": (c_int, [c_void_p, POINTER(VanerfFrame), _FP, _FP, _FP, _FP, _FP, _FP, c_int, c_int64, _FP, _FP, _FP, _FP, c_void_p]),
     "vanerf_query_forward_spill": (c_int, [c_void_p, POINTER(VanerfFrame), _FP, _FP, _FP, _FP, c_int64, c_int64, _FP, _FP, _FP, _FP, _FP, c_void_p]),
     "vanerf_query_backward": (c_int, [c_void_p, _FP, _FP, _FP, _FP, _FP, _FP, c_int64, c_int64, _FP, _FP, _FP, _FP, c_void_p]),
     "vanerf_weight_products": (c_int, [_FP, _FP, c_int64, c_int, c_int, _FP, c_void_p]),
@@ -115,8 +114,7 @@ _SIGS = {
     "vanerf_layer_rows": (c_int, [c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
     "vanerf_query_order": (c_int, [POINTER(VanerfFrame), _FP, c_int64, _FP, _FP, c_int64, c_void_p]),
     "vanerf_query_order_scratch": (c_int64, [c_int64]),
-    "vanerf_composite": (c_int, [_FP, _FP, _FP, c_int, c_int, c_float, _FP, _FP, _FP, _FP, _FP, c_void_p]),
-    "vanerf_composite_merged": (c_int, [_FP, _FP, c_int, _FP, _FP, c_int, _FP, _FP, c_int, c_float, _FP, _FP, _FP, _FP, _FP, c_void_p]),
+    "vanerf_composite": (c_int, [_FP, _FP, _FP, c_int, _FP, _FP, c_int, _FP, c_int, c_float, _FP, _FP, _FP, _FP, _FP, c_void_p]),
     "vanerf_eval_func": (c_int, [_FP, _FP, _FP, _FP, _FP, _FP, c_int, c_int, c_int, c_float, _FP, _FP, c_void_p]),
     "vanerf_composite_handle": (c_int, [c_void_p, _FP, _FP, _FP, c_int, _FP, _FP, c_int, _FP, c_int, _FP, _FP, _FP, _FP, _FP, c_void_p]),
     "vanerf_composite_backward": (c_int, [c_void_p, _FP, _FP, _FP, c_int, _FP, _FP, c_int, _FP, c_int, _FP, _FP, _FP, _FP, _FP, _FP, _FP, c_void_p]),
@@ -124,14 +122,10 @@ _SIGS = {
     "vanerf_importance_sample": (c_int, [_FP, _FP, _FP, _FP, c_int, c_int, c_int, _FP, _FP, c_void_p]),
     "vanerf_render_pass_scratch": (c_int64, [c_int, c_int, c_int, c_int, c_int]),
     "vanerf_render_pass": (c_int, [c_void_p, POINTER(VanerfFrame), POINTER(VanerfMeshAccel), _FP, c_int, _FP, c_int, POINTER(VanerfPassDesc),
-                                   POINTER(VanerfPassOut), _FP, c_int64, c_void_p]),
-    "vanerf_render_pass_vp": (c_int, [c_void_p, POINTER(VanerfFrame), POINTER(VanerfMeshAccel), _FP, c_int, _FP, c_int, POINTER(VanerfPassDesc),
-                                      POINTER(VanerfPassOut), _FP, c_int64, _FP, c_void_p]),
-    "vanerf_render_pass_views_vp": (c_int, [c_void_p, POINTER(VanerfFrame), POINTER(VanerfMeshAccel), _FP, c_int, _FP, c_int, POINTER(VanerfViewsDesc),
-                                            POINTER(VanerfPassOut), _FP, c_int64, _FP, c_void_p]),
+                                   POINTER(VanerfPassOut), _FP, c_int64, _FP, c_void_p]),
     "vanerf_render_pass_views_scratch": (c_int64, [c_int, c_int, c_int, c_int, c_int, c_int]),
     "vanerf_render_pass_views": (c_int, [c_void_p, POINTER(VanerfFrame), POINTER(VanerfMeshAccel), _FP, c_int, _FP, c_int, POINTER(VanerfViewsDesc),
-                                         POINTER(VanerfPassOut), _FP, c_int64, c_void_p]),
+                                         POINTER(VanerfPassOut), _FP, c_int64, _FP, c_void_p]),
     "vanerf_scatter_add_rows": (c_int, [_FP, _FP, _FP, c_int64, c_int64, c_int, _FP, c_int, c_void_p]),
     "vanerf_bilinear_taps": (c_int, [_FP, c_int64, c_int, c_int, _FP, _FP, c_void_p]),
     "vanerf_scatter_add_rows2": (c_int, [_FP, _FP, _FP, _FP, _FP, _FP, c_int64, c_int64, c_int, _FP, c_int, c_void_p]),

@@ -90,9 +90,6 @@ int layer_slots(int layer, int* k_of_slot, int cap);
 // 32 bits, so the multi-view entry points refuse a launch that reaches this many (the bound vanerf_query_order itself applies).
 constexpr long long VIEWS_MAX_ITEMS = 0x7fffffffLL;
 
-void composite_with_handle(const VanerfWeights* w, const float* rgba, const float* z, const float* msdf, const float* rgba_b, const float* msdf_b,
-                           const int32_t* src, int Sa, int Sb, int R, float* color, float* depth, float* alpha, float* sdf, float* contrib, void* stream);
-
 } // namespace vanerf
 
 struct VanerfWeights {

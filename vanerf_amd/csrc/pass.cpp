@@ -83,7 +83,7 @@ struct Marches {
     int rays_per_view;        // 0: one origin L.cam_pos[3] for every ray; else ray r starts at L.cam_pos[r / rays_per_view][4]
     int grid_nx, grid_ny;     // ray-grid hint of the mesh query (0, 0: none); a pass over V views stacks their rows: (nx, V * ny)
     const float *u, *t_lin_f, *noise_c, *noise_f;
-    const float* vertex_products; // the frame's table for the per-sample launches, or NULL (vanerf_query_samples_vp)
+    const float* vertex_products; // the frame's table for the per-sample launches, or NULL (vanerf_query_samples)
 };
 
 void run_marches(const VanerfWeights* w, const VanerfFrame* frame, const VanerfMeshAccel* accel, const float* verts, int nv, const int32_t* faces, int nf,
@@ -113,7 +113,7 @@ void run_marches(const VanerfWeights* w, const VanerfFrame* frame, const VanerfM
             ok(vanerf_query_order(frame, L.pts, n, L.order, L.order_scratch, L.order_scratch_bytes, stream), "validity partition");
             order = L.order;
         }
-        ok(vanerf_query_samples_vp(w, frame, L.pts, q_sdf, L.q_vis, L.knn, noise, order, valid_raw ? 1 : 0, n, rgba, valid_raw, qw + 1, m.vertex_products, stream),
+        ok(vanerf_query_samples(w, frame, L.pts, q_sdf, L.q_vis, L.knn, noise, order, valid_raw ? 1 : 0, n, rgba, valid_raw, qw + 1, m.vertex_products, stream),
            "per-sample networks");
     };
     if (reuse == 2) { // the networks once per point; eval_func with the coarse draws here, with the fine batch's draws below
@@ -122,7 +122,7 @@ void run_marches(const VanerfWeights* w, const VanerfFrame* frame, const VanerfM
     } else {
         march(o.z, Sc, m.noise_c, L.q_sdf_c, L.rgba_c);
     }
-    composite_with_handle(w, L.rgba_c, o.z, L.q_sdf_c, nullptr, nullptr, nullptr, Sc, 0, R, o.color, o.depth, o.alpha, L.s1, L.contrib, stream);
+    ok(vanerf_composite_handle(w, L.rgba_c, o.z, L.q_sdf_c, Sc, nullptr, nullptr, 0, nullptr, R, o.color, o.depth, o.alpha, L.s1, L.contrib, stream), "composite");
     if (!m.fine) return;
     float* z_fine = o.z_fine ? o.z_fine : L.z_fine;
     float* cf = o.color_fine ? o.color_fine : L.color_f3;
@@ -134,13 +134,13 @@ void run_marches(const VanerfWeights* w, const VanerfFrame* frame, const VanerfM
         march(L.z_new, Sf, nullptr, L.q_sdf_f, L.rgba_f, L.valid_f);
         // noise_f holds one draw per position of the merged order (the reference draws them for the re-evaluated fine batch, src/model.py:1155-1156)
         ok(vanerf_eval_func(L.raw_c, L.valid_c, L.rgba_f, L.valid_f, L.src, m.noise_f, Sc, Sf, R, frame->invalid_sdf, L.rgba_cf, L.rgba_f, stream), "eval_func (fine)");
-        composite_with_handle(w, L.rgba_cf, z_fine, L.q_sdf_c, L.rgba_f, L.q_sdf_f, L.src, Sc, Sf, R, cf, df, af, sf, nullptr, stream);
+        ok(vanerf_composite_handle(w, L.rgba_cf, z_fine, L.q_sdf_c, Sc, L.rgba_f, L.q_sdf_f, Sf, L.src, R, cf, df, af, sf, nullptr, stream), "fine composite");
     } else if (reuse) {
         march(L.z_new, Sf, nullptr, L.q_sdf_f, L.rgba_f);
-        composite_with_handle(w, L.rgba_c, z_fine, L.q_sdf_c, L.rgba_f, L.q_sdf_f, L.src, Sc, Sf, R, cf, df, af, sf, nullptr, stream);
+        ok(vanerf_composite_handle(w, L.rgba_c, z_fine, L.q_sdf_c, Sc, L.rgba_f, L.q_sdf_f, Sf, L.src, R, cf, df, af, sf, nullptr, stream), "fine composite");
     } else {
         march(z_fine, Sc + Sf, m.noise_f, L.q_sdf_f, L.rgba_f);
-        composite_with_handle(w, L.rgba_f, z_fine, L.q_sdf_f, nullptr, nullptr, nullptr, Sc + Sf, 0, R, cf, df, af, sf, nullptr, stream);
+        ok(vanerf_composite_handle(w, L.rgba_f, z_fine, L.q_sdf_f, Sc + Sf, nullptr, nullptr, 0, nullptr, R, cf, df, af, sf, nullptr, stream), "fine composite");
     }
 }
 
@@ -155,6 +155,27 @@ void ok_setup(const char* who, int rc)
     }
 }
 
+// The argument checks the two entry points have in common -- null arguments, coarse output pointers, linspace tables, scratch size -- and the
+// carve of the scratch block.  own(d) holds the checks of what only the entry point's descriptor has and returns the shape of its pass.
+struct Shape {
+    int R, reuse, n_views;
+};
+
+template <class Desc, class Own>
+std::pair<Shape, Layout> checked_layout(const char* who, const VanerfWeights* w, const VanerfFrame* frame, const VanerfMeshAccel* accel, const float* verts,
+                                        const int32_t* faces, const Desc* desc, const VanerfPassOut* out, void* scratch, int64_t scratch_bytes, Own own)
+{
+    if (!w || !frame || !accel || !verts || !faces || !desc || !out || !scratch) throw_error("%s: null argument", who);
+    const Desc& d = *desc;
+    const VanerfPassOut& o = *out;
+    const Shape s = own(d);
+    if (!o.index || !o.hit || !o.z || !o.color || !o.depth || !o.alpha) throw_error("%s: a coarse output pointer is null", who);
+    if (!d.t_lin_c || (d.fine && !d.u && !d.t_lin_f)) throw_error("%s: linspace tables missing", who);
+    const Layout L = carve(scratch, s.R, d.Sc, d.Sf, d.fine != 0, s.reuse, s.n_views);
+    if (scratch_bytes < L.total) throw_error("%s: scratch of %lld bytes, %lld needed (%s_scratch)", who, (long long)scratch_bytes, (long long)L.total, who);
+    return {s, L};
+}
+
 } // namespace
 
 extern "C" int64_t vanerf_render_pass_scratch(int n_rays, int Sc, int Sf, int fine, int reuse_coarse)
@@ -165,29 +186,20 @@ extern "C" int64_t vanerf_render_pass_scratch(int n_rays, int Sc, int Sf, int fi
 
 extern "C" int vanerf_render_pass(const VanerfWeights* w, const VanerfFrame* frame, const VanerfMeshAccel* accel, const float* verts, int nv,
                                   const int32_t* faces, int nf, const VanerfPassDesc* desc, const VanerfPassOut* out, void* scratch,
-                                  int64_t scratch_bytes, void* stream)
-{
-    return vanerf_render_pass_vp(w, frame, accel, verts, nv, faces, nf, desc, out, scratch, scratch_bytes, nullptr, stream);
-}
-
-extern "C" int vanerf_render_pass_vp(const VanerfWeights* w, const VanerfFrame* frame, const VanerfMeshAccel* accel, const float* verts, int nv,
-                                     const int32_t* faces, int nf, const VanerfPassDesc* desc, const VanerfPassOut* out, void* scratch,
-                                     int64_t scratch_bytes, const float* vertex_products, void* stream)
+                                  int64_t scratch_bytes, const float* vertex_products, void* stream)
 {
     return guarded([&] {
-        if (!w || !frame || !accel || !verts || !faces || !desc || !out || !scratch) throw_error("vanerf_render_pass: null argument");
+        const char* const who = "vanerf_render_pass";
+        const auto [shape, L] = checked_layout(who, w, frame, accel, verts, faces, desc, out, scratch, scratch_bytes, [](const VanerfPassDesc& d) {
+            const bool fine = d.fine != 0;
+            if (d.nx <= 0 || d.ny <= 0 || d.Sc < 2 || (fine && d.Sf < 1)) throw_error("vanerf_render_pass: nx=%d ny=%d Sc=%d Sf=%d", d.nx, d.ny, d.Sc, d.Sf);
+            if (fine && d.noise_c && !d.noise_f) throw_error("vanerf_render_pass: noise_c without noise_f");
+            return Shape{d.nx * d.ny, !d.reuse_coarse || !fine ? 0 : d.noise_c ? 2 : 1, 1};
+        });
         const VanerfPassDesc& d = *desc;
         const VanerfPassOut& o = *out;
-        const int R = d.nx * d.ny, Sc = d.Sc, Sf = d.Sf, fine = d.fine != 0;
-        if (d.nx <= 0 || d.ny <= 0 || Sc < 2 || (fine && Sf < 1)) throw_error("vanerf_render_pass: nx=%d ny=%d Sc=%d Sf=%d", d.nx, d.ny, Sc, Sf);
-        if (!o.index || !o.hit || !o.z || !o.color || !o.depth || !o.alpha) throw_error("vanerf_render_pass: a coarse output pointer is null");
-        if (!d.t_lin_c || (fine && !d.u && !d.t_lin_f)) throw_error("vanerf_render_pass: linspace tables missing");
-        if (fine && d.noise_c && !d.noise_f) throw_error("vanerf_render_pass: noise_c without noise_f");
-        const int reuse = !d.reuse_coarse || !fine ? 0 : d.noise_c ? 2 : 1;
-        const Layout L = carve(scratch, R, Sc, Sf, fine, reuse);
-        if (scratch_bytes < L.total) throw_error("vanerf_render_pass: scratch of %lld bytes, %lld needed (vanerf_render_pass_scratch)", (long long)scratch_bytes, (long long)L.total);
+        const int R = shape.R, Sc = d.Sc, Sf = d.Sf, fine = d.fine != 0;
         // a1-a4: pixel grid, rays, bbox clip, coarse depths
-        const char* const who = "vanerf_render_pass";
         if (d.pixels_xy)
             ok_setup(who, vanerf_ray_setup_pixels(d.pixels_xy, R, d.width, d.invK_T, d.RT, d.znear, d.zfar, d.bounds, Sc, d.t_lin_c, d.jitter, o.index, L.rays_d,
                                                   L.cam_pos, L.near, L.far, o.hit, o.z, stream));
@@ -199,7 +211,7 @@ extern "C" int vanerf_render_pass_vp(const VanerfWeights* w, const VanerfFrame* 
                                            d.jitter, o.index, L.rays_d, L.cam_pos, L.near, L.far, o.hit, o.z, stream));
         const bool grid = d.pixels_xy == nullptr;
         run_marches(w, frame, accel, verts, nv, faces, nf,
-                    Marches{who, R, Sc, Sf, fine, reuse, 0, grid ? d.nx : 0, grid ? d.ny : 0, d.u, d.t_lin_f, d.noise_c, d.noise_f, vertex_products}, L, o, stream);
+                    Marches{who, R, Sc, Sf, fine, shape.reuse, 0, grid ? d.nx : 0, grid ? d.ny : 0, d.u, d.t_lin_f, d.noise_c, d.noise_f, vertex_products}, L, o, stream);
     });
 }
 
@@ -215,36 +227,26 @@ extern "C" int64_t vanerf_render_pass_views_scratch(int n_views, int rays_per_vi
 
 extern "C" int vanerf_render_pass_views(const VanerfWeights* w, const VanerfFrame* frame, const VanerfMeshAccel* accel, const float* verts, int nv,
                                         const int32_t* faces, int nf, const VanerfViewsDesc* desc, const VanerfPassOut* out, void* scratch,
-                                        int64_t scratch_bytes, void* stream)
-{
-    return vanerf_render_pass_views_vp(w, frame, accel, verts, nv, faces, nf, desc, out, scratch, scratch_bytes, nullptr, stream);
-}
-
-extern "C" int vanerf_render_pass_views_vp(const VanerfWeights* w, const VanerfFrame* frame, const VanerfMeshAccel* accel, const float* verts, int nv,
-                                           const int32_t* faces, int nf, const VanerfViewsDesc* desc, const VanerfPassOut* out, void* scratch,
-                                           int64_t scratch_bytes, const float* vertex_products, void* stream)
+                                        int64_t scratch_bytes, const float* vertex_products, void* stream)
 {
     return guarded([&] {
         const char* const who = "vanerf_render_pass_views";
-        if (!w || !frame || !accel || !verts || !faces || !desc || !out || !scratch) throw_error("vanerf_render_pass_views: null argument");
+        const auto [shape, L] = checked_layout(who, w, frame, accel, verts, faces, desc, out, scratch, scratch_bytes, [](const VanerfViewsDesc& d) {
+            const int V = d.n_views;
+            const bool fine = d.fine != 0, reuse = d.reuse_coarse && fine;
+            if (V <= 0 || d.nx <= 0 || d.ny <= 0 || d.Sc < 2 || (fine && d.Sf < 1))
+                throw_error("vanerf_render_pass_views: n_views=%d nx=%d ny=%d Sc=%d Sf=%d", V, d.nx, d.ny, d.Sc, d.Sf);
+            if (!d.cams) throw_error("vanerf_render_pass_views: camera table missing");
+            const int S_max = views_s_max(d.Sc, d.Sf, fine, reuse);
+            if ((long long)V * d.nx * d.ny * S_max >= VIEWS_MAX_ITEMS)
+                throw_error("vanerf_render_pass_views: %d views of %d x %d rays at %d samples do not fit a 32-bit sample index", V, d.nx, d.ny, S_max);
+            return Shape{V * d.nx * d.ny, reuse ? 1 : 0, V};
+        });
         const VanerfViewsDesc& d = *desc;
         const VanerfPassOut& o = *out;
         const int V = d.n_views, Sc = d.Sc, Sf = d.Sf, fine = d.fine != 0;
-        if (V <= 0 || d.nx <= 0 || d.ny <= 0 || Sc < 2 || (fine && Sf < 1))
-            throw_error("vanerf_render_pass_views: n_views=%d nx=%d ny=%d Sc=%d Sf=%d", V, d.nx, d.ny, Sc, Sf);
-        if (!d.cams) throw_error("vanerf_render_pass_views: camera table missing");
-        if (!o.index || !o.hit || !o.z || !o.color || !o.depth || !o.alpha) throw_error("vanerf_render_pass_views: a coarse output pointer is null");
-        if (!d.t_lin_c || (fine && !d.u && !d.t_lin_f)) throw_error("vanerf_render_pass_views: linspace tables missing");
-        const int reuse = d.reuse_coarse && fine ? 1 : 0;
-        const int S_max = views_s_max(Sc, Sf, fine, reuse);
-        if ((long long)V * d.nx * d.ny * S_max >= VIEWS_MAX_ITEMS)
-            throw_error("vanerf_render_pass_views: %d views of %d x %d rays at %d samples do not fit a 32-bit sample index", V, d.nx, d.ny, S_max);
-        const int rpv = d.nx * d.ny, R = V * rpv;
-        const Layout L = carve(scratch, R, Sc, Sf, fine, reuse, V);
-        if (scratch_bytes < L.total)
-            throw_error("vanerf_render_pass_views: scratch of %lld bytes, %lld needed (vanerf_render_pass_views_scratch)", (long long)scratch_bytes, (long long)L.total);
         ok_setup(who, vanerf_ray_setup_views(d.cams, V, d.x0, d.y0, d.step_x, d.step_y, d.nx, d.ny, d.width, d.bounds, Sc, d.t_lin_c, d.jitter, o.index, L.rays_d,
                                              L.cam_pos, L.near, L.far, o.hit, o.z, stream));
-        run_marches(w, frame, accel, verts, nv, faces, nf, Marches{who, R, Sc, Sf, fine, reuse, rpv, d.nx, V * d.ny, d.u, d.t_lin_f, nullptr, nullptr, vertex_products}, L, o, stream);
+        run_marches(w, frame, accel, verts, nv, faces, nf, Marches{who, shape.R, Sc, Sf, fine, shape.reuse, d.nx * d.ny, d.nx, V * d.ny, d.u, d.t_lin_f, nullptr, nullptr, vertex_products}, L, o, stream);
     });
 }

@@ -1109,18 +1109,11 @@ void launch_query(const QueryLaunch& L, long long blocks, QueryParams& P, void* 
 
 } // namespace
 
+// vertex_products: the frame's table from vanerf_vertex_products (built with the same handle, after its last update), or NULL.  With the
+// table a bf16x3 handle runs the hoisted kernel on its hoisted stream; without it every handle runs the un-hoisted kernel of its mode.
 extern "C" int vanerf_query_samples(const VanerfWeights* w, const VanerfFrame* frame, const float* pts, const float* query_sdf,
                                     const uint8_t* query_vis, const int32_t* knn_idx, const float* noise, const int32_t* order, int raw, int64_t n,
-                                    float* out, uint8_t* valid, void* queue_word, void* stream)
-{
-    return vanerf_query_samples_vp(w, frame, pts, query_sdf, query_vis, knn_idx, noise, order, raw, n, out, valid, queue_word, nullptr, stream);
-}
-
-// vertex_products: the frame's table from vanerf_vertex_products (built with the same handle, after its last update), or NULL.  With the
-// table a bf16x3 handle runs the hoisted kernel on its hoisted stream; without it the launch is vanerf_query_samples'.
-extern "C" int vanerf_query_samples_vp(const VanerfWeights* w, const VanerfFrame* frame, const float* pts, const float* query_sdf,
-                                       const uint8_t* query_vis, const int32_t* knn_idx, const float* noise, const int32_t* order, int raw, int64_t n,
-                                       float* out, uint8_t* valid, void* queue_word, const float* vertex_products, void* stream)
+                                    float* out, uint8_t* valid, void* queue_word, const float* vertex_products, void* stream)
 {
     return guarded([&] {
         if (n < 0) throw_error("vanerf_query_samples: n = %lld < 0", (long long)n);
@@ -1133,8 +1126,8 @@ extern "C" int vanerf_query_samples_vp(const VanerfWeights* w, const VanerfFrame
         if (f.h0 < 1 || f.w0 < 1 || f.h1 < 1 || f.w1 < 1 || f.ht < 1 || f.wt < 1 || f.hi < 1 || f.wi < 1)
             throw_error("vanerf_query_samples: feature-map sizes must be positive");
         const bool hoist = vertex_products != nullptr;
-        if (hoist && (w->mode != 1 || !w->n_floats_h)) throw_error("vanerf_query_samples_vp: a table of vertex products needs a bf16x3 weight handle");
-        if (hoist && (reinterpret_cast<uintptr_t>(vertex_products) & 15u)) throw_error("vanerf_query_samples_vp: the table must be 16-byte aligned");
+        if (hoist && (w->mode != 1 || !w->n_floats_h)) throw_error("vanerf_query_samples: a table of vertex products needs a bf16x3 weight handle");
+        if (hoist && (reinterpret_cast<uintptr_t>(vertex_products) & 15u)) throw_error("vanerf_query_samples: the table must be 16-byte aligned");
         QueryParams P = query_params(f, hoist ? w->dev + w->n_floats : w->dev, hoist ? w->n_floats_h : w->n_floats, pts, query_sdf, query_vis, knn_idx, raw, n, out);
         P.noise = noise; P.order = order; P.valid = valid; P.short_groups = w->stats; P.vp = vertex_products;
         const QueryLaunch L = w->mode == 1 && hoist ? query_launch<1, false, true>() : w->mode == 1 ? query_launch<1>() : query_launch<0>();

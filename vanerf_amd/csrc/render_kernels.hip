@@ -337,7 +337,23 @@ __global__ __launch_bounds__(IM_BLOCK) void importance_merge_kernel(const float*
 
 static void ray_setup_impl(const int32_t* pixels, const int32_t* row_blocks, int x0, int y0, int step_x, int step_y, int y_block, int nx, int ny, int width, const float* invK_T,
                            const float* RT, float znear, float zfar, const float* bounds, int S, const float* t_lin, const float* jitter,
-                           int64_t* index, float* rays_d, float* cam_pos, float* near, float* far, uint8_t* hit, float* z, void* stream);
+                           int64_t* index, float* rays_d, float* cam_pos, float* near, float* far, uint8_t* hit, float* z, void* stream)
+{
+    if (!invK_T || !RT || !bounds || !t_lin || !index || !rays_d || !cam_pos || !near || !far || !hit || !z)
+        throw_error("vanerf_ray_setup: null argument");
+    if (nx <= 0 || ny <= 0 || step_x <= 0 || step_y <= 0 || y_block <= 0 || S < 2 || width <= 0)
+        throw_error("vanerf_ray_setup: bad grid (nx=%d ny=%d step=%d,%d S=%d)", nx, ny, step_x, step_y, S);
+    RayParams P;
+    P.x0 = x0; P.y0 = y0; P.step_x = step_x; P.step_y = step_y; P.y_block = y_block; P.nx = nx; P.ny = ny; P.width = width; P.pixels = pixels; P.row_blocks = row_blocks;
+    std::copy_n(invK_T, 9, P.invK_T);
+    std::copy_n(RT, 12, P.RT);
+    std::copy_n(bounds, 6, P.bounds);
+    P.znear = znear; P.zfar = zfar; P.S = S; P.t_lin = t_lin; P.jitter = jitter;
+    P.index = index; P.rays_d = rays_d; P.cam_pos = cam_pos; P.near = near; P.far = far; P.hit = hit; P.z = z;
+    const int R = nx * ny;
+    hipLaunchKernelGGL(ray_setup_kernel, dim3((R + 255) / 256), dim3(256), 0, (hipStream_t)stream, P);
+    HIP_CHECK(hipGetLastError());
+}
 
 extern "C" int vanerf_ray_setup(int x0, int y0, int step_x, int step_y, int y_block, int nx, int ny, int width, const float* invK_T, const float* RT,
                                 float znear, float zfar, const float* bounds, int S, const float* t_lin, const float* jitter,
@@ -373,28 +389,6 @@ extern "C" int vanerf_ray_setup_pixels(const int32_t* pixels_xy, int n_rays, int
         ray_setup_impl(pixels_xy, nullptr, 0, 0, 1, 1, 1, n_rays, 1, width, invK_T, RT, znear, zfar, bounds, S, t_lin, jitter, index, rays_d, cam_pos,
                        near, far, hit, z, stream);
     });
-}
-
-static void ray_setup_impl(const int32_t* pixels, const int32_t* row_blocks, int x0, int y0, int step_x, int step_y, int y_block, int nx, int ny, int width, const float* invK_T,
-                           const float* RT, float znear, float zfar, const float* bounds, int S, const float* t_lin, const float* jitter,
-                           int64_t* index, float* rays_d, float* cam_pos, float* near, float* far, uint8_t* hit, float* z, void* stream)
-{
-    {
-        if (!invK_T || !RT || !bounds || !t_lin || !index || !rays_d || !cam_pos || !near || !far || !hit || !z)
-            throw_error("vanerf_ray_setup: null argument");
-        if (nx <= 0 || ny <= 0 || step_x <= 0 || step_y <= 0 || y_block <= 0 || S < 2 || width <= 0)
-            throw_error("vanerf_ray_setup: bad grid (nx=%d ny=%d step=%d,%d S=%d)", nx, ny, step_x, step_y, S);
-        RayParams P;
-        P.x0 = x0; P.y0 = y0; P.step_x = step_x; P.step_y = step_y; P.y_block = y_block; P.nx = nx; P.ny = ny; P.width = width; P.pixels = pixels; P.row_blocks = row_blocks;
-        std::copy_n(invK_T, 9, P.invK_T);
-        std::copy_n(RT, 12, P.RT);
-        std::copy_n(bounds, 6, P.bounds);
-        P.znear = znear; P.zfar = zfar; P.S = S; P.t_lin = t_lin; P.jitter = jitter;
-        P.index = index; P.rays_d = rays_d; P.cam_pos = cam_pos; P.near = near; P.far = far; P.hit = hit; P.z = z;
-        const int R = nx * ny;
-        hipLaunchKernelGGL(ray_setup_kernel, dim3((R + 255) / 256), dim3(256), 0, (hipStream_t)stream, P);
-        HIP_CHECK(hipGetLastError());
-    }
 }
 
 extern "C" int vanerf_ray_setup_views(const float* cams, int n_views, int x0, int y0, int step_x, int step_y, int nx, int ny, int width,
@@ -446,7 +440,7 @@ extern "C" int vanerf_sample_points_views(const float* rays_d, const float* cam_
 // (one thread per ray read 64 different cache lines per load instruction: 9.8 GB of line traffic for 0.6 GB of data, 1.33 ms).
 // The transmittance T_i = prod_{j<i} (1 - c_j) becomes a per-lane product followed by a wave scan, so its rounding differs from the
 // strictly sequential product in the last bits (~1e-7 relative; the reference's th.cumprod order is an implementation detail too).
-// Deterministic; identical arithmetic for vanerf_composite and vanerf_composite_merged on the same samples.
+// Deterministic; identical arithmetic for one table and for the merged order of two tables on the same samples.
 template <int SPL>
 __global__ __launch_bounds__(256) void composite_wave_kernel(const float* __restrict__ rgba, const float* __restrict__ z, const float* __restrict__ msdf,
                                                              const float* __restrict__ rgba_b, const float* __restrict__ msdf_b,
@@ -549,10 +543,11 @@ static void launch_composite(const float* rgba, const float* z, const float* msd
 // sdf = mask sdf_pred + (1 - mask) invalid_sdf -- the arithmetic of query_kernel's own epilogue, so the same bits.  With per-sample noise (training) the
 // networks are evaluated once per point (raw) and this runs once per set of draws: src == NULL: entry i of table a with noise[i]; otherwise position p of
 // a ray's merged order carries noise[r][p] and names its entry (src >= 0: table a, < 0: entry ~src of table b); every entry is written once
-// (rgba_a / rgba_b may be the raw tables themselves).
-__global__ __launch_bounds__(256) void eval_func_kernel(const float* __restrict__ raw_a, const uint8_t* __restrict__ valid_a, const float* __restrict__ raw_b,
+// (rgba_a / rgba_b may be the raw tables themselves: the four table pointers carry no __restrict__, and a thread reads its entry whole before it
+// writes it.  The flags, the origin map and the draws are never written here, so theirs stands).
+__global__ __launch_bounds__(256) void eval_func_kernel(const float* raw_a, const uint8_t* __restrict__ valid_a, const float* raw_b,
                                                         const uint8_t* __restrict__ valid_b, const int32_t* __restrict__ src, const float* __restrict__ noise,
-                                                        int Sa, int Sb, long long n, float invalid_sdf, float* __restrict__ rgba_a, float* __restrict__ rgba_b)
+                                                        int Sa, int Sb, long long n, float invalid_sdf, float* rgba_a, float* rgba_b)
 {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
@@ -727,46 +722,37 @@ extern "C" int vanerf_composite_backward(const VanerfWeights* w, const float* rg
     });
 }
 
-// pass.cpp's composites: sigmoid_beta from the weight handle's device copy (see vanerf_weights_update); rgba_b == null: one table of S = Sa samples
-void vanerf::composite_with_handle(const VanerfWeights* w, const float* rgba, const float* z, const float* msdf, const float* rgba_b, const float* msdf_b,
-                                   const int32_t* src, int Sa, int Sb, int R, float* color, float* depth, float* alpha, float* sdf, float* contrib,
-                                   void* stream)
+// vanerf_composite and vanerf_composite_handle behind one set of checks: sigmoid_beta by value, or read on the device when beta_dev is given.
+// rgba_n == NULL composites the Sa samples of one table, otherwise the merged order (src) of two tables.
+static void composite_checked(const char* who, const float* rgba, const float* z, const float* mesh_sdf, int Sa, const float* rgba_n, const float* mesh_sdf_n, int Sn,
+                              const int32_t* src, int R, float beta, const float* beta_dev, float* color, float* depth, float* alpha, float* sdf,
+                              float* contrib, void* stream)
 {
-    launch_composite(rgba, z, msdf, rgba_b, msdf_b, src, Sa, Sb, R, Sa + Sb, w->beta, w->dev_beta, color, depth, alpha, sdf, contrib, stream);
+    if (!rgba || !z || !mesh_sdf || !color || !depth || !alpha || !sdf) throw_error("%s: null argument", who);
+    if (rgba_n && (!mesh_sdf_n || !src || Sn <= 0)) throw_error("%s: the second table needs mesh_sdf_n, src and Sn > 0", who);
+    if (rgba_n && Sa <= 0) throw_error("%s: Sc=%d Sn=%d", who, Sa, Sn);
+    const int Sb = rgba_n ? Sn : 0;
+    launch_composite(rgba, z, mesh_sdf, rgba_n, rgba_n ? mesh_sdf_n : nullptr, rgba_n ? src : nullptr, Sa, Sb, R, Sa + Sb, beta, beta_dev, color, depth, alpha, sdf,
+                     contrib, stream);
 }
 
-extern "C" int vanerf_composite(const float* rgba, const float* z, const float* mesh_sdf, int R, int S, float beta,
-                                float* color, float* depth, float* alpha, float* sdf, float* contrib, void* stream)
+extern "C" int vanerf_composite(const float* rgba, const float* z, const float* mesh_sdf, int Sa, const float* rgba_n, const float* mesh_sdf_n, int Sn,
+                                const int32_t* src, int R, float beta, float* color, float* depth, float* alpha, float* sdf, float* contrib, void* stream)
 {
     return guarded([&] {
-        if (!rgba || !z || !mesh_sdf || !color || !depth || !alpha || !sdf) throw_error("vanerf_composite: null argument");
-        launch_composite(rgba, z, mesh_sdf, nullptr, nullptr, nullptr, S, 0, R, S, beta, nullptr, color, depth, alpha, sdf, contrib, stream);
+        composite_checked("vanerf_composite", rgba, z, mesh_sdf, Sa, rgba_n, mesh_sdf_n, Sn, src, R, beta, nullptr, color, depth, alpha, sdf, contrib, stream);
     });
 }
 
-// Either composite with sigmoid_beta taken from a weight handle's device copy (what vanerf_render_pass does): rgba_n == NULL composites the
-// Sa samples of one table, otherwise the merged order of two tables as vanerf_composite_merged.
+// ... with sigmoid_beta taken from a weight handle's device copy (what vanerf_render_pass does)
 extern "C" int vanerf_composite_handle(const VanerfWeights* w, const float* rgba, const float* z, const float* mesh_sdf, int Sa, const float* rgba_n,
                                        const float* mesh_sdf_n, int Sn, const int32_t* src, int R, float* color, float* depth, float* alpha,
                                        float* sdf, float* contrib, void* stream)
 {
     return guarded([&] {
-        if (!w || !rgba || !z || !mesh_sdf || !color || !depth || !alpha || !sdf) throw_error("vanerf_composite_handle: null argument");
-        if (rgba_n && (!mesh_sdf_n || !src || Sn <= 0)) throw_error("vanerf_composite_handle: the second table needs mesh_sdf_n, src and Sn > 0");
-        vanerf::composite_with_handle(w, rgba, z, mesh_sdf, rgba_n, rgba_n ? mesh_sdf_n : nullptr, rgba_n ? src : nullptr, Sa, rgba_n ? Sn : 0, R, color,
-                                      depth, alpha, sdf, contrib, stream);
-    });
-}
-
-extern "C" int vanerf_composite_merged(const float* rgba_c, const float* mesh_sdf_c, int Sc, const float* rgba_n, const float* mesh_sdf_n,
-                                       int Sn, const int32_t* src, const float* z_fine, int R, float beta, float* color, float* depth,
-                                       float* alpha, float* sdf, float* contrib, void* stream)
-{
-    return guarded([&] {
-        if (!rgba_c || !mesh_sdf_c || !rgba_n || !mesh_sdf_n || !src || !z_fine || !color || !depth || !alpha || !sdf)
-            throw_error("vanerf_composite_merged: null argument");
-        if (Sc <= 0 || Sn <= 0) throw_error("vanerf_composite_merged: Sc=%d Sn=%d", Sc, Sn);
-        launch_composite(rgba_c, z_fine, mesh_sdf_c, rgba_n, mesh_sdf_n, src, Sc, Sn, R, Sc + Sn, beta, nullptr, color, depth, alpha, sdf, contrib, stream);
+        if (!w) throw_error("vanerf_composite_handle: null argument");
+        composite_checked("vanerf_composite_handle", rgba, z, mesh_sdf, Sa, rgba_n, mesh_sdf_n, Sn, src, R, w->beta, w->dev_beta, color, depth, alpha, sdf, contrib,
+                          stream);
     });
 }
 

@@ -6,6 +6,7 @@ TexVisFusion per-frame conv stack).  Every per-ray / per-sample operation runs i
 There is no CPU or eager fallback: every entry point requires CUDA(ROCm) tensors.
 """
 import ctypes
+import dataclasses
 import os
 import weakref
 from ctypes import byref, c_float, c_int64, c_uint, c_void_p
@@ -281,6 +282,16 @@ class MeshAccel:
         return self.tables[off:off + n].view(dtype).view(*shape)
 
 
+@dataclasses.dataclass(eq=False)
+class _VertexProducts:
+    """FrameData's table of per-vertex products for one weight handle."""
+    weights: weakref.ref         # the PackedWeights the table belongs to
+    table: torch.Tensor = None
+    version: int = None          # weights.version at the build
+    stream: torch.cuda.Stream = None  # the stream of the build ...
+    event: torch.cuda.Event = None    # ... and the event recorded behind it
+
+
 class FrameData:
     """Everything the per-sample kernel needs about one source frame, resident in HBM (struct VanerfFrame)."""
 
@@ -355,7 +366,7 @@ class FrameData:
         c.pe_scale = float(sp_args.get("scale", 1.0))
         c.pe_inv_2sigma2 = 1.0 / (2.0 * float(sp_args.get("sigma", 0.1)) ** 2)
         self.c = c
-        self._vertex_products = []  # [weakref to the PackedWeights, its version at the build, table, build stream, event after the build]
+        self._vertex_products = []  # one _VertexProducts per weight handle that is still alive
 
     def vertex_products(self, weights):
         """The frame's table of per-vertex products for a bf16x3 handle (vanerf_vertex_products): the share of three first layers that depends
@@ -364,31 +375,28 @@ class FrameData:
         geometry weights -- one launch on the current stream, kept per handle and rebuilt when PackedWeights.update changed the weights."""
         if weights.mode != 1 or not vertex_products_enabled():
             return None
-        self._vertex_products = [e for e in self._vertex_products if e[0]() is not None]
+        self._vertex_products = [e for e in self._vertex_products if e.weights() is not None]
         stream = torch.cuda.current_stream()
         for e in self._vertex_products:
-            if e[0]() is weights:
-                if e[1] != weights.version:
+            if e.weights() is weights:
+                if e.version != weights.version:
                     self._build_vertex_products(weights, e)
-                elif e[3] != stream:  # built on another stream: ordered behind the build, and the allocator told about the reader
-                    stream.wait_event(e[4])
-                    e[2].record_stream(stream)
-                return e[2]
-        n = int(lib.vanerf_vertex_products(None, None, None, 0, None))
-        e = [weakref.ref(weights), None, torch.empty(n, dtype=torch.float32, device=self.vfeat0.device), None, None]
+                elif e.stream != stream:  # built on another stream: ordered behind the build, and the allocator told about the reader
+                    stream.wait_event(e.event)
+                    e.table.record_stream(stream)
+                return e.table
+        e = _VertexProducts(weakref.ref(weights))
         self._build_vertex_products(weights, e)
         self._vertex_products.append(e)
-        return e[2]
+        return e.table
 
     def _build_vertex_products(self, weights, e):
         stream = torch.cuda.current_stream()
-        if e[3] is not None and e[3] != stream:
-            e[2].record_stream(stream)
-        rc = lib.vanerf_vertex_products(weights.handle, byref(self.c), _ptr(e[2], torch.float32), e[2].numel(), _stream())
-        if rc != 0:
-            check(rc)
-        e[1], e[3], e[4] = weights.version, stream, torch.cuda.Event()
-        e[4].record(stream)
+        if e.stream is not None and e.stream != stream:
+            e.table.record_stream(stream)
+        e.table = build_vertex_products(weights, self, e.table)
+        e.version, e.stream, e.event = weights.version, stream, torch.cuda.Event()
+        e.event.record(stream)
 
 
 # What the table of per-vertex products holds, in the reference's own terms (vanerf_amd/csrc/layer_spec.h, vertex_products.hip).  Columns of the
@@ -439,13 +447,12 @@ def vertex_products_unpack(table):
     return out, pad
 
 
-def build_vertex_products(weights, frame):
-    """A fresh table for (weights, frame) on the current stream (vanerf_vertex_products); FrameData.vertex_products keeps one per handle."""
-    n = int(lib.vanerf_vertex_products(None, None, None, 0, None))
-    table = torch.empty(n, dtype=torch.float32, device=frame.vfeat0.device)
-    rc = lib.vanerf_vertex_products(weights.handle, byref(frame.c), _ptr(table, torch.float32), n, _stream())
-    if rc != 0:
-        check(rc)
+def build_vertex_products(weights, frame, table=None):
+    """The table for (weights, frame), built on the current stream (vanerf_vertex_products) into `table` or a fresh one; FrameData.vertex_products
+    keeps one per handle."""
+    if table is None:
+        table = torch.empty(int(lib.vanerf_vertex_products(None, None, None, 0, None)), dtype=torch.float32, device=frame.vfeat0.device)
+    check(lib.vanerf_vertex_products(weights.handle, byref(frame.c), _ptr(table, torch.float32), table.numel(), _stream()))
     return table
 
 
@@ -545,27 +552,34 @@ def query_samples(weights, frame, pts, query_sdf, query_vis, knn_idx, noise=None
     valid = torch.empty(n, dtype=torch.uint8, device=pts.device) if want_valid else None
     if order is not None and order.shape != (n,):
         raise ValueError("order must hold one index per sample")
-    check(lib.vanerf_query_samples_vp(weights.handle, byref(frame.c), _ptr(pts, torch.float32), _ptr(query_sdf, torch.float32),
-                                      _ptr(query_vis, torch.uint8), _ptr(knn_idx, torch.int32), _ptr(noise, torch.float32), _ptr(order, torch.int32),
-                                      int(bool(raw)), n, _ptr(out), _ptr(valid), _ptr(_queue_word(pts.device)), _ptr(vp, torch.float32), _stream()))
+    check(lib.vanerf_query_samples(weights.handle, byref(frame.c), _ptr(pts, torch.float32), _ptr(query_sdf, torch.float32),
+                                   _ptr(query_vis, torch.uint8), _ptr(knn_idx, torch.int32), _ptr(noise, torch.float32), _ptr(order, torch.int32),
+                                   int(bool(raw)), n, _ptr(out), _ptr(valid), _ptr(_queue_word(pts.device)), _ptr(vp, torch.float32), _stream()))
     return (out, valid) if want_valid else out
+
+
+def _composite(rgba, z, mesh_sdf, rgba_n, sdf_n, src, beta, want_contrib):
+    """Either composite: one table of S samples per ray (rgba_n None), or [table | rgba_n table] in the merged order src.  beta: a number
+    (vanerf_composite), or the PackedWeights whose device copy of sigmoid_beta the kernel reads (vanerf_composite_handle: no host value involved)."""
+    R, S = z.shape
+    Sn = 0 if rgba_n is None else sdf_n.shape[1]
+    dev, f32 = z.device, torch.float32
+    color = torch.empty(R, 3, dtype=f32, device=dev)
+    depth, alpha, sdf = (torch.empty(R, dtype=f32, device=dev) for _ in range(3))
+    contrib = torch.empty(R, S, dtype=f32, device=dev) if want_contrib else None
+    tables = (_ptr(rgba, f32), _ptr(z, f32), _ptr(mesh_sdf, f32), S - Sn, _ptr(rgba_n, f32), _ptr(sdf_n, f32), Sn, _ptr(src, torch.int32), R)
+    outs = (_ptr(color), _ptr(depth), _ptr(alpha), _ptr(sdf), _ptr(contrib), _stream())
+    if isinstance(beta, PackedWeights):
+        check(lib.vanerf_composite_handle(beta.handle, *tables, *outs))
+    else:
+        check(lib.vanerf_composite(*tables, float(beta), *outs))
+    return color, depth, alpha, contrib, sdf
 
 
 def composite(rgba, z, mesh_sdf, beta, want_contrib=True):
     """sdf_activation + rgba2out (src/model.py:879-882, 1464-1494).  rgba (R,S,5), z (R,S), mesh_sdf (R,S).
     beta: a number, or the PackedWeights whose device copy of sigmoid_beta the kernel reads (no host value involved)."""
-    R, S = z.shape
-    dev = z.device
-    color = torch.empty(R, 3, dtype=torch.float32, device=dev)
-    depth, alpha, sdf = (torch.empty(R, dtype=torch.float32, device=dev) for _ in range(3))
-    contrib = torch.empty(R, S, dtype=torch.float32, device=dev) if want_contrib else None
-    if isinstance(beta, PackedWeights):
-        check(lib.vanerf_composite_handle(beta.handle, _ptr(rgba, torch.float32), _ptr(z, torch.float32), _ptr(mesh_sdf, torch.float32), S, None, None, 0,
-                                          None, R, _ptr(color), _ptr(depth), _ptr(alpha), _ptr(sdf), _ptr(contrib), _stream()))
-    else:
-        check(lib.vanerf_composite(_ptr(rgba, torch.float32), _ptr(z, torch.float32), _ptr(mesh_sdf, torch.float32), R, S, float(beta),
-                                   _ptr(color), _ptr(depth), _ptr(alpha), _ptr(sdf), _ptr(contrib), _stream()))
-    return color, depth, alpha, contrib, sdf
+    return _composite(rgba, z, mesh_sdf, None, None, None, beta, want_contrib)
 
 
 def composite_backward(weights, rgba, z, mesh_sdf, g_color=None, g_depth=None, g_alpha=None, g_sdf=None, rgba_n=None, sdf_n=None, src=None):
@@ -591,23 +605,9 @@ def composite_backward(weights, rgba, z, mesh_sdf, g_color=None, g_depth=None, g
 
 
 def composite_merged(rgba_c, sdf_c, rgba_n, sdf_n, src, z_fine, beta, want_contrib=False):
-    """Fine composite over [coarse samples | new importance samples] in merged depth order (vanerf_composite_merged)."""
-    R, S = z_fine.shape
-    Sc, Sn = sdf_c.shape[1], sdf_n.shape[1]
-    assert Sc + Sn == S and src.shape == (R, S)
-    dev = z_fine.device
-    color = torch.empty(R, 3, dtype=torch.float32, device=dev)
-    depth, alpha, sdf = (torch.empty(R, dtype=torch.float32, device=dev) for _ in range(3))
-    contrib = torch.empty(R, S, dtype=torch.float32, device=dev) if want_contrib else None
-    if isinstance(beta, PackedWeights):
-        check(lib.vanerf_composite_handle(beta.handle, _ptr(rgba_c, torch.float32), _ptr(z_fine, torch.float32), _ptr(sdf_c, torch.float32), Sc,
-                                          _ptr(rgba_n, torch.float32), _ptr(sdf_n, torch.float32), Sn, _ptr(src, torch.int32), R,
-                                          _ptr(color), _ptr(depth), _ptr(alpha), _ptr(sdf), _ptr(contrib), _stream()))
-    else:
-        check(lib.vanerf_composite_merged(_ptr(rgba_c, torch.float32), _ptr(sdf_c, torch.float32), Sc, _ptr(rgba_n, torch.float32),
-                                          _ptr(sdf_n, torch.float32), Sn, _ptr(src, torch.int32), _ptr(z_fine, torch.float32), R, float(beta),
-                                          _ptr(color), _ptr(depth), _ptr(alpha), _ptr(sdf), _ptr(contrib), _stream()))
-    return color, depth, alpha, contrib, sdf
+    """Fine composite over [coarse samples | new importance samples] in merged depth order (the two-table form of vanerf_composite)."""
+    assert sdf_c.shape[1] + sdf_n.shape[1] == z_fine.shape[1] and src.shape == z_fine.shape
+    return _composite(rgba_c, z_fine, sdf_c, rgba_n, sdf_n, src, beta, want_contrib)
 
 
 _HOST = {}
@@ -698,14 +698,22 @@ def ray_bbox(bounds, orig, dirs):
     return near, far, hit
 
 
+def _camera_floats(cam):
+    """A target-camera dict -> invK_T (9 floats), RT (12), [znear, zfar] as the ray kernels get them: host_copy, th.inverse on the host
+    (th.inverse(...).transpose(1, 2), model.py:1208), Python floats.  The one place these numbers are produced: the single-view calls pass them
+    by value and camera_table uploads them, so a view's rays have the same bits either way."""
+    K, RT = host_copy(cam["K"]), host_copy(cam["RT"])
+    return (torch.inverse(K[:, :3, :3]).transpose(1, 2)[0].reshape(-1).tolist(), RT[0, :3, :4].reshape(-1).tolist(),
+            [float(cam["znear"]), float(cam["zfar"])])
+
+
 def ray_setup(cam_tar, bounds, x0, y0, step, nx, ny, S, jitter=None, device=None, y_step=None, pixels=None, y_block=1, row_blocks=None):
     """Pixel grid + rays + bbox clip + coarse depths (src/model.py:1191-1238, 1496-1570).
     pixels: optional explicit (R,2) int32 device tensor of (x, y) (training patches); then nx*ny must equal R.
     y_step, y_block: rows are y0 + (iy // y_block) * y_step + (iy % y_block) * step (multi-GPU shards: blocks of y_block rows).
     row_blocks: optional (ny // y_block,) int32 device tensor, the first row of every block (shards dealt by cost: parallel.deal_blocks)."""
     dev = device or bounds.device
-    K, RT = host_copy(cam_tar["K"]), host_copy(cam_tar["RT"])
-    inv_K_T = torch.inverse(K[:, :3, :3]).transpose(1, 2)[0].contiguous()  # th.inverse(...).transpose(1, 2), model.py:1208
+    inv_K_T, RT, (znear, zfar) = _camera_floats(cam_tar)
     R = nx * ny
     index = torch.empty(R, dtype=torch.int64, device=dev)
     rays_d = torch.empty(R, 3, dtype=torch.float32, device=dev)
@@ -714,8 +722,7 @@ def ray_setup(cam_tar, bounds, x0, y0, step, nx, ny, S, jitter=None, device=None
     hit = torch.empty(R, dtype=torch.uint8, device=dev)
     z = torch.empty(R, S, dtype=torch.float32, device=dev)
     t_lin = _t_lin(S, dev)
-    cam_args = (_farr(inv_K_T.reshape(-1).tolist(), 9), _farr(RT[0, :3, :4].reshape(-1).tolist(), 12), float(cam_tar["znear"]),
-                float(cam_tar["zfar"]), _farr(host_copy(bounds).reshape(-1).tolist(), 6), int(S), _ptr(t_lin), _ptr(jitter, torch.float32),
+    cam_args = (_farr(inv_K_T, 9), _farr(RT, 12), znear, zfar, _farr(host_copy(bounds).reshape(-1).tolist(), 6), int(S), _ptr(t_lin), _ptr(jitter, torch.float32),
                 _ptr(index), _ptr(rays_d), _ptr(cam_pos), _ptr(near), _ptr(far), _ptr(hit), _ptr(z), _stream())
     if pixels is not None:
         assert pixels.shape == (R, 2)
@@ -732,20 +739,15 @@ CAM_FLOATS = 24  # a row of the camera table of the *_views entry points: invK_T
 
 
 def camera_table(cam_tars, dev):
-    """(V, 24) device table of the target cameras for vanerf_ray_setup_views / vanerf_render_pass_views.  Every number is produced the way the
-    single-view path produces the values it passes to the kernels -- host_copy, th.inverse on the host per matrix, Python float -> fp32 -- so a
-    view's rays are bit-identical to ray_setup's; one asynchronous host -> device copy for all of them (_staged_upload)."""
+    """(V, 24) device table of the target cameras for vanerf_ray_setup_views / vanerf_render_pass_views.  Every number comes from _camera_floats,
+    as the values the single-view path passes to the kernels do (Python float -> fp32 on both sides), so a view's rays are bit-identical to
+    ray_setup's; one asynchronous host -> device copy for all of them (_staged_upload)."""
     if not cam_tars:
         raise ValueError("at least one target camera")
     size = lambda c: (int(c["width"]), int(c.get("height", 0)))
     if any(size(c) != size(cam_tars[0]) for c in cam_tars):
         raise ValueError("the views of one pass share one width / height")
-    rows = []
-    for cam in cam_tars:
-        K, RT = host_copy(cam["K"]), host_copy(cam["RT"])
-        rows.append(torch.inverse(K[:, :3, :3]).transpose(1, 2)[0].reshape(-1).tolist() + RT[0, :3, :4].reshape(-1).tolist()
-                    + [float(cam["znear"]), float(cam["zfar"]), 0.0])
-    table = torch.tensor(rows, dtype=torch.float32)
+    table = torch.tensor([sum(_camera_floats(cam), []) + [0.0] for cam in cam_tars], dtype=torch.float32)
     assert table.shape == (len(cam_tars), CAM_FLOATS)
     if torch.device(dev).type != "cuda":
         return table.to(dev)
@@ -931,6 +933,20 @@ def render_pass(weights, frame, cam_tar, bounds, x0, y0, step, nx, ny, sample_pe
     return out
 
 
+def _pass_outputs(lead, Sc, Sf, fine, dev):
+    """The output tensors of a one-call pass for a leading shape -- (R,) or (V, R) -- and the VanerfPassOut that points at them."""
+    def new(*tail, dtype=torch.float32):
+        return torch.empty(*lead, *tail, dtype=dtype, device=dev)
+
+    out = {"index": new(dtype=torch.int64), "hit": new(dtype=torch.uint8), "z": new(Sc), "color": new(3), "depth": new(), "alpha": new()}
+    if fine:
+        out.update({"color_fine": new(3), "depth_fine": new(), "alpha_fine": new(), "sdf": new(), "z_fine": new(Sc + Sf)})
+    o = VanerfPassOut()
+    for k, _ in VanerfPassOut._fields_:
+        setattr(o, k, _ptr(out.get(k)))
+    return out, o
+
+
 def render_pass_c(weights, frame, cam_tar, bounds, x0, y0, step, nx, ny, sample_per_ray_c=64, sample_per_ray_f=64, fine=True, jitter=None, u=None,
                   noise_std=0.0, generator=None, y_step=None, reuse_coarse=True, pixels=None, y_block=1, noise_draws=None, row_blocks=None):
     """The same pass through the single C entry point vanerf_render_pass (include/vanerf_hip.h): one ctypes call enqueues every kernel of
@@ -938,15 +954,13 @@ def render_pass_c(weights, frame, cam_tar, bounds, x0, y0, step, nx, ny, sample_
     temporaries in one scratch block.  This is what a non-Python host binds; the model's eval / no-grad passes go through it too."""
     Sc, Sf, R = int(sample_per_ray_c), int(sample_per_ray_f), nx * ny
     dev = frame.verts3.device
-    K, RT = host_copy(cam_tar["K"]), host_copy(cam_tar["RT"])
+    inv_K_T, RT, (znear, zfar) = _camera_floats(cam_tar)
     d = VanerfPassDesc()
     d.x0, d.y0, d.step_x, d.step_y, d.y_block, d.nx, d.ny = int(x0), int(y0), int(step), int(y_step or step), int(y_block), int(nx), int(ny)
     d.pixels_xy = _ptr(pixels, torch.int32)
     d.row_blocks = _ptr(row_blocks, torch.int32)
     d.width = int(cam_tar["width"])
-    d.invK_T = _farr(torch.inverse(K[:, :3, :3]).transpose(1, 2)[0].reshape(-1).tolist(), 9)
-    d.RT = _farr(RT[0, :3, :4].reshape(-1).tolist(), 12)
-    d.znear, d.zfar = float(cam_tar["znear"]), float(cam_tar["zfar"])
+    d.invK_T, d.RT, d.znear, d.zfar = _farr(inv_K_T, 9), _farr(RT, 12), znear, zfar
     d.bounds = _farr(host_copy(bounds).reshape(-1).tolist(), 6)
     d.Sc, d.Sf, d.fine = Sc, Sf, int(bool(fine))
     noise = None
@@ -959,22 +973,12 @@ def render_pass_c(weights, frame, cam_tar, bounds, x0, y0, step, nx, ny, sample_
     d.t_lin_c, d.t_lin_f = _ptr(t_c), _ptr(t_f)
     d.jitter, d.u = _ptr(jitter, torch.float32), _ptr(u, torch.float32)
     d.noise_c, d.noise_f = (_ptr(noise[0]), _ptr(noise[1])) if noise is not None else (None, None)
-    f32 = torch.float32
-    out = {"index": torch.empty(R, dtype=torch.int64, device=dev), "hit": torch.empty(R, dtype=torch.uint8, device=dev),
-           "z": torch.empty(R, Sc, dtype=f32, device=dev), "color": torch.empty(R, 3, dtype=f32, device=dev),
-           "depth": torch.empty(R, dtype=f32, device=dev), "alpha": torch.empty(R, dtype=f32, device=dev)}
-    if fine:
-        out.update({"color_fine": torch.empty(R, 3, dtype=f32, device=dev), "depth_fine": torch.empty(R, dtype=f32, device=dev),
-                    "alpha_fine": torch.empty(R, dtype=f32, device=dev), "sdf": torch.empty(R, dtype=f32, device=dev),
-                    "z_fine": torch.empty(R, Sc + Sf, dtype=f32, device=dev)})
-    o = VanerfPassOut()
-    for k in ("index", "hit", "z", "color", "depth", "alpha", "color_fine", "depth_fine", "alpha_fine", "sdf", "z_fine"):
-        setattr(o, k, _ptr(out.get(k)))
+    out, o = _pass_outputs((R,), Sc, Sf, fine, dev)
     nbytes = int(lib.vanerf_render_pass_scratch(R, Sc, Sf, d.fine, 2 if d.reuse_coarse and noise is not None else d.reuse_coarse))
     scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    check(lib.vanerf_render_pass_vp(weights.handle, byref(frame.c), byref(frame.accel.c), _ptr(frame.verts3, f32), frame.verts3.shape[0],
-                                    _ptr(frame.faces, torch.int32), frame.faces.shape[0], byref(d), byref(o), _ptr(scratch), nbytes,
-                                    _ptr(frame.vertex_products(weights), f32), _stream()))
+    check(lib.vanerf_render_pass(weights.handle, byref(frame.c), byref(frame.accel.c), _ptr(frame.verts3, torch.float32), frame.verts3.shape[0],
+                                 _ptr(frame.faces, torch.int32), frame.faces.shape[0], byref(d), byref(o), _ptr(scratch), nbytes,
+                                 _ptr(frame.vertex_products(weights), torch.float32), _stream()))
     return out
 
 
@@ -1005,25 +1009,15 @@ def render_pass_views(weights, frame, cam_tars, bounds, x0, y0, step, nx, ny, sa
     if jitter is not None and jitter.numel() != V * R * Sc or u is not None and u.numel() != V * R * Sf:
         raise ValueError("jitter / u: one draw per sample of every view, (V*R, Sc) / (V*R, Sf)")
     d.jitter, d.u = _ptr(jitter, torch.float32), _ptr(u, torch.float32)
-    f32 = torch.float32
-    out = {"index": torch.empty(V, R, dtype=torch.int64, device=dev), "hit": torch.empty(V, R, dtype=torch.uint8, device=dev),
-           "z": torch.empty(V, R, Sc, dtype=f32, device=dev), "color": torch.empty(V, R, 3, dtype=f32, device=dev),
-           "depth": torch.empty(V, R, dtype=f32, device=dev), "alpha": torch.empty(V, R, dtype=f32, device=dev)}
-    if fine:
-        out.update({"color_fine": torch.empty(V, R, 3, dtype=f32, device=dev), "depth_fine": torch.empty(V, R, dtype=f32, device=dev),
-                    "alpha_fine": torch.empty(V, R, dtype=f32, device=dev), "sdf": torch.empty(V, R, dtype=f32, device=dev),
-                    "z_fine": torch.empty(V, R, Sc + Sf, dtype=f32, device=dev)})
-    o = VanerfPassOut()
-    for k in ("index", "hit", "z", "color", "depth", "alpha", "color_fine", "depth_fine", "alpha_fine", "sdf", "z_fine"):
-        setattr(o, k, _ptr(out.get(k)))
+    out, o = _pass_outputs((V, R), Sc, Sf, fine, dev)
     nbytes = render_pass_views_scratch(V, R, Sc, Sf, fine, reuse_coarse)
     if nbytes <= 0:
         raise ValueError(f"{V} views of {nx} x {ny} rays at {Sc} + {Sf} samples: not a valid multi-view pass")
     if scratch is None:
         scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    check(lib.vanerf_render_pass_views_vp(weights.handle, byref(frame.c), byref(frame.accel.c), _ptr(frame.verts3, f32), frame.verts3.shape[0],
-                                          _ptr(frame.faces, torch.int32), frame.faces.shape[0], byref(d), byref(o), _ptr(scratch, torch.uint8), scratch.numel(),
-                                          _ptr(frame.vertex_products(weights), f32), _stream()))
+    check(lib.vanerf_render_pass_views(weights.handle, byref(frame.c), byref(frame.accel.c), _ptr(frame.verts3, torch.float32), frame.verts3.shape[0],
+                                       _ptr(frame.faces, torch.int32), frame.faces.shape[0], byref(d), byref(o), _ptr(scratch, torch.uint8), scratch.numel(),
+                                       _ptr(frame.vertex_products(weights), torch.float32), _stream()))
     return out
 
 

@@ -122,7 +122,7 @@ def field_on_grid(net, frame, bounds=None, dims=None, voxel_size=None, want_rgb=
     frame data of the render pass, in the handle's precision.  bounds: (2, 3)-shaped, default the frame's own (dr_data['bounds'], or the
     vertices' box as mask_at_box.frame_bounds gives it); dims / voxel_size: grid_spec.  Per slab of whole z-layers with at most slab_points
     points (at least one layer): vanerf_grid_points -> vanerf_mesh_query_accel with the 1-NN vertex -> vanerf_query_order ->
-    vanerf_query_samples_vp (raw = 0, no noise) -> vanerf_field_values.  Every step is a per-point function, so the slab size changes no bit."""
+    vanerf_query_samples (raw = 0, no noise) -> vanerf_field_values.  Every step is a per-point function, so the slab size changes no bit."""
     from . import renderer as R
     if (dims is None) == (voxel_size is None):
         raise ValueError("give exactly one of dims and voxel_size")
