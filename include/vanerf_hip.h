@@ -16,7 +16,7 @@
  *   - return value: 0 on success, negative on error (message via vanerf_last_error(), thread local);
  *   - B = V = 1 (one target view, one source view): the non-spconv reference path is
  *     structurally single-view (src/networks.py:86,94) and evaluates batch items in Python loops.
- *     The *_views entry points march several TARGET views of the one source view in one pass.
+ *     A VanerfPassDesc with a camera table marches several TARGET views of the one source view in one pass.
  */
 #ifndef VANERF_HIP_H
 #define VANERF_HIP_H
@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define VANERF_ABI_VERSION 11
+#define VANERF_ABI_VERSION 12
 
 #define VANERF_OK 0
 #define VANERF_EINVAL (-22)
@@ -123,43 +123,34 @@ int vanerf_weights_stream_host(const VanerfWeightTable* w, int which, float* out
  * stream of the handle's mode, 2 the backward stream (fp32 handles only), 3 the hoisted bf16x3 stream (bf16x3 handles only).                     */
 int vanerf_weights_download(const VanerfWeights* w, int which, float* out, int64_t cap, int64_t* n_out);
 
-/* a1-a4  Pixel grid, ray generation, bbox clipping, coarse depths (src/model.py:1191-1238, 1496-1570).
- *   grid: x = x0 + ix*step_x, y = y0 + (iy / y_block)*step_y + (iy % y_block)*step_x for iy < ny (outer), ix < nx (inner); R = nx*ny rays
+/* a1-a4  Pixel grid, ray generation, bbox clipping, coarse depths (src/model.py:1191-1238, 1496-1570), described by a VanerfPassDesc (below).
+ *   Read: x0, y0, step_x, step_y, y_block, nx, ny, pixels_xy, row_blocks, width, n_views, cams or invK_T / RT / znear / zfar, bounds, Sc,
+ *   t_lin_c and jitter.  The other fields are ignored.
+ *   grid: x = x0 + ix*step_x, y = y0 + (iy / y_block)*step_y + (iy % y_block)*step_x for iy < ny (outer), ix < nx (inner); nx*ny rays per view
  *         (the reference's strided grid: step_x = step_y = 2^(level-1), y_block = 1, model.py:1194; a multi-GPU shard takes blocks of
  *          y_block = 8 consecutive rows, step_x = 1, step_y = 8 N, y0 = 8 rank: 8x8 pixel tiles stay whole, the load stays balanced)
- *   invK_T[9]: inverse(K[:3,:3]) transposed, row-major (host computed, as th.inverse at model.py:1208)
- *   RT[12]: target [R|t] rows 0..2;  bounds[6] = {min xyz, max xyz} (host values)
- *   t_lin[S]: th.linspace(0, 1, S) (device; computed by the caller so that it is bit-identical to torch's)
- *   outputs: index[R] (int64 pixel index x + y*W), rays_d[R][3], cam_pos[3] (device), near[R], far[R], hit[R] (u8),
- *            z[R][S] coarse depths (uniform=True: t_lin; else stratified with jitter[R][S] in [0,1) drawn by the caller) */
-int vanerf_ray_setup(int x0, int y0, int step_x, int step_y, int y_block, int nx, int ny, int width, const float* invK_T, const float* RT,
-                     float znear, float zfar, const float* bounds, int S, const float* t_lin, const float* jitter,
-                     int64_t* index, float* rays_d, float* cam_pos, float* near, float* far, uint8_t* hit, float* z,
-                     void* stream);
+ *   row_blocks: the rows as a list of blocks instead, row iy = row_blocks[iy / y_block] + (iy % y_block) * step_x (device table of ny / y_block
+ *         entries; ny a whole number of blocks): the shard of a multi-GPU view whose blocks of 8 rows were dealt by cost instead of round
+ *         robin (vanerf_amd/parallel.py: deal_blocks)
+ *   pixels_xy: an explicit pixel list [nx*ny][2] instead of a grid (the grid fields are ignored): the training branch's clamped 64x64 window
+ *         around a random mask pixel (src/model.py:1172-1189) is not a regular grid
+ *   camera: cams == NULL: invK_T[9] = inverse(K[:3,:3]) transposed, row-major (host computed, as th.inverse at model.py:1208), RT[12] = target
+ *         [R|t] rows 0..2, znear, zfar, by value; n_views = 1.  Else cams[n_views][24] (DEVICE, fp32) = invK_T[9], RT[12], znear, zfar, one pad
+ *         per view, n_views in [1, 65535]: every view has the same grid (plain: no pixel list, no row blocks, y_block = 1) and width, and
+ *         n_views * nx * ny * Sc must stay below 2^31 - 1 (the 32-bit sample index of vanerf_query_order).  Ray v * nx * ny + iy * nx + ix of
+ *         the outputs is ray (ix, iy) of view v, with the bits the by-value form gives for that camera alone (one ray function behind both).
+ *   bounds[6] = {min xyz, max xyz} (host values);  t_lin_c[Sc]: th.linspace(0, 1, Sc) (device; computed by the caller so that it is
+ *         bit-identical to torch's)
+ *   outputs, R = n_views*nx*ny: index[R] (int64 pixel index x + y*W), rays_d[R][3], cam_pos (device: [3] with a by-value camera,
+ *            [n_views][4] with a table), near[R], far[R], hit[R] (u8),
+ *            z[R][Sc] coarse depths (uniform=True: t_lin_c; else stratified with jitter[R][Sc] in [0,1) drawn by the caller) */
+struct VanerfPassDesc;
+int vanerf_ray_setup(const struct VanerfPassDesc* desc, int64_t* index, float* rays_d, float* cam_pos, float* near, float* far, uint8_t* hit,
+                     float* z, void* stream);
 
-/* ... with the rows as a list of blocks: row iy = row_blocks[iy / y_block] + (iy % y_block) * step_x (device table of ny / y_block entries): the
- * shard of a multi-GPU view whose blocks of 8 rows were dealt by cost instead of round robin (vanerf_amd/parallel.py: deal_blocks)          */
-int vanerf_ray_setup_blocks(const int32_t* row_blocks, int x0, int step_x, int y_block, int nx, int ny, int width, const float* invK_T,
-                            const float* RT, float znear, float zfar, const float* bounds, int S, const float* t_lin, const float* jitter,
-                            int64_t* index, float* rays_d, float* cam_pos, float* near, float* far, uint8_t* hit, float* z, void* stream);
-/* Same with an explicit pixel list pixels_xy[n_rays][2] (int32, device): the training branch's clamped 64x64 window around a
- * random mask pixel (src/model.py:1172-1189) is not a regular grid.                                                         */
-int vanerf_ray_setup_pixels(const int32_t* pixels_xy, int n_rays, int width, const float* invK_T, const float* RT, float znear,
-                            float zfar, const float* bounds, int S, const float* t_lin, const float* jitter, int64_t* index,
-                            float* rays_d, float* cam_pos, float* near, float* far, uint8_t* hit, float* z, void* stream);
-
-/* The regular grid (y_block = 1) for n_views target cameras at once: cams[n_views][24] (DEVICE, fp32) = invK_T[9], RT[12], znear, zfar, one pad;
- * every view has the same grid and width.  Ray v * nx * ny + iy * nx + ix of the outputs is ray (ix, iy) of view v, with the bits
- * vanerf_ray_setup gives for that camera alone (one ray function behind both); jitter[n_views*nx*ny][S] or NULL; cam_pos is [n_views][4].
- * n_views * nx * ny * S must stay below 2^31 - 1 (the 32-bit sample index of vanerf_query_order).                                        */
-int vanerf_ray_setup_views(const float* cams, int n_views, int x0, int y0, int step_x, int step_y, int nx, int ny, int width,
-                           const float* bounds, int S, const float* t_lin, const float* jitter, int64_t* index, float* rays_d,
-                           float* cam_pos, float* near, float* far, uint8_t* hit, float* z, void* stream);
-
-/* eval_pts = cam_pos + dir * z (src/model.py:1234-1235).  pts[R*S][3]. */
-int vanerf_sample_points(const float* rays_d, const float* cam_pos, const float* z, int R, int S, float* pts, void* stream);
-/* ... with one origin per view: ray r starts at cam_pos[r / rays_per_view][4] (the table vanerf_ray_setup_views writes); R is a whole number of views */
-int vanerf_sample_points_views(const float* rays_d, const float* cam_pos, const float* z, int R, int rays_per_view, int S, float* pts, void* stream);
+/* eval_pts = cam_pos + dir * z (src/model.py:1234-1235).  pts[R*S][3].  rays_per_view = 0: one origin cam_pos[3]; > 0: ray r starts at
+ * cam_pos[r / rays_per_view][4] (the table vanerf_ray_setup writes from a camera table), and R is a whole number of views. */
+int vanerf_sample_points(const float* rays_d, const float* cam_pos, const float* z, int R, int rays_per_view, int S, float* pts, void* stream);
 
 /* a6  get_visibility (mesh_util.py:284-318): vert_xy01[NV][2], vert_z01[NV], faces[NF][3] int32 -> vert_vis[NV];
  *     pix_to_face[S*S] int32 is scratch (may be NULL only if `scratch` given).                                          */
@@ -298,11 +289,15 @@ int vanerf_importance_sample(const float* contrib_inner, const float* z_mid, con
  * enqueues the kernels above on `stream` in the order vanerf_amd/renderer.py:render_pass does (same kernels, same arguments: same bits).
  * No allocation, no host synchronisation: all temporaries live in `scratch` (device memory of at least vanerf_render_pass_scratch(...) bytes,
  * caller-owned; two passes may run concurrently on different streams with different scratch blocks and the same weights handle).            */
-typedef struct {
-    int x0, y0, step_x, step_y, y_block, nx, ny; /* pixel grid as in vanerf_ray_setup (ignored when pixels_xy is given; then n_rays = nx * ny) */
-    const int32_t* pixels_xy;  /* optional explicit pixel list [nx*ny][2] (device), as in vanerf_ray_setup_pixels */
-    const int32_t* row_blocks; /* optional first rows of the ny / y_block blocks of rows (device), as in vanerf_ray_setup_blocks (y0, step_y ignored) */
+typedef struct VanerfPassDesc {
+    int x0, y0, step_x, step_y, y_block, nx, ny; /* pixel grid as in vanerf_ray_setup (ignored when pixels_xy is given; then nx * ny rays are listed) */
+    const int32_t* pixels_xy;  /* optional explicit pixel list [nx*ny][2] (device) */
+    const int32_t* row_blocks; /* optional first rows of the ny / y_block blocks of rows (device); y0, step_y ignored */
     int width;                 /* target image width (pixel index = x + y * width) */
+    int n_views;               /* >= 1 target views of the one source frame that share the grid and width; must be 1 when cams == NULL */
+    const float* cams;         /* NULL: the camera is invK_T / RT / znear / zfar below.  Else the [n_views][24] DEVICE table invK_T[9], RT[12], znear,
+                                  zfar, pad per view, and the by-value camera is not read.  The table form is the evaluation form: it takes the plain
+                                  grid only (no pixels_xy, no row_blocks, y_block = 1) and no noise_c / noise_f */
     float invK_T[9], RT[12];   /* target camera: inverse(K[:3,:3]) transposed; [R|t] rows 0..2 */
     float znear, zfar;
     float bounds[6];           /* {min xyz, max xyz} of the mesh bounding box (config['bounds']) */
@@ -314,13 +309,13 @@ typedef struct {
                                   (src/model.py:1155-1156), so the bits are those of re-evaluating all Sc + Sf samples */
     const float* t_lin_c;      /* th.linspace(0, 1, Sc) (device) */
     const float* t_lin_f;      /* th.linspace(0, 1, Sf) (device); used when u == NULL (uniform=True) */
-    const float* jitter;       /* [R][Sc] stratification draws or NULL (uniform=True) */
+    const float* jitter;       /* [R][Sc] stratification draws or NULL (uniform=True); R = n_views * nx * ny, view-major */
     const float* u;            /* [R][Sf] importance draws or NULL */
     const float* noise_c;      /* [R*Sc] rand_noise_std * randn draws for the coarse march, or NULL */
     const float* noise_f;      /* [R*(Sc+Sf)] the same for the fine march (required with noise_c when fine) */
 } VanerfPassDesc;
 
-typedef struct {               /* all device pointers; R = nx * ny */
+typedef struct {               /* all device pointers; R = n_views * nx * ny, view-major */
     int64_t* index;            /* [R]    pixel index */
     uint8_t* hit;              /* [R]    ray crosses the bounding box */
     float* z;                  /* [R][Sc] coarse depths */
@@ -334,35 +329,18 @@ typedef struct {               /* all device pointers; R = nx * ny */
     float* z_fine;             /* [R][Sc+Sf] merged depths, or NULL */
 } VanerfPassOut;
 
-/* reuse_coarse: 0, 1 as VanerfPassDesc.reuse_coarse; 2 = re-use under per-sample noise (desc->reuse_coarse with noise_c given: more temporaries) */
-int64_t vanerf_render_pass_scratch(int n_rays, int Sc, int Sf, int fine, int reuse_coarse);
-/* vertex_products: the frame's table of vanerf_vertex_products for the pass's per-sample launches, or NULL (as vanerf_query_samples) */
+/* Bytes of scratch a pass over n_views views of rays_per_view = nx * ny rays needs.  reuse_coarse: 0, 1 as VanerfPassDesc.reuse_coarse; 2 = re-use
+ * under per-sample noise (desc->reuse_coarse with noise_c given: more temporaries).  0: bad arguments, or the largest march of the pass,
+ * n_views * nx * ny * (Sc, max(Sc, Sf) with re-use, or Sc + Sf), reaches 2^31 - 1: the 32-bit sample index of vanerf_query_order bounds every
+ * pass (a single view that large used to fail inside vanerf_query_order; now here and at the head of vanerf_render_pass). */
+int64_t vanerf_render_pass_scratch(int n_views, int rays_per_view, int Sc, int Sf, int fine, int reuse_coarse);
+/* With a camera table the kernels run once over n_views * nx * ny rays instead of n_views times over nx * ny (the frames of an orbit, the views
+ * of a validation step): behind the ray setup nothing depends on the camera but the ray origin, so view v's slice of every output holds the
+ * bits the by-value form gives for that camera alone.
+ * vertex_products: the frame's table of vanerf_vertex_products for the pass's per-sample launches, or NULL (as vanerf_query_samples) */
 int vanerf_render_pass(const VanerfWeights* w, const VanerfFrame* frame, const VanerfMeshAccel* accel, const float* verts, int nv,
                        const int32_t* faces, int nf, const VanerfPassDesc* desc, const VanerfPassOut* out, void* scratch, int64_t scratch_bytes,
                        const float* vertex_products, void* stream);
-
-/* One pass over n_views target views of the same source frame that share a pixel grid (the frames of an orbit, the views of a validation step):
- * the kernels of vanerf_render_pass once over n_views * nx * ny rays instead of n_views times over nx * ny.  Behind the ray setup nothing
- * depends on the camera but the ray origin, so view v's slice of every output holds the bits vanerf_render_pass gives for that camera alone.
- * Evaluation only: no pixel list, no row blocks, no per-sample noise (training patches and multi-GPU ray shards keep vanerf_render_pass).    */
-typedef struct {
-    int n_views;
-    int x0, y0, step_x, step_y, nx, ny; /* x = x0 + ix*step_x, y = y0 + iy*step_y, the same for every view */
-    int width;                 /* target image width (pixel index = x + y * width) */
-    const float* cams;         /* [n_views][24] DEVICE table: invK_T[9], RT[12], znear, zfar, pad (as vanerf_ray_setup_views) */
-    float bounds[6];
-    int Sc, Sf, fine, reuse_coarse; /* as VanerfPassDesc */
-    const float* t_lin_c;      /* th.linspace(0, 1, Sc) (device) */
-    const float* t_lin_f;      /* th.linspace(0, 1, Sf) (device); used when u == NULL */
-    const float* jitter;       /* [n_views*nx*ny][Sc] or NULL */
-    const float* u;            /* [n_views*nx*ny][Sf] or NULL */
-} VanerfViewsDesc;
-
-/* out: VanerfPassOut with R = n_views * nx * ny (view-major).  The largest march, n_views * nx * ny * (Sf, Sc or Sc + Sf), must stay below 2^31 - 1. */
-int64_t vanerf_render_pass_views_scratch(int n_views, int rays_per_view, int Sc, int Sf, int fine, int reuse_coarse); /* 0: bad arguments */
-int vanerf_render_pass_views(const VanerfWeights* w, const VanerfFrame* frame, const VanerfMeshAccel* accel, const float* verts, int nv,
-                             const int32_t* faces, int nf, const VanerfViewsDesc* desc, const VanerfPassOut* out, void* scratch,
-                             int64_t scratch_bytes, const float* vertex_products /* as vanerf_render_pass */, void* stream);
 
 /* Training step, backward of the row gathers (bilinear taps of feat_sample, src/utils.py:136-151; nearest / twin vertex rows of KNN_vis,
  * src/networks.py:27-33):  table[idx[i]][0..C) += w[i] * g[i][0..C)  for i < n  (w may be NULL = 1; rows outside [0, R) are ignored).
@@ -458,7 +436,7 @@ int vanerf_image_metrics(const float* pred, const float* gt, const uint8_t* mask
 
 /* The dataset's mask_at_box and near / far range of V target views, on the device: Dataset.get_mask_at_box ->
  * get_rays / get_near_far (src/dataset.py:122-129, 609-658) restated.
- *     cams[V][24]: the DEVICE table of vanerf_ray_setup_views (invK_T[9], RT[12]; znear, zfar and the pad are not read).  bounds[6]: HOST,
+ *     cams[V][24]: the DEVICE table of VanerfPassDesc.cams (invK_T[9], RT[12]; znear, zfar and the pad are not read).  bounds[6]: HOST,
  *     min xyz then max xyz, read before the call returns.  Per pixel (r, c) of view v, in fp64 from the fp32 values:
  *        pc = (c, r, 1) . invK_T,  o = -R^T T,  d = (pc - T) . R - o;  o and d are each rounded to fp32 once, and a component of d with
  *        |d| < 1e-5 becomes +1e-5 (both in fp32; the sign is lost, as in the reference).

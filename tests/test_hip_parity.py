@@ -1067,7 +1067,7 @@ def test_many_passes_in_flight_on_two_streams(R, sd_full, precision):
 
 
 def test_rows_given_as_a_list_of_blocks(R, sd_full):
-    """vanerf_ray_setup_blocks / VanerfPassDesc.row_blocks: a shard whose 8-row blocks come from a table (parallel.deal_blocks) renders the bits
+    """VanerfPassDesc.row_blocks (vanerf_ray_setup, vanerf_render_pass): a shard whose 8-row blocks come from a table (parallel.deal_blocks) renders the bits
     those rows have in the whole image -- through the Python sequence and through the one-call C entry point."""
     from vanerf_amd.parallel import block_rows, deal_blocks
     frame = _frame(3, 64)

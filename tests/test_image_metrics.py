@@ -207,7 +207,7 @@ def test_image_metrics_is_declared_and_exported(ffi):
     assert re.search(r"\bint64_t\s+vanerf_image_metrics_scratch\s*\(", hdr) and re.search(r"\bint\s+vanerf_image_metrics\s*\(", hdr)
     for name in ("vanerf_image_metrics_scratch", "vanerf_image_metrics"):
         assert name in ffi.EXPORTS and hasattr(ffi.lib, name)
-    assert ffi.lib.vanerf_abi_version() == 11
+    assert ffi.lib.vanerf_abi_version() == 12
     from vanerf_amd import metrics
     assert metrics.SLOTS == tuple(sorted(SLOT, key=SLOT.get))
 

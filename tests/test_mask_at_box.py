@@ -235,7 +235,7 @@ def test_mask_at_box_is_declared_and_exported(ffi):
     assert re.search(r"\bint64_t\s+vanerf_mask_at_box_scratch\s*\(", hdr) and re.search(r"\bint\s+vanerf_mask_at_box\s*\(", hdr)
     for name in NEW_EXPORTS:
         assert name in ffi.EXPORTS and hasattr(ffi.lib, name)
-    assert ffi.ABI_VERSION == 11 and ffi.lib.vanerf_abi_version() == 11 and "#define VANERF_ABI_VERSION 11" in hdr
+    assert ffi.ABI_VERSION == 12 and ffi.lib.vanerf_abi_version() == 12 and "#define VANERF_ABI_VERSION 12" in hdr
     from vanerf_amd import mask_at_box as mab
     assert mab.SLOTS == tuple(sorted(SLOT, key=SLOT.get))
 

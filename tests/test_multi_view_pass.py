@@ -1,5 +1,5 @@
-"""Several target views of one source frame in a single pass (vanerf_ray_setup_views, vanerf_render_pass_views, renderer.render_pass_views,
-VANeRF.render_pifu_nerf_views, render_novel_views(views_per_pass=...)).
+"""Several target views of one source frame in a single pass (VanerfPassDesc.cams / n_views behind vanerf_ray_setup and vanerf_render_pass,
+renderer.render_pass_views, VANeRF.render_pifu_nerf_views, render_novel_views(views_per_pass=...)).
 
 Behind the ray setup nothing in a pass depends on the camera except the ray origin, and both ray kernels run one ray function, so a pass over
 V views must give, view after view, the BITS of V single-view passes: every comparison on the GPU below is torch.equal, none has a tolerance.
@@ -7,6 +7,7 @@ The CPU tests cover the ABI surface (exports, scratch sizes, argument errors) an
 import ctypes
 import inspect
 import os
+import re
 import sys
 
 import numpy as np
@@ -17,7 +18,6 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from vanerf_amd import synth  # noqa: E402
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW_EXPORTS = ("vanerf_ray_setup_views", "vanerf_sample_points_views", "vanerf_render_pass_views_scratch", "vanerf_render_pass_views")
 KEYS = ("index", "hit", "z", "color", "depth", "alpha", "color_fine", "depth_fine", "alpha_fine", "sdf", "z_fine")
 
 
@@ -31,69 +31,94 @@ def ffi():
 # CPU: ABI surface
 # ------------------------------------------------------------------------------------------------
 def test_new_entry_points_are_exported_and_declared(ffi):
+    """ABI 12: the multi-view pass is the camera-table form of the one pass descriptor; the exports are exactly what the header declares."""
     header = open(os.path.join(REPO, "include", "vanerf_hip.h")).read()
-    for name in NEW_EXPORTS:
+    assert set(re.findall(r"\b(vanerf_[a-z0-9_]+)\s*\(", header)) == set(ffi.EXPORTS)
+    for name in ("vanerf_ray_setup", "vanerf_sample_points", "vanerf_render_pass_scratch", "vanerf_render_pass"):
         assert name in ffi.EXPORTS and hasattr(ffi.lib, name)
         assert f"{name}(" in header
-    assert "VanerfViewsDesc" in header and hasattr(ffi, "VanerfViewsDesc")
-    assert ffi.ABI_VERSION == 11 and ffi.lib.vanerf_abi_version() == 11 and "#define VANERF_ABI_VERSION 11" in header
+    assert not [n for n in ffi.EXPORTS if n.endswith("_views") or n.startswith("vanerf_ray_setup") and n != "vanerf_ray_setup"]  # one entry each: no per-form twins
+    fields = [f for f, _ in ffi.VanerfPassDesc._fields_]
+    assert "n_views" in fields and "cams" in fields and "const float* cams;" in header and "int n_views;" in header
+    assert header.count("} VanerfPassDesc;") == 1 and "ViewsDesc" not in header  # one pass descriptor
+    assert ffi.ABI_VERSION == 12 and ffi.lib.vanerf_abi_version() == 12 and "#define VANERF_ABI_VERSION 12" in header
 
 
 def test_views_scratch_size(ffi):
-    lib = ffi.lib
+    scratch = ffi.lib.vanerf_render_pass_scratch
     for R, Sc, Sf, fine, reuse in ((64 * 64, 16, 16, 1, 1), (40 * 20, 16, 16, 1, 0), (256 * 256, 64, 64, 1, 1), (64 * 64, 16, 16, 0, 1)):
-        single = lib.vanerf_render_pass_scratch(R, Sc, Sf, fine, reuse if fine else 0)
-        sizes = [lib.vanerf_render_pass_views_scratch(V, R, Sc, Sf, fine, reuse) for V in (1, 2, 3, 4, 8, 16)]
+        single = scratch(1, R, Sc, Sf, fine, reuse if fine else 0)
+        sizes = [scratch(V, R, Sc, Sf, fine, reuse) for V in (1, 2, 3, 4, 8, 16)]
         assert single > 0 and sizes[0] >= single
         assert all(b >= a for a, b in zip(sizes, sizes[1:])) and sizes[-1] > sizes[0]
         assert sizes[3] <= 4 * sizes[0]  # a group needs no more than its views would need one by one
+        for r in (0, 1, 2):  # a single view under every re-use mode (2: per-sample noise, more temporaries) fits what two views need
+            assert 0 < scratch(1, R, Sc, Sf, fine, r) <= scratch(2, R, Sc, Sf, fine, r), (R, Sc, Sf, fine, r)
     for bad in ((0, 4096, 16, 16, 1, 1), (-1, 4096, 16, 16, 1, 1), (2, 0, 16, 16, 1, 1), (2, -5, 16, 16, 1, 1), (2, 4096, 0, 16, 1, 1), (2, 4096, 16, -1, 1, 1)):
-        assert lib.vanerf_render_pass_views_scratch(*bad) == 0, bad
+        assert scratch(*bad) == 0, bad
     # 0 also for a shape the pass itself refuses (16 M rays x 128 samples do not fit the 32-bit sample index), so that 0 means "not a valid pass"
-    assert lib.vanerf_render_pass_views_scratch(16, 1024 * 1024, 64, 64, 1, 0) == 0
-    assert lib.vanerf_render_pass_views_scratch(16, 1024 * 1024, 64, 64, 1, 1) > 0  # with coarse re-use the largest march has 64 per ray
+    assert scratch(16, 1024 * 1024, 64, 64, 1, 0) == 0
+    assert scratch(16, 1024 * 1024, 64, 64, 1, 1) > 0  # with coarse re-use the largest march has 64 per ray
+
+
+def _views_desc(ffi, p, **kw):
+    """2 views of 16 x 16 rays at 16 + 16 samples from a camera table; p: a pointer that is never dereferenced."""
+    d = ffi.VanerfPassDesc()
+    d.n_views, d.x0, d.y0, d.step_x, d.step_y, d.y_block, d.nx, d.ny, d.width = 2, 0, 0, 1, 1, 1, 16, 16, 16
+    d.cams, d.Sc, d.Sf, d.fine, d.reuse_coarse, d.t_lin_c, d.t_lin_f = p, 16, 16, 1, 1, p, p
+    d.bounds = (ctypes.c_float * 6)(-1, -1, -1, 1, 1, 1)
+    for k, v in kw.items():
+        setattr(d, k, v)
+    return d
 
 
 def test_ray_setup_views_rejects_bad_arguments(ffi):
     lib = ffi.lib
     p = ctypes.c_void_p(8)  # never dereferenced: every call below fails its argument checks before anything touches a GPU
-    bounds = (ctypes.c_float * 6)(-1, -1, -1, 1, 1, 1)
 
-    def call(cams=p, V=2, nx=16, ny=16, S=16, t_lin=p, bounds=bounds):
-        return lib.vanerf_ray_setup_views(cams, V, 0, 0, 1, 1, nx, ny, 16, bounds, S, t_lin, None, p, p, p, p, p, p, p, None)
+    def call(d="desc", index=p, cam_pos=p, z=p, **kw):
+        d = _views_desc(ffi, p, **kw) if d == "desc" else d
+        return lib.vanerf_ray_setup(ctypes.byref(d) if d is not None else None, index, p, cam_pos, p, p, p, z, None)
 
-    assert call(cams=None) == -22 and b"null" in lib.vanerf_last_error()
-    assert call(t_lin=None) == -22 and b"null" in lib.vanerf_last_error()  # the linspace table is required
-    assert call(bounds=None) == -22 and b"null" in lib.vanerf_last_error()
-    for V in (0, -3):
-        assert call(V=V) == -22 and b"n_views" in lib.vanerf_last_error()
-    assert call(S=1) == -22 and b"S=1" in lib.vanerf_last_error()
+    assert call(None) == -22 and b"null" in lib.vanerf_last_error()  # no descriptor
+    assert call(t_lin_c=None) == -22 and b"null" in lib.vanerf_last_error()  # the linspace table is required
+    for out in ("index", "cam_pos", "z"):
+        assert call(**{out: None}) == -22 and b"null" in lib.vanerf_last_error()
+    assert call(cams=None) == -22 and b"n_views" in lib.vanerf_last_error() and b"cams" in lib.vanerf_last_error()  # two views need a table
+    for V in (0, -3, 65536):
+        assert call(n_views=V) == -22 and b"n_views" in lib.vanerf_last_error()
+        assert call(n_views=V, cams=None) == -22 and b"n_views" in lib.vanerf_last_error()
+    assert call(Sc=1) == -22 and b"S=1" in lib.vanerf_last_error()
     assert call(nx=0) == -22 and b"nx=0" in lib.vanerf_last_error()
-    assert call(V=8, nx=4096, ny=4096, S=64) == -22 and b"32-bit" in lib.vanerf_last_error()  # 8.6e9 samples
-    assert lib.vanerf_sample_points_views(p, p, p, 10, 4, 8, p, None) == -22 and b"whole number of views" in lib.vanerf_last_error()
-    assert lib.vanerf_sample_points_views(None, p, p, 8, 4, 8, p, None) == -22 and b"null" in lib.vanerf_last_error()
+    assert call(n_views=1, cams=None, Sc=1) == -22 and b"S=1" in lib.vanerf_last_error()  # the by-value form makes the same grid checks
+    assert call(n_views=1, cams=None, nx=0) == -22 and b"nx=0" in lib.vanerf_last_error()
+    assert call(n_views=1, cams=None, step_x=0) == -22 and b"bad grid" in lib.vanerf_last_error()
+    assert call(n_views=8, nx=4096, ny=4096, Sc=64) == -22 and b"32-bit" in lib.vanerf_last_error()  # 8.6e9 samples
+    # the table form is the evaluation form: the plain grid only
+    assert call(pixels_xy=p) == -22 and b"pixels_xy" in lib.vanerf_last_error()
+    assert call(row_blocks=p) == -22 and b"row_blocks" in lib.vanerf_last_error()
+    assert call(y_block=2) == -22 and b"y_block" in lib.vanerf_last_error()
+    # rows as a list of blocks (by-value camera): ny is a whole number of blocks
+    assert call(n_views=1, cams=None, row_blocks=p, y_block=8, ny=20) == -22 and b"y_block" in lib.vanerf_last_error() and b"row_blocks" in lib.vanerf_last_error()
+    assert call(n_views=1, cams=None, row_blocks=p, y_block=0) == -22 and b"bad grid" in lib.vanerf_last_error()
+    assert lib.vanerf_sample_points(p, p, p, 10, 4, 8, p, None) == -22 and b"whole number of views" in lib.vanerf_last_error()
+    assert lib.vanerf_sample_points(None, p, p, 8, 4, 8, p, None) == -22 and b"null" in lib.vanerf_last_error()
+    assert lib.vanerf_sample_points(None, p, p, 8, 0, 8, p, None) == -22 and b"null" in lib.vanerf_last_error()
+    assert lib.vanerf_sample_points(p, p, p, 8, -1, 8, p, None) == -22 and b"rays_per_view=-1" in lib.vanerf_last_error()
 
 
 def test_render_pass_views_rejects_bad_arguments(ffi):
     lib = ffi.lib
     p = ctypes.c_void_p(8)
     frame, accel = ffi.VanerfFrame(), ffi.VanerfMeshAccel()
-
-    def desc(**kw):
-        d = ffi.VanerfViewsDesc()
-        d.n_views, d.x0, d.y0, d.step_x, d.step_y, d.nx, d.ny, d.width = 2, 0, 0, 1, 1, 16, 16, 16
-        d.cams, d.Sc, d.Sf, d.fine, d.reuse_coarse, d.t_lin_c, d.t_lin_f = p, 16, 16, 1, 1, p, p
-        for k, v in kw.items():
-            setattr(d, k, v)
-        return d
-
+    desc = lambda **kw: _views_desc(ffi, p, **kw)
     out = ffi.VanerfPassOut()
     for k in ("index", "hit", "z", "color", "depth", "alpha"):
         setattr(out, k, p)
 
     def call(d, w=p, o=out, scratch=p, nbytes=0):
-        return lib.vanerf_render_pass_views(w, ctypes.byref(frame), ctypes.byref(accel), p, 4, p, 4, ctypes.byref(d) if d is not None else None,
-                                            ctypes.byref(o), scratch, nbytes, None, None)
+        return lib.vanerf_render_pass(w, ctypes.byref(frame), ctypes.byref(accel), p, 4, p, 4, ctypes.byref(d) if d is not None else None,
+                                      ctypes.byref(o), scratch, nbytes, None, None)
 
     assert call(desc(), w=None) == -22 and b"null" in lib.vanerf_last_error()
     assert call(None) == -22 and b"null" in lib.vanerf_last_error()
@@ -102,13 +127,22 @@ def test_render_pass_views_rejects_bad_arguments(ffi):
         assert call(desc(n_views=V)) == -22 and f"n_views={V}".encode() in lib.vanerf_last_error()
     assert call(desc(Sc=1)) == -22 and b"Sc=1" in lib.vanerf_last_error()
     assert call(desc(Sf=0)) == -22 and b"Sf=0" in lib.vanerf_last_error()
-    assert call(desc(cams=None)) == -22 and b"camera table" in lib.vanerf_last_error()
+    assert call(desc(cams=None)) == -22 and b"n_views" in lib.vanerf_last_error() and b"cams" in lib.vanerf_last_error()  # n_views = 2 without a camera table
     assert call(desc(t_lin_c=None)) == -22 and b"linspace" in lib.vanerf_last_error()
     assert call(desc(t_lin_f=None)) == -22 and b"linspace" in lib.vanerf_last_error()  # no importance draws and no table to take their place
     assert call(desc(), o=ffi.VanerfPassOut()) == -22 and b"output pointer" in lib.vanerf_last_error()
     assert call(desc(n_views=8, nx=4096, ny=4096, Sc=64, Sf=64)) == -22 and b"32-bit" in lib.vanerf_last_error()
     assert call(desc(n_views=16, nx=1024, ny=1024, Sc=64, Sf=64, reuse_coarse=0)) == -22 and b"32-bit" in lib.vanerf_last_error()  # 16 M rays x 128
+    assert call(desc(n_views=1, cams=None, nx=4096, ny=4096, Sc=64, Sf=64, reuse_coarse=0)) == -22 and b"32-bit" in lib.vanerf_last_error()  # every pass
     assert call(desc(), nbytes=1024) == -22 and b"scratch" in lib.vanerf_last_error()  # valid arguments, a block that is too small
+    assert call(desc(n_views=1, cams=None), nbytes=1024) == -22 and b"scratch" in lib.vanerf_last_error()  # the same with the camera by value
+    # the table form is the evaluation form: each field it does not take is refused by name
+    assert call(desc(pixels_xy=p)) == -22 and b"pixels_xy" in lib.vanerf_last_error()
+    assert call(desc(row_blocks=p)) == -22 and b"row_blocks" in lib.vanerf_last_error()
+    assert call(desc(y_block=2)) == -22 and b"y_block" in lib.vanerf_last_error()
+    assert call(desc(noise_c=p, noise_f=p)) == -22 and b"noise_c" in lib.vanerf_last_error()
+    assert call(desc(noise_c=p)) == -22 and b"noise_c" in lib.vanerf_last_error()
+    assert call(desc(n_views=1, cams=None, noise_c=p)) == -22 and b"noise_c without noise_f" in lib.vanerf_last_error()  # (by value: as before)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -272,6 +306,71 @@ def test_ray_setup_views_equals_ray_setup_per_view(R, sd):
                     assert torch.equal(got["cam_pos"][v, :3], one["cam_pos"]), (v, V)
                 assert got["hit"].any() and not got["hit"].all()
     torch.cuda.synchronize()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("precision", ["fp32", "bf16x3"])
+def test_one_view_table_pass_equals_the_by_value_pass(R, sd, precision):
+    """vanerf_render_pass itself (descriptors filled here, not by the renderer's wrappers), one target camera, twice: cams = NULL with the camera
+    by value, and n_views = 1 with a one-row camera table.  20 x 13 = 260 rays (two 256-ray blocks, a tail of 4), 16 + 16 samples, fine, coarse
+    re-use, jitter and u handed in.  The two forms differ in where the camera comes from, in the layout of cam_pos ([3] / [1][4]) and in
+    rays_per_view (0 / 260): every field of VanerfPassOut must carry the same bits, and a direct vanerf_ray_setup must write the same origin."""
+    ffi, lib = R._ffi, R._ffi.lib
+    w = _weights(R, sd, precision)
+    fdat, cams, bounds = _scene(R, sd, 64, 64)
+    cam, nx, ny, Sc, Sf = cams[1], 20, 13, 16, 16
+    Rn, dev = nx * ny, fdat.verts3.device
+    g = torch.Generator(device="cuda").manual_seed(11)
+    jitter, u = torch.rand(Rn, Sc, device="cuda", generator=g), torch.rand(Rn, Sf, device="cuda", generator=g)
+    t_c, t_f = torch.linspace(0.0, 1.0, Sc).cuda(), torch.linspace(0.0, 1.0, Sf).cuda()
+    table = R.camera_table([cam], dev)
+    assert table.shape == (1, 24)
+    ptr = lambda t: ctypes.c_void_p(t.data_ptr())
+
+    def desc(by_value):
+        d = ffi.VanerfPassDesc()
+        d.x0, d.y0, d.step_x, d.step_y, d.y_block, d.nx, d.ny, d.width, d.n_views = 2, 4, 3, 3, 1, nx, ny, int(cam["width"]), 1
+        if by_value:
+            inv_K_T, RT, (d.znear, d.zfar) = R._camera_floats(cam)
+            d.invK_T, d.RT = (ctypes.c_float * 9)(*inv_K_T), (ctypes.c_float * 12)(*RT)
+        else:
+            d.cams = ptr(table)
+        d.bounds = (ctypes.c_float * 6)(*R.host_copy(bounds).reshape(-1).tolist())
+        d.Sc, d.Sf, d.fine, d.reuse_coarse = Sc, Sf, 1, 1
+        d.t_lin_c, d.t_lin_f, d.jitter, d.u = ptr(t_c), ptr(t_f), ptr(jitter), ptr(u)
+        return d
+
+    nbytes = lib.vanerf_render_pass_scratch(1, Rn, Sc, Sf, 1, 1)
+    assert nbytes > 0
+    shapes = {"index": ((Rn,), torch.int64), "hit": ((Rn,), torch.uint8), "z": ((Rn, Sc), None), "color": ((Rn, 3), None), "depth": ((Rn,), None),
+              "alpha": ((Rn,), None), "color_fine": ((Rn, 3), None), "depth_fine": ((Rn,), None), "alpha_fine": ((Rn,), None), "sdf": ((Rn,), None),
+              "z_fine": ((Rn, Sc + Sf), None)}
+    assert set(shapes) == {f for f, _ in ffi.VanerfPassOut._fields_}
+    results, origins = [], []
+    for by_value in (True, False):
+        d = desc(by_value)
+        out = {k: torch.full(shape, 77, dtype=dtype or torch.float32, device=dev) for k, (shape, dtype) in shapes.items()}
+        o = ffi.VanerfPassOut()
+        for k, t in out.items():
+            setattr(o, k, ptr(t))
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        ffi.check(lib.vanerf_render_pass(w.handle, ctypes.byref(fdat.c), ctypes.byref(fdat.accel.c), ptr(fdat.verts3), fdat.verts3.shape[0], ptr(fdat.faces),
+                                         fdat.faces.shape[0], ctypes.byref(d), ctypes.byref(o), ptr(scratch), nbytes, None, None))
+        rays = {k: torch.empty(shape, dtype=dtype or torch.float32, device=dev)
+                for k, (shape, dtype) in dict(index=shapes["index"], rays_d=((Rn, 3), None), near=((Rn,), None), far=((Rn,), None), hit=shapes["hit"], z=shapes["z"]).items()}
+        cam_pos = torch.full((3,) if by_value else (1, 4), 77.0, device=dev)
+        ffi.check(lib.vanerf_ray_setup(ctypes.byref(d), ptr(rays["index"]), ptr(rays["rays_d"]), ptr(cam_pos), ptr(rays["near"]), ptr(rays["far"]), ptr(rays["hit"]),
+                                       ptr(rays["z"]), None))
+        torch.cuda.synchronize()
+        for k in ("index", "hit", "z"):  # the pass's rays are those of a direct ray setup
+            assert torch.equal(rays[k], out[k]), (k, by_value)
+        results.append(out)
+        origins.append(cam_pos.reshape(-1)[:3].clone())
+    for k in shapes:
+        assert torch.equal(results[0][k], results[1][k]), k
+        assert not torch.isnan(results[0][k].float()).any(), k
+    assert torch.equal(origins[0], origins[1]) and not (origins[0] == 77.0).any()
+    assert results[0]["hit"].any() and results[0]["color_fine"].std().item() > 1e-3  # the hands are in view
 
 
 @pytest.mark.gpu

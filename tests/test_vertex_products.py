@@ -269,7 +269,7 @@ def test_one_call_pass_with_the_table_equals_the_python_sequence(R, sd_full):
 
 @pytest.mark.gpu
 def test_multi_view_pass_with_the_table_equals_single_passes(R, sd_full):
-    """vanerf_render_pass_views with vertex_products: 2 views of 40 x 20 rays in one pass hold, view after view, the bits of the single-view passes."""
+    """vanerf_render_pass over a camera table with vertex_products: 2 views of 40 x 20 rays in one pass hold, view after view, the bits of the single-view passes."""
     from vanerf_amd.model import get_360cameras
     from vanerf_amd.novel_views import camera_to_cam_tar
     frame = synth.make_frame(seed=3, tar_h=64, tar_w=64)

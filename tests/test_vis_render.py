@@ -156,7 +156,7 @@ def test_render_vis_is_declared_and_exported(ffi):
     assert re.search(r"\bint\s+vanerf_render_vis\s*\(", hdr)
     assert "vanerf_render_vis" in ffi.EXPORTS
     assert hasattr(ffi.lib, "vanerf_render_vis")
-    assert ffi.lib.vanerf_abi_version() == 11
+    assert ffi.lib.vanerf_abi_version() == 12
 
 
 def test_render_vis_rejects_bad_arguments_without_a_gpu(ffi):

@@ -58,4 +58,4 @@ print(f"bare render passes:  {1e3 * dt2 / n_frames:.2f} ms per frame", flush=Tru
 if vpp > 1:
     print(f"scratch per group:   {R.render_pass_views_scratch(vpp, 256 * 256, 64, 64)} bytes ({vpp} views)", flush=True)
 else:
-    print(f"scratch per pass:    {R.lib.vanerf_render_pass_scratch(256 * 256, 64, 64, 1, 1)} bytes (vanerf_render_pass)", flush=True)
+    print(f"scratch per pass:    {R.lib.vanerf_render_pass_scratch(1, 256 * 256, 64, 64, 1, 1)} bytes (vanerf_render_pass)", flush=True)

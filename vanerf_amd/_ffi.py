@@ -12,7 +12,7 @@ from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VANERF_HIP_LIB") or os.path.join(_HERE, "lib", "libvanerf_hip.so")  # the override is for A/B runs of kernel builds (tools/)
-ABI_VERSION = 11
+ABI_VERSION = 12
 NUM_LAYERS = 20
 
 if not os.path.exists(LIB_PATH):
@@ -56,17 +56,9 @@ class VanerfMeshAccel(Structure):
 class VanerfPassDesc(Structure):
     _fields_ = [
         ("x0", c_int), ("y0", c_int), ("step_x", c_int), ("step_y", c_int), ("y_block", c_int), ("nx", c_int), ("ny", c_int),
-        ("pixels_xy", _FP), ("row_blocks", _FP), ("width", c_int), ("invK_T", c_float * 9), ("RT", c_float * 12), ("znear", c_float), ("zfar", c_float),
+        ("pixels_xy", _FP), ("row_blocks", _FP), ("width", c_int), ("n_views", c_int), ("cams", _FP), ("invK_T", c_float * 9), ("RT", c_float * 12), ("znear", c_float), ("zfar", c_float),
         ("bounds", c_float * 6), ("Sc", c_int), ("Sf", c_int), ("fine", c_int), ("reuse_coarse", c_int),
         ("t_lin_c", _FP), ("t_lin_f", _FP), ("jitter", _FP), ("u", _FP), ("noise_c", _FP), ("noise_f", _FP),
-    ]
-
-
-class VanerfViewsDesc(Structure):
-    _fields_ = [
-        ("n_views", c_int), ("x0", c_int), ("y0", c_int), ("step_x", c_int), ("step_y", c_int), ("nx", c_int), ("ny", c_int), ("width", c_int),
-        ("cams", _FP), ("bounds", c_float * 6), ("Sc", c_int), ("Sf", c_int), ("fine", c_int), ("reuse_coarse", c_int),
-        ("t_lin_c", _FP), ("t_lin_f", _FP), ("jitter", _FP), ("u", _FP),
     ]
 
 
@@ -88,16 +80,8 @@ _SIGS = {
     "vanerf_weights_pack_host": (c_int, [POINTER(VanerfWeightTable), _FP, c_int64, POINTER(c_int64), POINTER(c_uint)]),
     "vanerf_weights_stream_host": (c_int, [POINTER(VanerfWeightTable), c_int, _FP, c_int64, POINTER(c_int64)]),
     "vanerf_weights_download": (c_int, [c_void_p, c_int, _FP, c_int64, POINTER(c_int64)]),
-    "vanerf_ray_setup": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_float), POINTER(c_float), c_float, c_float,
-                                 POINTER(c_float), c_int, _FP, _FP, _FP, _FP, _FP, _FP, _FP, _FP, _FP, c_void_p]),
-    "vanerf_ray_setup_pixels": (c_int, [_FP, c_int, c_int, POINTER(c_float), POINTER(c_float), c_float, c_float, POINTER(c_float), c_int, _FP, _FP,
-                                        _FP, _FP, _FP, _FP, _FP, _FP, _FP, c_void_p]),
-    "vanerf_ray_setup_blocks": (c_int, [_FP, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_float), POINTER(c_float), c_float, c_float,
-                                        POINTER(c_float), c_int, _FP, _FP, _FP, _FP, _FP, _FP, _FP, _FP, _FP, c_void_p]),
-    "vanerf_ray_setup_views": (c_int, [_FP, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_float), c_int, _FP, _FP, _FP, _FP, _FP, _FP,
-                                       _FP, _FP, _FP, c_void_p]),
-    "vanerf_sample_points": (c_int, [_FP, _FP, _FP, c_int, c_int, _FP, c_void_p]),
-    "vanerf_sample_points_views": (c_int, [_FP, _FP, _FP, c_int, c_int, c_int, _FP, c_void_p]),
+    "vanerf_ray_setup": (c_int, [POINTER(VanerfPassDesc), _FP, _FP, _FP, _FP, _FP, _FP, _FP, c_void_p]),
+    "vanerf_sample_points": (c_int, [_FP, _FP, _FP, c_int, c_int, c_int, _FP, c_void_p]),
     "vanerf_vertex_visibility": (c_int, [_FP, _FP, c_int, _FP, c_int, c_int, _FP, _FP, c_void_p]),
     "vanerf_mesh_query": (c_int, [_FP, c_int, _FP, c_int, _FP, _FP, c_int64, _FP, _FP, _FP, c_void_p]),
     "vanerf_mesh_query_accel": (c_int, [POINTER(VanerfMeshAccel), _FP, c_int, _FP, c_int, _FP, _FP, c_int64, _FP, _FP, _FP, _FP, c_int, c_int, c_int,
@@ -120,12 +104,9 @@ _SIGS = {
     "vanerf_composite_backward": (c_int, [c_void_p, _FP, _FP, _FP, c_int, _FP, _FP, c_int, _FP, c_int, _FP, _FP, _FP, _FP, _FP, _FP, _FP, c_void_p]),
     "vanerf_importance_merge": (c_int, [_FP, _FP, _FP, _FP, c_int, c_int, c_int, _FP, _FP, _FP, _FP, c_void_p]),
     "vanerf_importance_sample": (c_int, [_FP, _FP, _FP, _FP, c_int, c_int, c_int, _FP, _FP, c_void_p]),
-    "vanerf_render_pass_scratch": (c_int64, [c_int, c_int, c_int, c_int, c_int]),
+    "vanerf_render_pass_scratch": (c_int64, [c_int, c_int, c_int, c_int, c_int, c_int]),
     "vanerf_render_pass": (c_int, [c_void_p, POINTER(VanerfFrame), POINTER(VanerfMeshAccel), _FP, c_int, _FP, c_int, POINTER(VanerfPassDesc),
                                    POINTER(VanerfPassOut), _FP, c_int64, _FP, c_void_p]),
-    "vanerf_render_pass_views_scratch": (c_int64, [c_int, c_int, c_int, c_int, c_int, c_int]),
-    "vanerf_render_pass_views": (c_int, [c_void_p, POINTER(VanerfFrame), POINTER(VanerfMeshAccel), _FP, c_int, _FP, c_int, POINTER(VanerfViewsDesc),
-                                         POINTER(VanerfPassOut), _FP, c_int64, _FP, c_void_p]),
     "vanerf_scatter_add_rows": (c_int, [_FP, _FP, _FP, c_int64, c_int64, c_int, _FP, c_int, c_void_p]),
     "vanerf_bilinear_taps": (c_int, [_FP, c_int64, c_int, c_int, _FP, _FP, c_void_p]),
     "vanerf_scatter_add_rows2": (c_int, [_FP, _FP, _FP, _FP, _FP, _FP, c_int64, c_int64, c_int, _FP, c_int, c_void_p]),

@@ -86,9 +86,10 @@ struct PackTables {
 const PackTables& pack_tables();
 int layer_slots(int layer, int* k_of_slot, int cap);
 
-// A pass over several views marches n_views * nx * ny * S samples in one launch; the validity partition (vanerf_query_order) indexes them with
-// 32 bits, so the multi-view entry points refuse a launch that reaches this many (the bound vanerf_query_order itself applies).
+// A pass marches n_views * nx * ny * S samples in one launch; the validity partition (vanerf_query_order) indexes them with 32 bits, so
+// vanerf_render_pass and the table form of vanerf_ray_setup refuse a launch that reaches this many (the bound vanerf_query_order itself applies).
 constexpr long long VIEWS_MAX_ITEMS = 0x7fffffffLL;
+void check_camera_source(const char* who, const VanerfPassDesc& d); // render_kernels.hip: n_views and cams agree, and the table form has the plain grid
 
 } // namespace vanerf
 

@@ -37,7 +37,7 @@ struct Layout {
 
 // reuse: 0 the fine march evaluates all Sc + Sf samples; 1 it evaluates the Sf new ones and the composite gathers the coarse evaluations;
 // 2 the same under per-sample noise: raw network outputs once per point, eval_func once per set of draws (vanerf_eval_func)
-Layout carve(void* base, int R, int Sc, int Sf, int fine, int reuse, int n_views = 1)
+Layout carve(void* base, int R, int Sc, int Sf, int fine, int reuse, int n_views)
 {
     Carver c(base);
     Layout L{};
@@ -75,178 +75,106 @@ Layout carve(void* base, int R, int Sc, int Sf, int fine, int reuse, int n_views
     return L;
 }
 
-// Everything of a pass behind its ray setup, for both entry points: the marches, the composites and the importance merge over R rays whose
-// directions, clip range and coarse depths (o.z) are in place.  The entry points differ only in what they hand in here.
-struct Marches {
-    const char* who;          // the entry point's name, for error messages
-    int R, Sc, Sf, fine, reuse;
-    int rays_per_view;        // 0: one origin L.cam_pos[3] for every ray; else ray r starts at L.cam_pos[r / rays_per_view][4]
-    int grid_nx, grid_ny;     // ray-grid hint of the mesh query (0, 0: none); a pass over V views stacks their rows: (nx, V * ny)
-    const float *u, *t_lin_f, *noise_c, *noise_f;
-    const float* vertex_products; // the frame's table for the per-sample launches, or NULL (vanerf_query_samples)
-};
-
-void run_marches(const VanerfWeights* w, const VanerfFrame* frame, const VanerfMeshAccel* accel, const float* verts, int nv, const int32_t* faces, int nf,
-                 const Marches& m, const Layout& L, const VanerfPassOut& o, void* stream)
+void ok(int rc, const char* what)
 {
-    const int R = m.R, Sc = m.Sc, Sf = m.Sf, reuse = m.reuse;
-    auto ok = [&](int rc, const char* what) {
-        if (rc != VANERF_OK) {
-            const std::string inner = vanerf_last_error();
-            throw Error(rc, std::string(m.who) + ": " + what + ": " + inner);
-        }
-    };
+    if (rc != VANERF_OK) {
+        const std::string inner = vanerf_last_error();
+        throw Error(rc, std::string("vanerf_render_pass: ") + what + ": " + inner);
+    }
+}
+
+// Everything of a pass behind its ray setup: the marches, the composites and the importance merge over the R rays whose directions, origins,
+// clip range and coarse depths (o.z) are in place.  Nothing here knows about cameras except the per-view ray origin.
+void run_marches(const VanerfWeights* w, const VanerfFrame* frame, const VanerfMeshAccel* accel, const float* verts, int nv, const int32_t* faces, int nf,
+                 const VanerfPassDesc& d, int reuse, const float* vertex_products, const Layout& L, const VanerfPassOut& o, void* stream)
+{
+    const int R = d.n_views * d.nx * d.ny, Sc = d.Sc, Sf = d.Sf;
+    const int rays_per_view = d.cams ? d.nx * d.ny : 0; // 0: one origin L.cam_pos[3] for every ray; else ray r starts at L.cam_pos[r / rays_per_view][4]
+    // ray-grid hint of the mesh query (0, 0 with a pixel list: none); the views of a pass stack their rows: (nx, n_views * ny)
+    const int grid_nx = d.pixels_xy ? 0 : d.nx, grid_ny = d.pixels_xy ? 0 : d.n_views * d.ny;
     // one march: points, mesh query (+ 1-NN), validity partition, per-sample networks
     int marches = 0; // every launch with a work queue gets a word of its own from the scratch block (nothing is shared between launches in flight)
     auto march = [&](const float* z, int S, const float* noise, float* q_sdf, float* rgba, uint8_t* valid_raw = nullptr) { // valid_raw: raw outputs + flags
         unsigned long long* const qw = L.queue_words + 2 * marches++;
         const int64_t n = (int64_t)R * S;
-        if (m.rays_per_view)
-            ok(vanerf_sample_points_views(L.rays_d, L.cam_pos, z, R, m.rays_per_view, S, L.pts, stream), "sample points");
-        else
-            ok(vanerf_sample_points(L.rays_d, L.cam_pos, z, R, S, L.pts, stream), "sample points");
-        const bool grid = m.grid_nx != 0;
-        ok(vanerf_mesh_query_accel(accel, verts, nv, faces, nf, frame->vert_vis, L.pts, n, q_sdf, L.q_vis, nullptr, L.knn, m.grid_nx, m.grid_ny, grid ? S : 0, qw,
+        ok(vanerf_sample_points(L.rays_d, L.cam_pos, z, R, rays_per_view, S, L.pts, stream), "sample points");
+        ok(vanerf_mesh_query_accel(accel, verts, nv, faces, nf, frame->vert_vis, L.pts, n, q_sdf, L.q_vis, nullptr, L.knn, grid_nx, grid_ny, grid_nx ? S : 0, qw,
                                    stream), "mesh query");
         const int32_t* order = nullptr;
         if (n >= PARTITION_MIN_SAMPLES) {
             ok(vanerf_query_order(frame, L.pts, n, L.order, L.order_scratch, L.order_scratch_bytes, stream), "validity partition");
             order = L.order;
         }
-        ok(vanerf_query_samples(w, frame, L.pts, q_sdf, L.q_vis, L.knn, noise, order, valid_raw ? 1 : 0, n, rgba, valid_raw, qw + 1, m.vertex_products, stream),
+        ok(vanerf_query_samples(w, frame, L.pts, q_sdf, L.q_vis, L.knn, noise, order, valid_raw ? 1 : 0, n, rgba, valid_raw, qw + 1, vertex_products, stream),
            "per-sample networks");
     };
     if (reuse == 2) { // the networks once per point; eval_func with the coarse draws here, with the fine batch's draws below
         march(o.z, Sc, nullptr, L.q_sdf_c, L.raw_c, L.valid_c);
-        ok(vanerf_eval_func(L.raw_c, L.valid_c, nullptr, nullptr, nullptr, m.noise_c, Sc, 0, R, frame->invalid_sdf, L.rgba_c, nullptr, stream), "eval_func (coarse)");
+        ok(vanerf_eval_func(L.raw_c, L.valid_c, nullptr, nullptr, nullptr, d.noise_c, Sc, 0, R, frame->invalid_sdf, L.rgba_c, nullptr, stream), "eval_func (coarse)");
     } else {
-        march(o.z, Sc, m.noise_c, L.q_sdf_c, L.rgba_c);
+        march(o.z, Sc, d.noise_c, L.q_sdf_c, L.rgba_c);
     }
     ok(vanerf_composite_handle(w, L.rgba_c, o.z, L.q_sdf_c, Sc, nullptr, nullptr, 0, nullptr, R, o.color, o.depth, o.alpha, L.s1, L.contrib, stream), "composite");
-    if (!m.fine) return;
+    if (!d.fine) return;
     float* z_fine = o.z_fine ? o.z_fine : L.z_fine;
     float* cf = o.color_fine ? o.color_fine : L.color_f3;
     float* df = o.depth_fine ? o.depth_fine : L.s1 + R;
     float* af = o.alpha_fine ? o.alpha_fine : L.s1 + 2LL * R;
     float* sf = o.sdf ? o.sdf : L.s1 + 3LL * R;
-    ok(vanerf_importance_merge(L.contrib, o.z, m.u, m.u ? nullptr : m.t_lin_f, R, Sc, Sf, L.z_new, z_fine, L.src, nullptr, stream), "importance sampling");
+    ok(vanerf_importance_merge(L.contrib, o.z, d.u, d.u ? nullptr : d.t_lin_f, R, Sc, Sf, L.z_new, z_fine, L.src, nullptr, stream), "importance sampling");
     if (reuse == 2) {
         march(L.z_new, Sf, nullptr, L.q_sdf_f, L.rgba_f, L.valid_f);
         // noise_f holds one draw per position of the merged order (the reference draws them for the re-evaluated fine batch, src/model.py:1155-1156)
-        ok(vanerf_eval_func(L.raw_c, L.valid_c, L.rgba_f, L.valid_f, L.src, m.noise_f, Sc, Sf, R, frame->invalid_sdf, L.rgba_cf, L.rgba_f, stream), "eval_func (fine)");
+        ok(vanerf_eval_func(L.raw_c, L.valid_c, L.rgba_f, L.valid_f, L.src, d.noise_f, Sc, Sf, R, frame->invalid_sdf, L.rgba_cf, L.rgba_f, stream), "eval_func (fine)");
         ok(vanerf_composite_handle(w, L.rgba_cf, z_fine, L.q_sdf_c, Sc, L.rgba_f, L.q_sdf_f, Sf, L.src, R, cf, df, af, sf, nullptr, stream), "fine composite");
     } else if (reuse) {
         march(L.z_new, Sf, nullptr, L.q_sdf_f, L.rgba_f);
         ok(vanerf_composite_handle(w, L.rgba_c, z_fine, L.q_sdf_c, Sc, L.rgba_f, L.q_sdf_f, Sf, L.src, R, cf, df, af, sf, nullptr, stream), "fine composite");
     } else {
-        march(z_fine, Sc + Sf, m.noise_f, L.q_sdf_f, L.rgba_f);
+        march(z_fine, Sc + Sf, d.noise_f, L.q_sdf_f, L.rgba_f);
         ok(vanerf_composite_handle(w, L.rgba_f, z_fine, L.q_sdf_f, Sc + Sf, nullptr, nullptr, 0, nullptr, R, cf, df, af, sf, nullptr, stream), "fine composite");
     }
 }
 
-// samples per ray of the largest march of a pass (what the multi-view entry points hold against VIEWS_MAX_ITEMS)
-int views_s_max(int Sc, int Sf, bool fine, bool reuse) { return !fine ? Sc : reuse ? (Sc > Sf ? Sc : Sf) : Sc + Sf; }
-
-void ok_setup(const char* who, int rc)
-{
-    if (rc != VANERF_OK) {
-        const std::string inner = vanerf_last_error();
-        throw Error(rc, std::string(who) + ": ray setup: " + inner);
-    }
-}
-
-// The argument checks the two entry points have in common -- null arguments, coarse output pointers, linspace tables, scratch size -- and the
-// carve of the scratch block.  own(d) holds the checks of what only the entry point's descriptor has and returns the shape of its pass.
-struct Shape {
-    int R, reuse, n_views;
-};
-
-template <class Desc, class Own>
-std::pair<Shape, Layout> checked_layout(const char* who, const VanerfWeights* w, const VanerfFrame* frame, const VanerfMeshAccel* accel, const float* verts,
-                                        const int32_t* faces, const Desc* desc, const VanerfPassOut* out, void* scratch, int64_t scratch_bytes, Own own)
-{
-    if (!w || !frame || !accel || !verts || !faces || !desc || !out || !scratch) throw_error("%s: null argument", who);
-    const Desc& d = *desc;
-    const VanerfPassOut& o = *out;
-    const Shape s = own(d);
-    if (!o.index || !o.hit || !o.z || !o.color || !o.depth || !o.alpha) throw_error("%s: a coarse output pointer is null", who);
-    if (!d.t_lin_c || (d.fine && !d.u && !d.t_lin_f)) throw_error("%s: linspace tables missing", who);
-    const Layout L = carve(scratch, s.R, d.Sc, d.Sf, d.fine != 0, s.reuse, s.n_views);
-    if (scratch_bytes < L.total) throw_error("%s: scratch of %lld bytes, %lld needed (%s_scratch)", who, (long long)scratch_bytes, (long long)L.total, who);
-    return {s, L};
-}
+// samples per ray of the largest march of a pass (held against VIEWS_MAX_ITEMS)
+int s_max(int Sc, int Sf, bool fine, bool reuse) { return !fine ? Sc : reuse ? (Sc > Sf ? Sc : Sf) : Sc + Sf; }
 
 } // namespace
 
-extern "C" int64_t vanerf_render_pass_scratch(int n_rays, int Sc, int Sf, int fine, int reuse_coarse)
+extern "C" int64_t vanerf_render_pass_scratch(int n_views, int rays_per_view, int Sc, int Sf, int fine, int reuse_coarse)
 {
-    if (n_rays <= 0 || Sc <= 0 || Sf < 0) return 0;
-    return carve(nullptr, n_rays, Sc, Sf, fine, reuse_coarse).total;
+    if (n_views <= 0 || rays_per_view <= 0 || Sc <= 0 || Sf < 0) return 0;
+    if ((long long)n_views * rays_per_view * s_max(Sc, Sf, fine != 0, reuse_coarse != 0) >= VIEWS_MAX_ITEMS) return 0; // as the pass itself
+    return carve(nullptr, n_views * rays_per_view, Sc, Sf, fine, reuse_coarse, n_views).total;
 }
 
+// check, carve, ray setup, marches
 extern "C" int vanerf_render_pass(const VanerfWeights* w, const VanerfFrame* frame, const VanerfMeshAccel* accel, const float* verts, int nv,
                                   const int32_t* faces, int nf, const VanerfPassDesc* desc, const VanerfPassOut* out, void* scratch,
                                   int64_t scratch_bytes, const float* vertex_products, void* stream)
 {
     return guarded([&] {
-        const char* const who = "vanerf_render_pass";
-        const auto [shape, L] = checked_layout(who, w, frame, accel, verts, faces, desc, out, scratch, scratch_bytes, [](const VanerfPassDesc& d) {
-            const bool fine = d.fine != 0;
-            if (d.nx <= 0 || d.ny <= 0 || d.Sc < 2 || (fine && d.Sf < 1)) throw_error("vanerf_render_pass: nx=%d ny=%d Sc=%d Sf=%d", d.nx, d.ny, d.Sc, d.Sf);
-            if (fine && d.noise_c && !d.noise_f) throw_error("vanerf_render_pass: noise_c without noise_f");
-            return Shape{d.nx * d.ny, !d.reuse_coarse || !fine ? 0 : d.noise_c ? 2 : 1, 1};
-        });
+        if (!w || !frame || !accel || !verts || !faces || !desc || !out || !scratch) throw_error("vanerf_render_pass: null argument");
         const VanerfPassDesc& d = *desc;
         const VanerfPassOut& o = *out;
-        const int R = shape.R, Sc = d.Sc, Sf = d.Sf, fine = d.fine != 0;
+        const int V = d.n_views, Sc = d.Sc, Sf = d.Sf;
+        const bool fine = d.fine != 0;
+        if (V <= 0 || d.nx <= 0 || d.ny <= 0 || Sc < 2 || (fine && Sf < 1))
+            throw_error("vanerf_render_pass: n_views=%d nx=%d ny=%d Sc=%d Sf=%d", V, d.nx, d.ny, Sc, Sf);
+        check_camera_source("vanerf_render_pass", d);
+        if (d.cams && (d.noise_c || d.noise_f)) throw_error("vanerf_render_pass: noise_c / noise_f with a camera table (cams): the table form is the evaluation form");
+        if (fine && d.noise_c && !d.noise_f) throw_error("vanerf_render_pass: noise_c without noise_f");
+        const int reuse = !d.reuse_coarse || !fine ? 0 : d.noise_c ? 2 : 1;
+        const int S_max = s_max(Sc, Sf, fine, reuse != 0);
+        if ((long long)V * d.nx * d.ny * S_max >= VIEWS_MAX_ITEMS)
+            throw_error("vanerf_render_pass: %d views of %d x %d rays at %d samples do not fit a 32-bit sample index", V, d.nx, d.ny, S_max);
+        if (!o.index || !o.hit || !o.z || !o.color || !o.depth || !o.alpha) throw_error("vanerf_render_pass: a coarse output pointer is null");
+        if (!d.t_lin_c || (fine && !d.u && !d.t_lin_f)) throw_error("vanerf_render_pass: linspace tables missing");
+        const Layout L = carve(scratch, V * d.nx * d.ny, Sc, Sf, fine, reuse, V);
+        if (scratch_bytes < L.total)
+            throw_error("vanerf_render_pass: scratch of %lld bytes, %lld needed (vanerf_render_pass_scratch)", (long long)scratch_bytes, (long long)L.total);
         // a1-a4: pixel grid, rays, bbox clip, coarse depths
-        if (d.pixels_xy)
-            ok_setup(who, vanerf_ray_setup_pixels(d.pixels_xy, R, d.width, d.invK_T, d.RT, d.znear, d.zfar, d.bounds, Sc, d.t_lin_c, d.jitter, o.index, L.rays_d,
-                                                  L.cam_pos, L.near, L.far, o.hit, o.z, stream));
-        else if (d.row_blocks)
-            ok_setup(who, vanerf_ray_setup_blocks(d.row_blocks, d.x0, d.step_x, d.y_block, d.nx, d.ny, d.width, d.invK_T, d.RT, d.znear, d.zfar, d.bounds, Sc, d.t_lin_c,
-                                                  d.jitter, o.index, L.rays_d, L.cam_pos, L.near, L.far, o.hit, o.z, stream));
-        else
-            ok_setup(who, vanerf_ray_setup(d.x0, d.y0, d.step_x, d.step_y, d.y_block, d.nx, d.ny, d.width, d.invK_T, d.RT, d.znear, d.zfar, d.bounds, Sc, d.t_lin_c,
-                                           d.jitter, o.index, L.rays_d, L.cam_pos, L.near, L.far, o.hit, o.z, stream));
-        const bool grid = d.pixels_xy == nullptr;
-        run_marches(w, frame, accel, verts, nv, faces, nf,
-                    Marches{who, R, Sc, Sf, fine, shape.reuse, 0, grid ? d.nx : 0, grid ? d.ny : 0, d.u, d.t_lin_f, d.noise_c, d.noise_f, vertex_products}, L, o, stream);
-    });
-}
-
-// A pass over n_views target views of one source frame that share a pixel grid: one ray setup that reads the cameras from a device table, then
-// the marches above over n_views * nx * ny rays (the views' rows stacked: the ray-grid hint is nx x (n_views * ny)).  Nothing behind the ray
-// setup knows about cameras except the per-view ray origin, so the outputs hold, view after view, the bits of n_views single passes.
-extern "C" int64_t vanerf_render_pass_views_scratch(int n_views, int rays_per_view, int Sc, int Sf, int fine, int reuse_coarse)
-{
-    if (n_views <= 0 || rays_per_view <= 0 || Sc <= 0 || Sf < 0) return 0;
-    if ((long long)n_views * rays_per_view * views_s_max(Sc, Sf, fine != 0, reuse_coarse && fine) >= VIEWS_MAX_ITEMS) return 0; // as the pass itself
-    return carve(nullptr, n_views * rays_per_view, Sc, Sf, fine, reuse_coarse ? 1 : 0, n_views).total;
-}
-
-extern "C" int vanerf_render_pass_views(const VanerfWeights* w, const VanerfFrame* frame, const VanerfMeshAccel* accel, const float* verts, int nv,
-                                        const int32_t* faces, int nf, const VanerfViewsDesc* desc, const VanerfPassOut* out, void* scratch,
-                                        int64_t scratch_bytes, const float* vertex_products, void* stream)
-{
-    return guarded([&] {
-        const char* const who = "vanerf_render_pass_views";
-        const auto [shape, L] = checked_layout(who, w, frame, accel, verts, faces, desc, out, scratch, scratch_bytes, [](const VanerfViewsDesc& d) {
-            const int V = d.n_views;
-            const bool fine = d.fine != 0, reuse = d.reuse_coarse && fine;
-            if (V <= 0 || d.nx <= 0 || d.ny <= 0 || d.Sc < 2 || (fine && d.Sf < 1))
-                throw_error("vanerf_render_pass_views: n_views=%d nx=%d ny=%d Sc=%d Sf=%d", V, d.nx, d.ny, d.Sc, d.Sf);
-            if (!d.cams) throw_error("vanerf_render_pass_views: camera table missing");
-            const int S_max = views_s_max(d.Sc, d.Sf, fine, reuse);
-            if ((long long)V * d.nx * d.ny * S_max >= VIEWS_MAX_ITEMS)
-                throw_error("vanerf_render_pass_views: %d views of %d x %d rays at %d samples do not fit a 32-bit sample index", V, d.nx, d.ny, S_max);
-            return Shape{V * d.nx * d.ny, reuse ? 1 : 0, V};
-        });
-        const VanerfViewsDesc& d = *desc;
-        const VanerfPassOut& o = *out;
-        const int V = d.n_views, Sc = d.Sc, Sf = d.Sf, fine = d.fine != 0;
-        ok_setup(who, vanerf_ray_setup_views(d.cams, V, d.x0, d.y0, d.step_x, d.step_y, d.nx, d.ny, d.width, d.bounds, Sc, d.t_lin_c, d.jitter, o.index, L.rays_d,
-                                             L.cam_pos, L.near, L.far, o.hit, o.z, stream));
-        run_marches(w, frame, accel, verts, nv, faces, nf, Marches{who, shape.R, Sc, Sf, fine, shape.reuse, d.nx * d.ny, d.nx, V * d.ny, d.u, d.t_lin_f, nullptr, nullptr, vertex_products}, L, o, stream);
+        ok(vanerf_ray_setup(desc, o.index, L.rays_d, L.cam_pos, L.near, L.far, o.hit, o.z, stream), "ray setup");
+        run_marches(w, frame, accel, verts, nv, faces, nf, d, reuse, vertex_products, L, o, stream);
     });
 }

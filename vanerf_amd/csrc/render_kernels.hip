@@ -335,104 +335,60 @@ __global__ __launch_bounds__(IM_BLOCK) void importance_merge_kernel(const float*
 
 } // namespace
 
-static void ray_setup_impl(const int32_t* pixels, const int32_t* row_blocks, int x0, int y0, int step_x, int step_y, int y_block, int nx, int ny, int width, const float* invK_T,
-                           const float* RT, float znear, float zfar, const float* bounds, int S, const float* t_lin, const float* jitter,
-                           int64_t* index, float* rays_d, float* cam_pos, float* near, float* far, uint8_t* hit, float* z, void* stream)
+// What both users of a VanerfPassDesc's camera source (vanerf_ray_setup, vanerf_render_pass) hold it to.
+void vanerf::check_camera_source(const char* who, const VanerfPassDesc& d)
 {
-    if (!invK_T || !RT || !bounds || !t_lin || !index || !rays_d || !cam_pos || !near || !far || !hit || !z)
-        throw_error("vanerf_ray_setup: null argument");
-    if (nx <= 0 || ny <= 0 || step_x <= 0 || step_y <= 0 || y_block <= 0 || S < 2 || width <= 0)
-        throw_error("vanerf_ray_setup: bad grid (nx=%d ny=%d step=%d,%d S=%d)", nx, ny, step_x, step_y, S);
-    RayParams P;
-    P.x0 = x0; P.y0 = y0; P.step_x = step_x; P.step_y = step_y; P.y_block = y_block; P.nx = nx; P.ny = ny; P.width = width; P.pixels = pixels; P.row_blocks = row_blocks;
-    std::copy_n(invK_T, 9, P.invK_T);
-    std::copy_n(RT, 12, P.RT);
-    std::copy_n(bounds, 6, P.bounds);
-    P.znear = znear; P.zfar = zfar; P.S = S; P.t_lin = t_lin; P.jitter = jitter;
-    P.index = index; P.rays_d = rays_d; P.cam_pos = cam_pos; P.near = near; P.far = far; P.hit = hit; P.z = z;
-    const int R = nx * ny;
-    hipLaunchKernelGGL(ray_setup_kernel, dim3((R + 255) / 256), dim3(256), 0, (hipStream_t)stream, P);
-    HIP_CHECK(hipGetLastError());
+    if (d.n_views <= 0 || d.n_views > 65535) throw_error("%s: n_views = %d outside [1, 65535]", who, d.n_views);
+    if (!d.cams && d.n_views != 1) throw_error("%s: n_views = %d without a camera table (cams == NULL is one camera by value)", who, d.n_views);
+    if (!d.cams) return;
+    if (d.pixels_xy) throw_error("%s: pixels_xy with a camera table (cams): the table form takes the regular grid only", who);
+    if (d.row_blocks) throw_error("%s: row_blocks with a camera table (cams): the table form takes the regular grid only", who);
+    if (d.y_block != 1) throw_error("%s: y_block = %d with a camera table (cams): the table form takes y_block = 1 only", who, d.y_block);
 }
 
-extern "C" int vanerf_ray_setup(int x0, int y0, int step_x, int step_y, int y_block, int nx, int ny, int width, const float* invK_T, const float* RT,
-                                float znear, float zfar, const float* bounds, int S, const float* t_lin, const float* jitter,
-                                int64_t* index, float* rays_d, float* cam_pos, float* near, float* far, uint8_t* hit, float* z,
+extern "C" int vanerf_ray_setup(const VanerfPassDesc* desc, int64_t* index, float* rays_d, float* cam_pos, float* near, float* far, uint8_t* hit, float* z,
                                 void* stream)
 {
     return guarded([&] {
-        ray_setup_impl(nullptr, nullptr, x0, y0, step_x, step_y, y_block, nx, ny, width, invK_T, RT, znear, zfar, bounds, S, t_lin, jitter, index, rays_d,
-                       cam_pos, near, far, hit, z, stream);
-    });
-}
-
-// the same grid with the rows given as a list of blocks: row iy is row_blocks[iy / y_block] + (iy % y_block) * step_x (device table of ny / y_block
-// entries) -- a multi-GPU shard whose 8-row blocks were dealt by cost (vanerf_amd/parallel.py: deal_blocks) instead of round robin
-extern "C" int vanerf_ray_setup_blocks(const int32_t* row_blocks, int x0, int step_x, int y_block, int nx, int ny, int width, const float* invK_T,
-                                       const float* RT, float znear, float zfar, const float* bounds, int S, const float* t_lin, const float* jitter,
-                                       int64_t* index, float* rays_d, float* cam_pos, float* near, float* far, uint8_t* hit, float* z, void* stream)
-{
-    return guarded([&] {
-        if (!row_blocks) throw_error("vanerf_ray_setup_blocks: null block list");
-        if (y_block <= 0 || ny % y_block != 0) throw_error("vanerf_ray_setup_blocks: ny = %d is not a whole number of blocks of %d rows", ny, y_block);
-        ray_setup_impl(nullptr, row_blocks, x0, 0, step_x, 1, y_block, nx, ny, width, invK_T, RT, znear, zfar, bounds, S, t_lin, jitter, index, rays_d,
-                       cam_pos, near, far, hit, z, stream);
-    });
-}
-
-extern "C" int vanerf_ray_setup_pixels(const int32_t* pixels_xy, int n_rays, int width, const float* invK_T, const float* RT, float znear,
-                                       float zfar, const float* bounds, int S, const float* t_lin, const float* jitter, int64_t* index,
-                                       float* rays_d, float* cam_pos, float* near, float* far, uint8_t* hit, float* z, void* stream)
-{
-    return guarded([&] {
-        if (!pixels_xy) throw_error("vanerf_ray_setup_pixels: null pixel list");
-        ray_setup_impl(pixels_xy, nullptr, 0, 0, 1, 1, 1, n_rays, 1, width, invK_T, RT, znear, zfar, bounds, S, t_lin, jitter, index, rays_d, cam_pos,
-                       near, far, hit, z, stream);
-    });
-}
-
-extern "C" int vanerf_ray_setup_views(const float* cams, int n_views, int x0, int y0, int step_x, int step_y, int nx, int ny, int width,
-                                      const float* bounds, int S, const float* t_lin, const float* jitter, int64_t* index, float* rays_d,
-                                      float* cam_pos, float* near, float* far, uint8_t* hit, float* z, void* stream)
-{
-    return guarded([&] {
-        if (!cams || !bounds || !t_lin || !index || !rays_d || !cam_pos || !near || !far || !hit || !z) throw_error("vanerf_ray_setup_views: null argument");
-        if (n_views <= 0 || n_views > 65535) throw_error("vanerf_ray_setup_views: n_views = %d outside [1, 65535]", n_views);
-        if (nx <= 0 || ny <= 0 || step_x <= 0 || step_y <= 0 || S < 2 || width <= 0)
-            throw_error("vanerf_ray_setup_views: bad grid (nx=%d ny=%d step=%d,%d S=%d)", nx, ny, step_x, step_y, S);
-        if ((long long)n_views * nx * ny * S >= VIEWS_MAX_ITEMS)
-            throw_error("vanerf_ray_setup_views: %d views of %d x %d rays at %d samples do not fit a 32-bit sample index", n_views, nx, ny, S);
+        if (!desc || !desc->t_lin_c || !index || !rays_d || !cam_pos || !near || !far || !hit || !z) throw_error("vanerf_ray_setup: null argument");
+        const VanerfPassDesc& d = *desc;
+        check_camera_source("vanerf_ray_setup", d);
+        const int V = d.n_views, S = d.Sc;
+        const bool grid = !d.pixels_xy;          // else the listed nx * ny pixels are the rays and the grid fields are not read
+        const bool rows = grid && !d.row_blocks; // else the blocks' first rows come from the table: y0 and step_y are not read
+        if (d.nx <= 0 || d.ny <= 0 || (grid && (d.step_x <= 0 || d.y_block <= 0)) || (rows && d.step_y <= 0) || S < 2 || d.width <= 0)
+            throw_error("vanerf_ray_setup: bad grid (nx=%d ny=%d step=%d,%d S=%d)", d.nx, d.ny, d.step_x, d.step_y, S);
+        if (grid && !rows && d.ny % d.y_block != 0) throw_error("vanerf_ray_setup: row_blocks: ny = %d is not a whole number of blocks of y_block = %d rows", d.ny, d.y_block);
+        if (d.cams && (long long)V * d.nx * d.ny * S >= VIEWS_MAX_ITEMS)
+            throw_error("vanerf_ray_setup: %d views of %d x %d rays at %d samples do not fit a 32-bit sample index", V, d.nx, d.ny, S);
         RayParams P{};
-        P.x0 = x0; P.y0 = y0; P.step_x = step_x; P.step_y = step_y; P.y_block = 1; P.nx = nx; P.ny = ny; P.width = width;
-        std::copy_n(bounds, 6, P.bounds);
-        P.S = S; P.t_lin = t_lin; P.jitter = jitter;
+        P.x0 = grid ? d.x0 : 0; P.y0 = rows ? d.y0 : 0; P.step_x = grid ? d.step_x : 1; P.step_y = rows ? d.step_y : 1; P.y_block = grid ? d.y_block : 1;
+        P.nx = grid ? d.nx : d.nx * d.ny; P.ny = grid ? d.ny : 1; P.width = d.width; P.pixels = d.pixels_xy; P.row_blocks = grid ? d.row_blocks : nullptr;
+        std::copy_n(d.bounds, 6, P.bounds);
+        P.S = S; P.t_lin = d.t_lin_c; P.jitter = d.jitter;
         P.index = index; P.rays_d = rays_d; P.cam_pos = cam_pos; P.near = near; P.far = far; P.hit = hit; P.z = z;
-        const int R = nx * ny;
-        hipLaunchKernelGGL(ray_setup_views_kernel, dim3((R + 255) / 256, n_views), dim3(256), 0, (hipStream_t)stream, P, cams);
+        const dim3 blocks((P.nx * P.ny + 255) / 256, V);
+        if (d.cams) { // P's own camera fields are not read
+            hipLaunchKernelGGL(ray_setup_views_kernel, blocks, dim3(256), 0, (hipStream_t)stream, P, d.cams);
+        } else {
+            std::copy_n(d.invK_T, 9, P.invK_T);
+            std::copy_n(d.RT, 12, P.RT);
+            P.znear = d.znear; P.zfar = d.zfar;
+            hipLaunchKernelGGL(ray_setup_kernel, blocks, dim3(256), 0, (hipStream_t)stream, P);
+        }
         HIP_CHECK(hipGetLastError());
     });
 }
 
-static void sample_points_impl(const char* who, const float* rays_d, const float* cam_pos, const float* z, int R, int S, int rays_per_view, float* pts, void* stream)
-{
-    if (!rays_d || !cam_pos || !z || !pts) throw_error("%s: null argument", who);
-    if (R <= 0 || S <= 0 || rays_per_view < 0) throw_error("%s: R=%d S=%d rays_per_view=%d", who, R, S, rays_per_view);
-    const long long n = (long long)R * S;
-    hipLaunchKernelGGL(sample_points_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, rays_d, cam_pos, z, n, S, rays_per_view, pts);
-    HIP_CHECK(hipGetLastError());
-}
-
-extern "C" int vanerf_sample_points(const float* rays_d, const float* cam_pos, const float* z, int R, int S, float* pts, void* stream)
-{
-    return guarded([&] { sample_points_impl("vanerf_sample_points", rays_d, cam_pos, z, R, S, 0, pts, stream); });
-}
-
-extern "C" int vanerf_sample_points_views(const float* rays_d, const float* cam_pos, const float* z, int R, int rays_per_view, int S, float* pts, void* stream)
+extern "C" int vanerf_sample_points(const float* rays_d, const float* cam_pos, const float* z, int R, int rays_per_view, int S, float* pts, void* stream)
 {
     return guarded([&] {
-        if (rays_per_view <= 0 || R % (rays_per_view > 0 ? rays_per_view : 1) != 0)
-            throw_error("vanerf_sample_points_views: R = %d is not a whole number of views of %d rays", R, rays_per_view);
-        sample_points_impl("vanerf_sample_points_views", rays_d, cam_pos, z, R, S, rays_per_view, pts, stream);
+        if (!rays_d || !cam_pos || !z || !pts) throw_error("vanerf_sample_points: null argument");
+        if (R <= 0 || S <= 0 || rays_per_view < 0) throw_error("vanerf_sample_points: R=%d S=%d rays_per_view=%d", R, S, rays_per_view);
+        if (rays_per_view && R % rays_per_view != 0) throw_error("vanerf_sample_points: R = %d is not a whole number of views of %d rays", R, rays_per_view);
+        const long long n = (long long)R * S;
+        hipLaunchKernelGGL(sample_points_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, rays_d, cam_pos, z, n, S, rays_per_view, pts);
+        HIP_CHECK(hipGetLastError());
     });
 }
 

@@ -572,7 +572,7 @@ class VANeRF(nn.Module):
 
     @torch.no_grad()
     def render_pifu_nerf_views(net, img_in, cam_in, hand_type, targets, cam_tars, sp_data={}, **config):
-        """render_pifu_nerf for several target views of one source frame in ONE pass (vanerf_render_pass_views): the callers of the reference
+        """render_pifu_nerf for several target views of one source frame in ONE pass (vanerf_render_pass with a camera table): the callers of the reference
         that render a frame from many cameras (render_novel_views, render_video, the validation and test steps, src/model.py:513-545, 140-197)
         call render_pifu_nerf once per camera.  cam_tars: list of cam_tar dicts of one width / height.  Evaluation only: eval mode, uniform=True,
         no rand_noise_std (a training patch has a pixel list and noise draws of its own and keeps the single-view pass).  Returns one dict per

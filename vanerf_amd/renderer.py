@@ -15,7 +15,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _ffi
-from ._ffi import VanerfFrame, VanerfMeshAccel, VanerfPassDesc, VanerfPassOut, VanerfViewsDesc, VanerfWeightTable, check, lib
+from ._ffi import VanerfFrame, VanerfMeshAccel, VanerfPassDesc, VanerfPassOut, VanerfWeightTable, check, lib
 
 NV, NV_HAND, NKPT = 1558, 779, 42
 
@@ -707,39 +707,11 @@ def _camera_floats(cam):
             [float(cam["znear"]), float(cam["zfar"])])
 
 
-def ray_setup(cam_tar, bounds, x0, y0, step, nx, ny, S, jitter=None, device=None, y_step=None, pixels=None, y_block=1, row_blocks=None):
-    """Pixel grid + rays + bbox clip + coarse depths (src/model.py:1191-1238, 1496-1570).
-    pixels: optional explicit (R,2) int32 device tensor of (x, y) (training patches); then nx*ny must equal R.
-    y_step, y_block: rows are y0 + (iy // y_block) * y_step + (iy % y_block) * step (multi-GPU shards: blocks of y_block rows).
-    row_blocks: optional (ny // y_block,) int32 device tensor, the first row of every block (shards dealt by cost: parallel.deal_blocks)."""
-    dev = device or bounds.device
-    inv_K_T, RT, (znear, zfar) = _camera_floats(cam_tar)
-    R = nx * ny
-    index = torch.empty(R, dtype=torch.int64, device=dev)
-    rays_d = torch.empty(R, 3, dtype=torch.float32, device=dev)
-    cam_pos = torch.empty(3, dtype=torch.float32, device=dev)
-    near, far = torch.empty(R, dtype=torch.float32, device=dev), torch.empty(R, dtype=torch.float32, device=dev)
-    hit = torch.empty(R, dtype=torch.uint8, device=dev)
-    z = torch.empty(R, S, dtype=torch.float32, device=dev)
-    t_lin = _t_lin(S, dev)
-    cam_args = (_farr(inv_K_T, 9), _farr(RT, 12), znear, zfar, _farr(host_copy(bounds).reshape(-1).tolist(), 6), int(S), _ptr(t_lin), _ptr(jitter, torch.float32),
-                _ptr(index), _ptr(rays_d), _ptr(cam_pos), _ptr(near), _ptr(far), _ptr(hit), _ptr(z), _stream())
-    if pixels is not None:
-        assert pixels.shape == (R, 2)
-        check(lib.vanerf_ray_setup_pixels(_ptr(pixels, torch.int32), R, int(cam_tar["width"]), *cam_args))
-    elif row_blocks is not None:
-        assert row_blocks.dtype == torch.int32 and row_blocks.is_cuda and row_blocks.numel() * int(y_block) == ny
-        check(lib.vanerf_ray_setup_blocks(_ptr(row_blocks, torch.int32), int(x0), int(step), int(y_block), int(nx), int(ny), int(cam_tar["width"]), *cam_args))
-    else:
-        check(lib.vanerf_ray_setup(int(x0), int(y0), int(step), int(y_step or step), int(y_block), int(nx), int(ny), int(cam_tar["width"]), *cam_args))
-    return dict(index=index, rays_d=rays_d, cam_pos=cam_pos, near=near, far=far, hit=hit, z=z)
-
-
-CAM_FLOATS = 24  # a row of the camera table of the *_views entry points: invK_T[9], RT[12], znear, zfar, one pad
+CAM_FLOATS = 24  # a row of the camera table (VanerfPassDesc.cams): invK_T[9], RT[12], znear, zfar, one pad
 
 
 def camera_table(cam_tars, dev):
-    """(V, 24) device table of the target cameras for vanerf_ray_setup_views / vanerf_render_pass_views.  Every number comes from _camera_floats,
+    """(V, 24) device table of the target cameras (VanerfPassDesc.cams).  Every number comes from _camera_floats,
     as the values the single-view path passes to the kernels do (Python float -> fp32 on both sides), so a view's rays are bit-identical to
     ray_setup's; one asynchronous host -> device copy for all of them (_staged_upload)."""
     if not cam_tars:
@@ -782,31 +754,72 @@ def _staged_upload(host, dev):
     return out
 
 
+def _pass_desc(cam, bounds, x0, y0, step, nx, ny, Sc, dev, Sf=0, fine=False, reuse_coarse=False, jitter=None, u=None, noise=(None, None), y_step=None,
+               pixels=None, y_block=1, row_blocks=None):
+    """The VanerfPassDesc of a ray setup or a pass.  cam: ONE target-camera dict -- the camera goes in by value, nothing is uploaded -- or a
+    LIST of them -- their camera_table, R = V * nx * ny rays, view-major.  Returns the descriptor and the tensors it points into (the caller
+    holds them until the call is enqueued)."""
+    table = camera_table(cam, dev) if isinstance(cam, (list, tuple)) else None
+    V = 1 if table is None else len(cam)
+    if jitter is not None and jitter.numel() != V * nx * ny * Sc or u is not None and u.numel() != V * nx * ny * Sf:
+        raise ValueError("jitter / u: one draw per sample of every view, (V*R, Sc) / (V*R, Sf)")
+    d = VanerfPassDesc()
+    d.x0, d.y0, d.step_x, d.step_y, d.y_block, d.nx, d.ny = int(x0), int(y0), int(step), int(y_step or step), int(y_block), int(nx), int(ny)
+    d.pixels_xy, d.row_blocks = _ptr(pixels, torch.int32), _ptr(row_blocks, torch.int32)
+    d.n_views, d.cams = V, _ptr(table, torch.float32)
+    if table is None:
+        inv_K_T, RT, (d.znear, d.zfar) = _camera_floats(cam)
+        d.invK_T, d.RT = _farr(inv_K_T, 9), _farr(RT, 12)
+    d.width = int((cam if table is None else cam[0])["width"])
+    d.bounds = _farr(host_copy(bounds).reshape(-1).tolist(), 6)
+    d.Sc, d.Sf, d.fine, d.reuse_coarse = int(Sc), int(Sf), int(bool(fine)), int(bool(reuse_coarse))
+    t_c, t_f = _t_lin(Sc, dev), _t_lin(Sf, dev) if fine else None
+    d.t_lin_c, d.t_lin_f = _ptr(t_c), _ptr(t_f)
+    d.jitter, d.u = _ptr(jitter, torch.float32), _ptr(u, torch.float32)
+    d.noise_c, d.noise_f = _ptr(noise[0], torch.float32), _ptr(noise[1], torch.float32)
+    return d, (table, t_c, t_f, jitter, u, *noise)
+
+
+def _run_ray_setup(d, dev):
+    """vanerf_ray_setup from a descriptor: flat (R, ...) tensors and cam_pos (3,) with a by-value camera; (V, R, ...) and cam_pos (V, 4: xyz + pad)
+    with a camera table."""
+    lead = (d.n_views, d.nx * d.ny) if d.cams else (d.nx * d.ny,)
+
+    def new(*tail, dtype=torch.float32):
+        return torch.empty(*lead, *tail, dtype=dtype, device=dev)
+
+    cam_pos = torch.zeros(d.n_views, 4, dtype=torch.float32, device=dev) if d.cams else torch.empty(3, dtype=torch.float32, device=dev)  # (the kernel writes xyz; the pad stays 0)
+    out = dict(index=new(dtype=torch.int64), rays_d=new(3), cam_pos=cam_pos, near=new(), far=new(), hit=new(dtype=torch.uint8), z=new(d.Sc))
+    check(lib.vanerf_ray_setup(byref(d), *(_ptr(t) for t in out.values()), _stream()))
+    return out
+
+
+def ray_setup(cam_tar, bounds, x0, y0, step, nx, ny, S, jitter=None, device=None, y_step=None, pixels=None, y_block=1, row_blocks=None):
+    """Pixel grid + rays + bbox clip + coarse depths (src/model.py:1191-1238, 1496-1570).
+    pixels: optional explicit (R,2) int32 device tensor of (x, y) (training patches); then nx*ny must equal R.
+    y_step, y_block: rows are y0 + (iy // y_block) * y_step + (iy % y_block) * step (multi-GPU shards: blocks of y_block rows).
+    row_blocks: optional (ny // y_block,) int32 device tensor, the first row of every block (shards dealt by cost: parallel.deal_blocks)."""
+    dev = device or bounds.device
+    assert pixels is None or pixels.shape == (nx * ny, 2)
+    assert pixels is not None or row_blocks is None or (row_blocks.is_cuda and row_blocks.numel() * int(y_block) == ny)
+    d, keep = _pass_desc(cam_tar, bounds, x0, y0, step, nx, ny, S, dev, jitter=jitter, y_step=y_step, pixels=pixels, y_block=y_block, row_blocks=row_blocks)
+    return _run_ray_setup(d, dev)
+
+
 def ray_setup_views(cam_tars, bounds, x0, y0, step, nx, ny, S, jitter=None, device=None, y_step=None):
-    """ray_setup for several target cameras on one pixel grid in ONE launch (vanerf_ray_setup_views): the tensors of ray_setup with a leading
-    view dimension -- index (V,R), rays_d (V,R,3), cam_pos (V,4: xyz + pad), near, far, hit (V,R), z (V,R,S) -- each view bit-identical to
+    """ray_setup for several target cameras on one pixel grid in ONE launch (a camera table): the tensors of ray_setup with a leading view
+    dimension -- index (V,R), rays_d (V,R,3), cam_pos (V,4: xyz + pad), near, far, hit (V,R), z (V,R,S) -- each view bit-identical to
     ray_setup(cam_tars[v], ...).  jitter: optional (V*R, S) draws."""
     dev = device or bounds.device
-    V, R = len(cam_tars), nx * ny
-    cams = camera_table(cam_tars, dev)
-    index = torch.empty(V, R, dtype=torch.int64, device=dev)
-    rays_d = torch.empty(V, R, 3, dtype=torch.float32, device=dev)
-    cam_pos = torch.zeros(V, 4, dtype=torch.float32, device=dev)  # (the kernel writes xyz; the pad stays 0)
-    near, far = torch.empty(V, R, dtype=torch.float32, device=dev), torch.empty(V, R, dtype=torch.float32, device=dev)
-    hit = torch.empty(V, R, dtype=torch.uint8, device=dev)
-    z = torch.empty(V, R, S, dtype=torch.float32, device=dev)
-    if jitter is not None and jitter.numel() != V * R * S:
-        raise ValueError("jitter: one draw per coarse sample of every view (V*R, S)")
-    check(lib.vanerf_ray_setup_views(_ptr(cams, torch.float32), V, int(x0), int(y0), int(step), int(y_step or step), int(nx), int(ny), int(cam_tars[0]["width"]),
-                                     _farr(host_copy(bounds).reshape(-1).tolist(), 6), int(S), _ptr(_t_lin(S, dev)), _ptr(jitter, torch.float32),
-                                     _ptr(index), _ptr(rays_d), _ptr(cam_pos), _ptr(near), _ptr(far), _ptr(hit), _ptr(z), _stream()))
-    return dict(index=index, rays_d=rays_d, cam_pos=cam_pos, near=near, far=far, hit=hit, z=z)
+    d, keep = _pass_desc(list(cam_tars), bounds, x0, y0, step, nx, ny, S, dev, jitter=jitter, y_step=y_step)
+    return _run_ray_setup(d, dev)
 
 
-def sample_points(rays_d, cam_pos, z):
+def sample_points(rays_d, cam_pos, z, rays_per_view=0):
+    """rays_per_view: 0 = one origin cam_pos (3,); else ray r starts at cam_pos[r // rays_per_view] of (V, 4)."""
     R, S = z.shape
     pts = torch.empty(R * S, 3, dtype=torch.float32, device=z.device)
-    check(lib.vanerf_sample_points(_ptr(rays_d, torch.float32), _ptr(cam_pos, torch.float32), _ptr(z, torch.float32), R, S, _ptr(pts), _stream()))
+    check(lib.vanerf_sample_points(_ptr(rays_d, torch.float32), _ptr(cam_pos, torch.float32), _ptr(z, torch.float32), R, int(rays_per_view), S, _ptr(pts), _stream()))
     return pts
 
 
@@ -947,6 +960,21 @@ def _pass_outputs(lead, Sc, Sf, fine, dev):
     return out, o
 
 
+def _run_pass(weights, frame, d, scratch=None):
+    """vanerf_render_pass from a descriptor.  scratch: optional uint8 device tensor of at least vanerf_render_pass_scratch bytes."""
+    dev = frame.verts3.device
+    out, o = _pass_outputs((d.n_views, d.nx * d.ny) if d.cams else (d.nx * d.ny,), d.Sc, d.Sf, d.fine, dev)
+    nbytes = int(lib.vanerf_render_pass_scratch(d.n_views, d.nx * d.ny, d.Sc, d.Sf, d.fine, 2 if d.reuse_coarse and d.noise_c else d.reuse_coarse))
+    if nbytes <= 0:
+        raise ValueError(f"{d.n_views} views of {d.nx} x {d.ny} rays at {d.Sc} + {d.Sf} samples: not a valid pass")
+    if scratch is None:
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    check(lib.vanerf_render_pass(weights.handle, byref(frame.c), byref(frame.accel.c), _ptr(frame.verts3, torch.float32), frame.verts3.shape[0],
+                                 _ptr(frame.faces, torch.int32), frame.faces.shape[0], byref(d), byref(o), _ptr(scratch, torch.uint8), scratch.numel(),
+                                 _ptr(frame.vertex_products(weights), torch.float32), _stream()))
+    return out
+
+
 def render_pass_c(weights, frame, cam_tar, bounds, x0, y0, step, nx, ny, sample_per_ray_c=64, sample_per_ray_f=64, fine=True, jitter=None, u=None,
                   noise_std=0.0, generator=None, y_step=None, reuse_coarse=True, pixels=None, y_block=1, noise_draws=None, row_blocks=None):
     """The same pass through the single C entry point vanerf_render_pass (include/vanerf_hip.h): one ctypes call enqueues every kernel of
@@ -954,71 +982,31 @@ def render_pass_c(weights, frame, cam_tar, bounds, x0, y0, step, nx, ny, sample_
     temporaries in one scratch block.  This is what a non-Python host binds; the model's eval / no-grad passes go through it too."""
     Sc, Sf, R = int(sample_per_ray_c), int(sample_per_ray_f), nx * ny
     dev = frame.verts3.device
-    inv_K_T, RT, (znear, zfar) = _camera_floats(cam_tar)
-    d = VanerfPassDesc()
-    d.x0, d.y0, d.step_x, d.step_y, d.y_block, d.nx, d.ny = int(x0), int(y0), int(step), int(y_step or step), int(y_block), int(nx), int(ny)
-    d.pixels_xy = _ptr(pixels, torch.int32)
-    d.row_blocks = _ptr(row_blocks, torch.int32)
-    d.width = int(cam_tar["width"])
-    d.invK_T, d.RT, d.znear, d.zfar = _farr(inv_K_T, 9), _farr(RT, 12), znear, zfar
-    d.bounds = _farr(host_copy(bounds).reshape(-1).tolist(), 6)
-    d.Sc, d.Sf, d.fine = Sc, Sf, int(bool(fine))
-    noise = None
+    noise = (None, None)
     if noise_std > 0.0:  # th.randn_like(rad) * rand_noise_std (src/model.py:1155-1156), drawn on the device (or handed in)
         draws = noise_draws if noise_draws is not None else (torch.randn(R * Sc, device=dev, generator=generator),
                                                              torch.randn(R * (Sc + Sf), device=dev, generator=generator) if fine else None)
         noise = tuple(None if t is None else (t.reshape(-1).to(dev, torch.float32) * noise_std).contiguous() for t in draws)
-    d.reuse_coarse = int(bool(reuse_coarse))  # (under noise: raw outputs once per point, eval_func per set of draws, as render_pass does)
-    t_c, t_f = _t_lin(Sc, dev), _t_lin(Sf, dev) if fine else None
-    d.t_lin_c, d.t_lin_f = _ptr(t_c), _ptr(t_f)
-    d.jitter, d.u = _ptr(jitter, torch.float32), _ptr(u, torch.float32)
-    d.noise_c, d.noise_f = (_ptr(noise[0]), _ptr(noise[1])) if noise is not None else (None, None)
-    out, o = _pass_outputs((R,), Sc, Sf, fine, dev)
-    nbytes = int(lib.vanerf_render_pass_scratch(R, Sc, Sf, d.fine, 2 if d.reuse_coarse and noise is not None else d.reuse_coarse))
-    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    check(lib.vanerf_render_pass(weights.handle, byref(frame.c), byref(frame.accel.c), _ptr(frame.verts3, torch.float32), frame.verts3.shape[0],
-                                 _ptr(frame.faces, torch.int32), frame.faces.shape[0], byref(d), byref(o), _ptr(scratch), nbytes,
-                                 _ptr(frame.vertex_products(weights), torch.float32), _stream()))
-    return out
+    # (reuse_coarse under noise: raw outputs once per point, eval_func per set of draws, as render_pass does)
+    d, keep = _pass_desc(cam_tar, bounds, x0, y0, step, nx, ny, Sc, dev, Sf, fine, reuse_coarse, jitter, u, noise, y_step, pixels, y_block, row_blocks)
+    return _run_pass(weights, frame, d)
 
 
 def render_pass_views_scratch(n_views, rays_per_view, Sc, Sf, fine=True, reuse_coarse=True):
-    """Bytes of scratch vanerf_render_pass_views needs for one group of views."""
-    return int(lib.vanerf_render_pass_views_scratch(int(n_views), int(rays_per_view), int(Sc), int(Sf), int(bool(fine)), int(bool(reuse_coarse))))
+    """Bytes of scratch vanerf_render_pass needs for one group of views."""
+    return int(lib.vanerf_render_pass_scratch(int(n_views), int(rays_per_view), int(Sc), int(Sf), int(bool(fine)), int(bool(reuse_coarse))))
 
 
 def render_pass_views(weights, frame, cam_tars, bounds, x0, y0, step, nx, ny, sample_per_ray_c=64, sample_per_ray_f=64, fine=True, jitter=None, u=None,
                       y_step=None, reuse_coarse=True, scratch=None):
-    """One pass over several target views of the same source frame (vanerf_render_pass_views): every kernel of render_pass_c once over
-    V * nx * ny rays.  cam_tars: list of the dicts render_pass takes, all of one width / height.  Returns the flat tensors of render_pass_c
+    """One pass over several target views of the same source frame (vanerf_render_pass with a camera table): every kernel of render_pass_c once
+    over V * nx * ny rays.  cam_tars: list of the dicts render_pass takes, all of one width / height.  Returns the flat tensors of render_pass_c
     with a leading view dimension; out[k][v] is bit-identical to render_pass_c(cam_tars[v], ...)[k].  jitter (V*R, Sc), u (V*R, Sf): optional
     draws (evaluation: no pixel list, no row blocks, no noise).  scratch: optional uint8 device tensor of at least render_pass_views_scratch
     bytes (a caller that renders group after group keeps one)."""
-    Sc, Sf, V, R = int(sample_per_ray_c), int(sample_per_ray_f), len(cam_tars), nx * ny
-    dev = frame.verts3.device
-    cams = camera_table(cam_tars, dev)
-    d = VanerfViewsDesc()
-    d.n_views = V
-    d.x0, d.y0, d.step_x, d.step_y, d.nx, d.ny = int(x0), int(y0), int(step), int(y_step or step), int(nx), int(ny)
-    d.width = int(cam_tars[0]["width"])
-    d.cams = _ptr(cams, torch.float32)
-    d.bounds = _farr(host_copy(bounds).reshape(-1).tolist(), 6)
-    d.Sc, d.Sf, d.fine, d.reuse_coarse = Sc, Sf, int(bool(fine)), int(bool(reuse_coarse))
-    t_c, t_f = _t_lin(Sc, dev), _t_lin(Sf, dev) if fine else None
-    d.t_lin_c, d.t_lin_f = _ptr(t_c), _ptr(t_f)
-    if jitter is not None and jitter.numel() != V * R * Sc or u is not None and u.numel() != V * R * Sf:
-        raise ValueError("jitter / u: one draw per sample of every view, (V*R, Sc) / (V*R, Sf)")
-    d.jitter, d.u = _ptr(jitter, torch.float32), _ptr(u, torch.float32)
-    out, o = _pass_outputs((V, R), Sc, Sf, fine, dev)
-    nbytes = render_pass_views_scratch(V, R, Sc, Sf, fine, reuse_coarse)
-    if nbytes <= 0:
-        raise ValueError(f"{V} views of {nx} x {ny} rays at {Sc} + {Sf} samples: not a valid multi-view pass")
-    if scratch is None:
-        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    check(lib.vanerf_render_pass_views(weights.handle, byref(frame.c), byref(frame.accel.c), _ptr(frame.verts3, torch.float32), frame.verts3.shape[0],
-                                       _ptr(frame.faces, torch.int32), frame.faces.shape[0], byref(d), byref(o), _ptr(scratch, torch.uint8), scratch.numel(),
-                                       _ptr(frame.vertex_products(weights), torch.float32), _stream()))
-    return out
+    d, keep = _pass_desc(list(cam_tars), bounds, x0, y0, step, nx, ny, int(sample_per_ray_c), frame.verts3.device, int(sample_per_ray_f), fine, reuse_coarse,
+                         jitter, u, y_step=y_step)
+    return _run_pass(weights, frame, d, scratch)
 
 
 def _rows(g):
