@@ -228,8 +228,34 @@ def test_hip_backward_at_the_real_patch_size():
     print(f"64x64 patch, 64 + 64 samples: worst relative L2 {worst[0]:.2e}, worst cosine {worst[1]:.6f}")
 
 
+def test_fused_backward_with_torch_composites_beyond_256_samples_per_ray():
+    """The mixed branch of the backward: vanerf_composite_backward takes at most 256 samples per ray, so at 136 + 128 samples (264 in the fine
+    composite) the composites are differentiated by the torch graph while the per-sample networks stay on the fused HIP backward.  Against the
+    PyTorch graph of the same step, with the bounds held at the real patch size (a larger sample count)."""
+    from vanerf_amd import hip_backward as HB, renderer as R
+    frame = synth.to_device(synth.make_frame(seed=3, tar_h=64, tar_w=64), "cuda")
+    calls = {"composite_backward": [], "run_block": [], "hip": None}  # per wrapped function: the hip_backward setting of the step that called it
+    orig = {"composite_backward": R.composite_backward, "run_block": HB.run_block}
+    res = []
+    try:
+        R.composite_backward = lambda *a, **k: (calls["composite_backward"].append(calls["hip"]), orig["composite_backward"](*a, **k))[1]
+        HB.run_block = lambda *a, **k: (calls["run_block"].append(calls["hip"]), orig["run_block"](*a, **k))[1]
+        for hip in (True, False):
+            net = _net(0.01)
+            net.kwargs["dr_kwargs"].update(sample_per_ray_c=136, sample_per_ray_f=128)
+            net.kwargs["hip_backward"] = calls["hip"] = hip
+            res.append(_grads_of_a_step(net, frame))
+            assert net._last_pass[0]["z_fine"].shape == (64, 264)
+    finally:
+        R.composite_backward, HB.run_block = orig["composite_backward"], orig["run_block"]
+    assert calls["composite_backward"] == [], "the composites of a 264-sample ray go through the torch graph"
+    assert calls["run_block"] and all(calls["run_block"]), "the fused per-sample backend ran, and only in the hip_backward step"
+    worst = _compare_backends(res[0], res[1], 5e-3, 0.9999)
+    print(f"8x8 patch, 136 + 128 samples: worst relative L2 {worst[0]:.2e}, worst cosine {worst[1]:.6f}")
+
+
 def test_chunked_backward_gives_the_same_gradients():
-    """torch_graph.PassGradient takes the gradient chunk of rays by chunk of rays when `grad_rays_per_chunk` is set, and the second stage of a
+    """pass_gradient.PassGradient takes the gradient chunk of rays by chunk of rays when `grad_rays_per_chunk` is set, and the second stage of a
     chunk block of samples by block when `grad_samples_per_block` is (bounded memory): the sum over chunks / blocks is the gradient of the
     whole patch (rays and samples are independent; the shared per-frame vertex table is closed once)."""
     frame = synth.to_device(synth.make_frame(seed=3, tar_h=64, tar_w=64), "cuda")

@@ -16,7 +16,6 @@ for _ in range(5):
     _, t_o = part(lambda: opt.step())
     rows.append((t_f, t_b, t_o))
 print("forward / backward / Adam (ms, synchronised, min over 5):", [round(min(r[i] for r in rows), 2) for i in range(3)])
-from vanerf_amd import hip_backward as HB, torch_graph as G
 import cProfile, pstats
 out = net(frame["img_in"], frame["cam_in"], frame["hand_type"], frame["targets"], None, None, n_views=1, sp_data=dict(frame["sp_data"]),
           dr_data=dr, src_foreground_mask=frame["src_foreground_mask"], bounds=frame["bounds"])["out"]["nerf"]

@@ -1,4 +1,5 @@
-"""Host side of the fused HIP backward pass of the per-sample networks (csrc/query_backward.hip).
+"""Host side of the fused HIP backward pass of the per-sample networks (csrc/query_backward.hip), driven block of
+samples by block by `pass_gradient.PassGradient`.
 
 For a block of samples two launches do what `torch_graph.networks_at` + `torch.autograd.grad` did in ~2 000 eager kernels:
 `vanerf_query_forward_spill` (the fp32 forward once more, spilling every layer's operands) and `vanerf_query_backward` (dX = W^T dY through

@@ -9,9 +9,9 @@ What runs where
   * n_views == 1 and batch == 1, as in both shipped configs (the non-spconv reference path is structurally single-view:
     src/networks.py:86,94; render_pifu_nerf hard-codes n_views = 1, src/model.py:1044).
 
-Training: `forward()` in train mode under autograd returns the HIP values with the gradients of `vanerf_amd.torch_graph` -- the same
-networks re-evaluated with torch ops at the samples of the HIP pass ("fused HIP forward + PyTorch autograd backward", SURVEY.md
-section 8 row f-4, first stage; a fused HIP backward is not built).  Under no_grad / eval nothing of that runs.  `forward()` returns the
+Training: `forward()` in train mode under autograd returns the HIP values with the gradients that `vanerf_amd.pass_gradient.PassGradient`
+takes at the samples of the HIP pass: the per-sample networks on the fused HIP backward (`hip_backward.py`), or
+re-evaluated with torch ops (`vanerf_amd.torch_graph`, the independent checker).  Under no_grad / eval nothing of that runs.  `forward()` returns the
 reference's `dict(loss, err_dict, out)`: the loss is `vanerf_amd.losses.compute_error` (src/utils.py:159-178) with `self.vgg_loss` as the
 perceptual term -- `None` unless the caller attaches one (the reference constructs a pretrained torchvision VGG19 there).
 A fresh module carries the reference's initial weights (`init_weights`, src/model.py:660-698; tests/golden/init_checksums.npz).
@@ -24,6 +24,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as thf
 
+from . import pass_gradient
 from . import renderer as R
 from .losses import compute_error
 from .synth import PACKED_PREFIXES
@@ -627,10 +628,9 @@ class VANeRF(nn.Module):
 
     def attach_autograd(self, out, img_in, feat_geo, feat_tex, targets, sp_data, fg_mask):
         """Replaces the differentiable entries of `out` (a batch_render_pifu_nerf result computed with _autograd=True) by tensors that
-        carry the HIP values and, in backward, the gradients of vanerf_amd.torch_graph evaluated at the same samples (same points, same
-        importance samples, same mesh queries, same noise draws) -- torch_graph.PassGradient: the graph is built and differentiated chunk of
-        rays by chunk of rays inside backward, so a training step never holds the activations of the whole patch."""
-        from . import torch_graph as G
+        carry the HIP values and, in backward, the gradients of the networks evaluated at the same samples (same points, same importance
+        samples, same mesh queries, same noise draws) -- pass_gradient.PassGradient: they are taken chunk of rays by chunk of rays and block
+        of samples by block inside backward, so a training step never holds the activations of the whole patch."""
         o, fd, cam_in = self._last_pass
         self._last_pass = (o, fd, cam_in) if getattr(self, "_keep_last_pass", False) else None  # tests inspect the pass
         self._hot_state()  # (refreshes the kept list; named_parameters() walks the encoders' ~1 700 entries too: 1 ms per step)
@@ -641,14 +641,14 @@ class VANeRF(nn.Module):
                  "vert_vis": fd.vert_vis, "kpt3d": sp_data["kpt3d"], "extrin": sp_data["extrin"]}
         keys = [k for k in ("tex_fg", "depth", "alpha", "tex_fg_fine", "depth_fine", "alpha_fine", "sdf") if k in out]
         spec = {"values": [out[k] for k in keys], "keys": keys, "names": names, "frame": frame, "pass": o, "sp_args": self.kwargs["sp_args"],
-                "rays_per_chunk": self.kwargs.get("grad_rays_per_chunk", G.GRAD_RAYS_PER_CHUNK),
-                "samples_per_block": self.kwargs.get("grad_samples_per_block", G.GRAD_SAMPLES_PER_BLOCK),
+                "rays_per_chunk": self.kwargs.get("grad_rays_per_chunk", pass_gradient.GRAD_RAYS_PER_CHUNK),
+                "samples_per_block": self.kwargs.get("grad_samples_per_block", pass_gradient.GRAD_SAMPLES_PER_BLOCK),
                 "graph_blocks": bool(self.kwargs.get("grad_graph_blocks", False)), "hip_backward": None}
         if self.kwargs.get("hip_backward", True):
             # the per-sample networks' gradient on the fused HIP backward (config key hip_backward, default on; off = the PyTorch graph of
             # torch_graph.networks_at, which stays as the independent checker): fp32 weights of this step, the pass's per-frame tables
             spec["hip_backward"] = {"w0": self.packed_weights("fp32"), "fdat": fd, "block": int(self.kwargs.get("hip_backward_block", 65536))}
-        for k, v in zip(keys, G.PassGradient.apply(spec, *leaves)):
+        for k, v in zip(keys, pass_gradient.PassGradient.apply(spec, *leaves)):
             out[k] = v
         return out
 
@@ -656,8 +656,8 @@ class VANeRF(nn.Module):
         """src/model.py:959-1024.  Returns dict(loss, err_dict, out={'nerf': out_nerf}) with the reference's out_nerf keys; the loss is
         compute_error(inter_loss=None, out_nerf, vggloss=self.vgg_loss, lambdas=cfg lambdas) as at src/model.py:1023."""
         assert len(im.shape) == 4 and len(cam["KRT"].shape) == 3
-        # Training under autograd ("fused HIP forward + PyTorch autograd backward", SURVEY.md section 8 row f-4, first stage): the values
-        # come from the HIP pass, the gradients from vanerf_amd.torch_graph evaluated at the same samples (attach_autograd below).
+        # Training under autograd (SURVEY.md section 8 row f-4): the values come from the HIP pass, the gradients from
+        # pass_gradient.PassGradient at the same samples (attach_autograd above).
         autograd = torch.is_grad_enabled() and self.training and any(p.requires_grad for p in self.parameters())
         dr_kwargs = self.kwargs.get("dr_kwargs", {})
         if autograd and self.kwargs.get("graph_encoders") and not self._encoders_graphed and im.is_cuda:

@@ -5,7 +5,7 @@ The values of a training step come from the HIP path (vanerf_amd.renderer.render
 the SAME sample points -- the points, importance samples, mesh queries (signed distance, visibility, nearest vertex) and noise draws
 are taken from the HIP pass, none of them carries gradient in the reference either (importance_sample runs under no_grad,
 src/model.py:1432; kaolin / pytorch3d inputs are constants) -- with torch ops on the device, so that gradients reach the module's
-parameters and the encoder feature maps.  `straight_through` then returns HIP values with this graph's gradients.
+parameters and the encoder feature maps.  `vanerf_amd.pass_gradient` drives it: which samples, in which blocks, into which accumulators.
 
 It is not a fallback: nothing here runs unless autograd is recording, and it cannot produce a frame on its own (it has no ray
 generation, no mesh query, no sampling).  Reference anchors: VANeRF.query / query_color src/model.py:748-957, eval_func 1140-1160,
@@ -16,15 +16,15 @@ import math
 import torch
 import torch.nn.functional as F
 
-from .renderer import _avg_pool3
+from . import renderer as R
 
 NUM_V = 779  # vertices per hand: the "other hand" twin of vertex i is (i + 779) mod 1558 (src/networks.py:30-32)
+COMPACT_VALID = True  # networks_at: evaluate the geometry branch on valid samples only (tests compare both settings)
 
 
 def _scatter_rows(n_rows, idx32, g, w=None):
     """sum over samples of w[i] g[i] into row idx[i] of a zero (n_rows, C) table: vanerf_scatter_add_rows (LDS-resident table slices; as
     torch's index_add_ -- contended global atomics, hundreds of samples per row -- this was 20 ms of a 73 ms step)."""
-    from . import renderer as R
     return R.scatter_add_rows(torch.zeros(n_rows, g.shape[1], dtype=torch.float32, device=g.device), idx32, g.contiguous(), w)
 
 
@@ -55,7 +55,6 @@ class _Bilinear(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         i32, wx, wy = ctx.saved_tensors
-        from . import renderer as R
         g = g.contiguous()
         out = torch.zeros(ctx.n_rows, g.shape[1], dtype=torch.float32, device=g.device)
         ws = ((1.0 - wx) * (1.0 - wy), wx * (1.0 - wy), (1.0 - wx) * wy, wx * wy)
@@ -223,7 +222,7 @@ def texture_vertex_table(P, vert_xy, feat_tex, img, pre="tex_vis_fusion."):
         x = torch.relu(F.layer_norm(x, [hw, hw], P[pre + name + ".1.weight"], P[pre + name + ".1.bias"], 1e-6))
         x = F.conv2d(x, P[pre + name + ".3.weight"], padding=1)
         x = torch.relu(F.layer_norm(x, [hw, hw], P[pre + name + ".4.weight"], P[pre + name + ".4.bias"], 1e-6))
-        return _avg_pool3(x).reshape(1, x.shape[1], 9)  # AdaptiveAvgPool2d(3) as two small products (renderer._avg_pool3; differentiable)
+        return R._avg_pool3(x).reshape(1, x.shape[1], 9)  # AdaptiveAvgPool2d(3) as two small products (renderer._avg_pool3; differentiable)
 
     gf = torch.cat([stack(img, "fconv4"), stack(feat_tex, "fconv3")], -1)  # (1, NV, 18): the conv stacks have NV output channels
     x = F.conv1d(gf, P[pre + "fconv_gt.0.weight"], padding=1)
@@ -245,10 +244,11 @@ def texture_fusion(P, table29, tex_xy, img_xy, idx, vert_vis, q_vis, latent24, p
     return _conv1(P, pre + "fconv.2.weight", torch.relu(_conv1(P, pre + "fconv.0.weight", g)))
 
 
-def networks_at(P, frame, pts, q_sdf, q_vis, knn, noise=None, sp_args=None):
+def networks_at(P, frame, pts, q_sdf, q_vis, knn, noise=None, sp_args=None, compact_valid=None):
     """VANeRF.query + query_color + eval_func at N given points -> (N,5) [alpha, sdf, r, g, b] with gradient.
     frame: dict(cam, img (1,3,H,W), feat_geo [2 maps], feat_tex, fg_mask (1,1,H,W), verts (NV,3), vert_vis (NV,), kpt3d, extrin,
-    table29 (optional, from texture_vertex_table)); q_sdf (N,), q_vis (N,) in {0,1}, knn (N,) int64, noise (N,) or None."""
+    table29 (optional, from texture_vertex_table)); q_sdf (N,), q_vis (N,) in {0,1}, knn (N,) int64, noise (N,) or None; compact_valid: the
+    valid-sample compaction below on / off, None = COMPACT_VALID as it stands at the call."""
     sp = sp_args or {"sp_level": 3, "scale": 1.0, "sigma": 0.1}
     cam = frame["cam"]
     xy, z = project(pts, cam)
@@ -266,7 +266,7 @@ def networks_at(P, frame, pts, q_sdf, q_vis, knn, noise=None, sp_args=None):
     # positional encoding and the geometry MLP (85 % of the per-sample arithmetic) are evaluated on the valid samples only; same values,
     # same gradients.  The texture branch below still runs on every sample: eval_func does not mask the colour.
     keep = None
-    if COMPACT_VALID:
+    if COMPACT_VALID if compact_valid is None else compact_valid:
         keep = mask.view(-1).nonzero().view(-1)
         if keep.numel() == mask.shape[0]:
             keep = None
@@ -308,338 +308,3 @@ def composite(P, rgba, z, mesh_sdf):
     w = c * torch.cumprod(torch.cat([torch.ones_like(c[:, :1]), 1.0 - c[:, :-1]], -1), -1)
     acc = w.sum(-1)
     return (rgba[..., 2:] * w[..., None]).sum(-2), (z * w).sum(-1) / (acc + 1e-8), acc, (rgba[..., 1] * w).sum(-1) / (acc + 1e-8)
-
-
-def straight_through(value, graph):
-    """HIP value, this module's gradient."""
-    return graph + (value - graph).detach()
-
-
-# Rays per chunk of the backward pass (PassGradient); None = the whole patch at once.  Chunking by rays repeats both stages per chunk; the block
-# size below bounds memory more cheaply (it only cuts the second stage).  Measured on the 64x64 patch at 64 + 64 samples (
-# tools/perf_train_step.py, one MI355X; 524 k network evaluations per step): whole patch 42 ms / 7.5 GiB; blocks of 262 144 samples 53 ms / 4.2 GiB;
-# 131 072: 63 ms / 2.5 GiB.  With 288 GB of HBM the default is speed; model config keys `grad_rays_per_chunk`, `grad_samples_per_block`.
-# (bf16 operands for this graph's GEMMs were measured too: 9 % faster, and the parameter gradients moved by 4e-2 relative -- dropped.)
-GRAD_RAYS_PER_CHUNK = None
-# Samples per block of the second stage of the backward pass (PassGradient); None = all samples of a chunk of rays in one block.
-GRAD_SAMPLES_PER_BLOCK = None
-
-
-COMPACT_VALID = True  # networks_at: evaluate the geometry branch on valid samples only (tests compare both settings)
-
-
-class _BlockGraph:
-    """Second stage of PassGradient for blocks of ONE fixed size, captured once as a HIP graph and replayed block after block (config key
-    `grad_graph_blocks`, with `grad_samples_per_block`).  Small blocks bound the step's memory, but eagerly every block re-launches the
-    graph's ~2 000 kernels and the step turns host-bound (131 072 samples per block: 63 ms); replayed, a block costs the host a few input
-    copies.  What capture needs: inputs, per-frame tensors and gradient accumulators at fixed addresses (copied in, read out), parameters that
-    stay where they are (in-place optimizer updates; a moved parameter re-captures), no data-dependent shapes (the valid-sample compaction of
-    networks_at is off inside: every sample of a block is evaluated)."""
-    cache = {}
-
-    def __init__(self, leaves, names, frame, table, block, two, with_noise, sp_args):
-        dev = table.device
-        f32 = torch.float32
-        self.block, self.two = block, two
-        self.pts, self.qs = torch.zeros(block, 3, device=dev), torch.zeros(block, device=dev)
-        self.qv, self.knn = torch.zeros(block, dtype=frame_dtype(frame, "q_vis"), device=dev), torch.zeros(block, dtype=torch.int32, device=dev)
-        self.nz = torch.zeros(block, device=dev) if with_noise else None
-        self.nz2 = torch.zeros(block, device=dev) if two else None
-        self.d, self.d2 = torch.zeros(block, 5, device=dev), (torch.zeros(block, 5, device=dev) if two else None)
-        # leaves: parameters are read where they live; the encoders' feature maps (new tensors every step) and the vertex table get fixed homes
-        self.static = {n: (t.detach().clone() if n.startswith("@") else t.detach()).requires_grad_(True) for n, t in zip(names, leaves)}
-        self.table = table.detach().clone().requires_grad_(True)
-        self.frame = {k: (v.detach().clone() if torch.is_tensor(v) else v) for k, v in frame.items() if k not in ("cam", "feat_geo", "feat_tex", "table29")}
-        self.frame["cam"] = {k: (v.detach().clone() if torch.is_tensor(v) else v) for k, v in frame["cam"].items()}
-        order = list(self.static.values()) + [self.table]
-        flat = torch.zeros(sum(t.numel() for t in order), dtype=f32, device=dev)
-        self.flat, self.acc, at = flat, [], 0
-        for t in order:
-            self.acc.append(flat[at:at + t.numel()].view(t.shape))
-            at += t.numel()
-        P = {k: v for k, v in self.static.items() if not k.startswith("@")}
-        fr = dict(self.frame, feat_geo=[self.static["@feat_geo0"], self.static["@feat_geo1"]], feat_tex=self.static["@feat_tex"], table29=self.table)
-
-        def body():
-            global COMPACT_VALID
-            keep, COMPACT_VALID = COMPACT_VALID, False
-            try:
-                noise = (self.nz, self.nz2) if two else self.nz
-                outs = networks_at(P, fr, self.pts, self.qs, self.qv, self.knn.long(), noise, sp_args)
-                grads = torch.autograd.grad(list(outs) if two else outs, order, [self.d, self.d2] if two else self.d, allow_unused=True)
-            finally:
-                COMPACT_VALID = keep
-            for a, g in zip(self.acc, grads):
-                if g is not None:
-                    a.add_(g)
-
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side), torch.enable_grad():
-            for _ in range(2):  # warm-up outside capture (library handles, workspaces, autotuning)
-                body()
-        torch.cuda.current_stream().wait_stream(side)
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.enable_grad(), torch.cuda.graph(self.graph):
-            body()
-
-    def begin(self, leaves, names, frame, table):
-        """New step: this step's feature maps, per-frame tensors and vertex table into their fixed homes, accumulators to zero."""
-        with torch.no_grad():
-            for n, t in zip(names, leaves):
-                if n.startswith("@"):
-                    self.static[n].copy_(t)
-            self.table.copy_(table)
-            for k, v in self.frame.items():
-                if torch.is_tensor(v):
-                    v.copy_(frame[k])
-            for k, v in self.frame["cam"].items():
-                if torch.is_tensor(v):
-                    v.copy_(frame["cam"][k])
-            self.flat.zero_()
-
-    def run(self, pts, qs, qv, knn, nz, nz2, d, d2):
-        n = pts.shape[0]
-        with torch.no_grad():
-            for dst, src in ((self.pts, pts), (self.qs, qs), (self.qv, qv), (self.knn, knn), (self.nz, nz), (self.nz2, nz2), (self.d, d), (self.d2, d2)):
-                if dst is not None:
-                    dst[:n].copy_(src)
-            if n < self.block:  # the last, shorter block: the tail keeps old samples with zero output gradients -- they add nothing
-                self.d[n:].zero_()
-                if self.d2 is not None:
-                    self.d2[n:].zero_()
-        self.graph.replay()
-
-    def results(self):
-        out = self.flat.clone()
-        res, at = [], 0
-        for a in self.acc:
-            res.append(out[at:at + a.numel()].view(a.shape))
-            at += a.numel()
-        return res
-
-    @classmethod
-    def get(cls, leaves, names, frame, table, block, two, with_noise, sp_args):
-        cam = frame["cam"]
-        key = (block, two, with_noise, tuple(sorted(sp_args.items())), tuple(t.data_ptr() for n, t in zip(names, leaves) if not n.startswith("@")),
-               tuple(tuple(t.shape) for n, t in zip(names, leaves) if n.startswith("@")), tuple((k, float(v)) for k, v in sorted(cam.items()) if not torch.is_tensor(v)),
-               tuple((k, tuple(v.shape)) for k, v in sorted(frame.items()) if torch.is_tensor(v)), str(table.device))
-        if key not in cls.cache:
-            cls.cache.clear()  # one configuration at a time (each holds a block's activations in its private pool)
-            cls.cache[key] = cls(leaves, names, frame, table, block, two, with_noise, sp_args)
-        return cls.cache[key]
-
-
-def frame_dtype(frame, key):
-    return torch.uint8
-
-
-class PassGradient(torch.autograd.Function):
-    """forward: the HIP pass's images, unchanged.  backward: the gradients of this module's graph at the samples of that pass with respect to
-    the leaves (the module's parameters and the encoders' feature maps), in two stages: the composites are differentiated at the pass's own
-    per-sample values (HIP), which gives the gradient with respect to every sample's network outputs; then the per-sample networks are
-    evaluated and differentiated block of samples by block (coarse batch, fine batch, optionally smaller blocks / chunks of rays): samples
-    are independent, so the gradient is the sum over blocks, and only one block's activations exist at a time.  The per-frame vertex table of
-    TexVisFusion (two conv stacks over the source image) is shared by all samples: its graph is built once, the chunks accumulate the
-    gradient with respect to the table, and one backward through the stacks closes the step."""
-
-    @staticmethod
-    def forward(ctx, spec, *leaves):
-        ctx.spec = spec
-        ctx.save_for_backward(*leaves)
-        return tuple(v.clone() for v in spec["values"])
-
-    @staticmethod
-    def backward(ctx, *gouts):
-        spec, names = ctx.spec, ctx.spec["names"]
-        import os, time
-        marks = [] if os.environ.get("VANERF_TIME_BACKWARD") else None  # diagnostic: synchronised wall time per section (tools/perf_train_parts.py)
-
-        def mark(what):
-            if marks is not None:
-                torch.cuda.synchronize()
-                marks.append((what, time.perf_counter()))
-        mark("start")
-        with torch.enable_grad():
-            loc = [t.detach().requires_grad_(True) for t in ctx.saved_tensors]
-            L = dict(zip(names, loc))
-            P = {k: v for k, v in L.items() if not k.startswith("@")}
-            frame = dict(spec["frame"], feat_geo=[L["@feat_geo0"], L["@feat_geo1"]], feat_tex=L["@feat_tex"])
-            total = [None] * len(loc)
-
-            def accumulate(grads):
-                for i, g in enumerate(grads):
-                    if g is not None:
-                        total[i] = g if total[i] is None else total[i] + g
-
-            hip_state = None
-            table_graph = texture_vertex_table(P, project_vertices(frame["verts"], frame["cam"]), frame["feat_tex"], frame["img"])
-            table = table_graph.detach().requires_grad_(True)
-            g_table = torch.zeros_like(table)
-            o, keys = spec["pass"], spec["keys"]
-            R = o["z"].shape[0]
-            c, f = o["coarse"], o.get("fine")
-            step = spec["rays_per_chunk"] or R
-            for r0 in range(0, R, step):
-                r1 = min(R, r0 + step)
-                # (1) the composites, differentiated at the HIP pass's own per-sample values: a small graph over (rays, samples, 5) tensors that
-                #     yields the gradient with respect to every sample's [alpha, sdf, r, g, b] (and to sigmoid_beta)
-                cf = o.get("coarse_in_fine") if f is not None else None
-                n_fine = 0 if f is None else (o["z_fine"].shape[1] if o.get("z_fine") is not None else f["rgba"].shape[1])
-                if spec.get("hip_backward") is not None and max(c["rgba"].shape[1], n_fine) <= 256:
-                    # vanerf_composite_backward: one launch per composite instead of this graph's ~500 (rays x samples x 5 element-wise kernels, a
-                    # cumprod whose backward blocks the host); sigmoid_beta is the handle's device copy (this step's parameter, clamped)
-                    from . import renderer as HR
-                    w0 = spec["hip_backward"]["w0"]
-                    gk = {}
-                    for k, g in zip(keys, gouts):
-                        if g is not None:
-                            gk[k] = (g.reshape(3, -1).t()[r0:r1] if k.startswith("tex_fg") else g.reshape(-1)[r0:r1]).contiguous()
-                    with torch.no_grad():
-                        d_rc, _, db = HR.composite_backward(w0, c["rgba"][r0:r1], o["z"][r0:r1], c["q_sdf"][r0:r1], gk.get("tex_fg"), gk.get("depth"), gk.get("alpha"))
-                        grads = [d_rc]
-                        if f is not None:
-                            gf = (gk.get("tex_fg_fine"), gk.get("depth_fine"), gk.get("alpha_fine"), gk.get("sdf"))
-                            if o.get("fine_src") is not None:
-                                rcf = c["rgba"] if cf is None else cf["rgba"]
-                                d_rcf, d_rf, db_f = HR.composite_backward(w0, rcf[r0:r1], o["z_fine"][r0:r1], c["q_sdf"][r0:r1], *gf, rgba_n=f["rgba"][r0:r1],
-                                                                          sdf_n=f["q_sdf"][r0:r1], src=o["fine_src"][r0:r1])
-                                if cf is None:
-                                    grads = [d_rc + d_rcf, d_rf]
-                                else:
-                                    grads = [d_rc, d_rf, d_rcf]
-                            else:
-                                d_rf, _, db_f = HR.composite_backward(w0, f["rgba"][r0:r1], o["z_fine"][r0:r1], f["q_sdf"][r0:r1], *gf)
-                                grads = [d_rc, d_rf]
-                            db = db.sum() + db_f.sum()
-                        else:
-                            db = db.sum()
-                        pb = P["sigmoid_beta"]
-                        g_beta = [None] * len(loc)
-                        g_beta[names.index("sigmoid_beta")] = (db * (pb.detach() >= 2e-3).to(db.dtype)).reshape(pb.shape)  # clamp(min = 2e-3)'s derivative
-                    accumulate(g_beta)
-                    per_sample = grads  # (only its length is used below)
-                    mark("composite backward (HIP)")
-                else:
-                    rc = c["rgba"][r0:r1].detach().clone().requires_grad_(True)
-                    col, dep, acc, _ = composite(P, rc, o["z"][r0:r1], c["q_sdf"][r0:r1])
-                    outs = {"tex_fg": col, "depth": dep, "alpha": acc}
-                    per_sample = [rc]
-                    if f is not None:
-                        rf = f["rgba"][r0:r1].detach().clone().requires_grad_(True)
-                        per_sample.append(rf)
-                        rgba_f, msdf = rf, f["q_sdf"][r0:r1]
-                        if o.get("fine_src") is not None:  # the pass re-used the coarse evaluations: merge [coarse | new] by the origin map
-                            src = o["fine_src"][r0:r1].long()
-                            take = torch.where(src >= 0, src, rc.shape[1] + (-src - 1))
-                            rcf = rc
-                            if cf is not None:  # (training noise: the coarse points carry other draws inside the fine batch)
-                                rcf = cf["rgba"][r0:r1].detach().clone().requires_grad_(True)
-                                per_sample.append(rcf)
-                            rgba_f = torch.gather(torch.cat([rcf, rf], 1), 1, take[..., None].expand(-1, -1, 5))
-                            msdf = torch.gather(torch.cat([c["q_sdf"][r0:r1], f["q_sdf"][r0:r1]], 1), 1, take)
-                        col, dep, acc, sdf = composite(P, rgba_f, o["z_fine"][r0:r1], msdf)
-                        outs.update({"tex_fg_fine": col, "depth_fine": dep, "alpha_fine": acc, "sdf": sdf})
-                    pairs = []
-                    for k, g in zip(keys, gouts):
-                        if g is None:
-                            continue
-                        # images are (1,3,h,w) / (1,h,w) over the patch's rays in row-major order: the chunk's rays are a slice of the flattened image
-                        gk = g.reshape(3, -1).t()[r0:r1] if k.startswith("tex_fg") else g.reshape(-1)[r0:r1]
-                        pairs.append((outs[k], gk))
-                    mark("table graph + composite forward")
-                    grads = torch.autograd.grad([a for a, _ in pairs], per_sample + loc, [b for _, b in pairs], allow_unused=True)
-                    accumulate(grads[len(per_sample):])
-                    mark("composite backward")
-                    del outs, pairs, col, dep, acc
-                # (2) the per-sample networks, one block of samples after the other (samples are independent): only one block's graph exists at a
-                #     time, which is what bounds the step's memory -- the coarse and the fine batch are never alive together
-                d_per = list(grads[:len(per_sample)])
-                # every sample of the chunk in one list: [coarse | new]; a second (noise, gradient) column exists when the coarse points appear
-                # in the fine composite with other draws (zeros for the new samples there)
-                parts = [(c, d_per[0], None if cf is None else (cf["noise"], d_per[2]))]
-                if f is not None:
-                    parts.append((f, d_per[1], None))
-                cols = {"pts": [], "q_sdf": [], "q_vis": [], "knn": [], "noise": [], "d": [], "noise2": [], "d2": []}
-                for part, d, second in parts:
-                    S = part["pts"].shape[0] // R
-                    sl = slice(r0 * S, r1 * S)
-                    n = sl.stop - sl.start
-                    cols["pts"].append(part["pts"][sl]); cols["q_sdf"].append(part["q_sdf"].reshape(-1)[sl]); cols["q_vis"].append(part["q_vis"][sl])
-                    cols["knn"].append(part["knn"][sl])
-                    cols["noise"].append(None if part["noise"] is None else part["noise"][sl])
-                    cols["d"].append(torch.zeros(n, 5, device=part["pts"].device) if d is None else d.reshape(-1, 5))
-                    if cf is not None:
-                        cols["noise2"].append(torch.zeros(n, device=part["pts"].device) if second is None else second[0][sl])
-                        cols["d2"].append(torch.zeros(n, 5, device=part["pts"].device) if second is None or second[1] is None else second[1].reshape(-1, 5))
-                cat = lambda k: torch.cat(cols[k], 0) if len(cols[k]) > 1 else cols[k][0]
-                pts_a, qs_a, qv_a, knn_a, d_a = cat("pts"), cat("q_sdf"), cat("q_vis"), cat("knn"), cat("d")
-                nz_a = None if cols["noise"][0] is None else cat("noise")
-                nz2_a, d2_a = (cat("noise2"), cat("d2")) if cf is not None else (None, None)
-                n_all = pts_a.shape[0]
-                if spec.get("hip_backward") is not None:
-                    # the fused HIP backward (csrc/query_backward.hip, hip_backward.py): two launches and twenty matrix products per block of samples
-                    from . import hip_backward as HB
-                    hb = spec["hip_backward"]
-                    if hip_state is None:  # the first chunk of rays is a full one: its sample count bounds every later block
-                        blk = min(int(hb["block"]), (n_all + 31) // 32 * 32)
-                        ws = HB.workspace(blk, pts_a.device)
-                        ws.dw.zero_()
-                        hip_state = {"ws": ws, "blk": blk, "scatter": HB.InputScatter(frame, pts_a.device)}
-                    ws, blk = hip_state["ws"], hip_state["blk"]
-                    mark("sample lists")
-                    with torch.no_grad():
-                        pts_a, qs_a, qv_a, knn_a = pts_a.contiguous(), qs_a.contiguous(), qv_a.contiguous(), knn_a.contiguous()
-                        hip_state["scatter"].prepare(project(pts_a, frame["cam"])[0], knn_a)
-                        mark("taps")
-                        for b0 in range(0, n_all, blk):
-                            sl = slice(b0, min(n_all, b0 + blk))
-                            ig, nb = HB.run_block(ws, hb["w0"], hb["fdat"], pts_a[sl], qs_a[sl], qv_a[sl], knn_a[sl], d_a[sl],
-                                                  None if nz_a is None else nz_a[sl], None if d2_a is None else d2_a[sl], None if nz2_a is None else nz2_a[sl])
-                            hip_state["scatter"].add(sl, ig)
-                    mark("fused backward blocks")
-                    continue
-                block = spec.get("samples_per_block") or n_all
-                if spec.get("graph_blocks") and spec.get("samples_per_block"):
-                    runner = _BlockGraph.get(list(ctx.saved_tensors), names, frame, table, block, nz2_a is not None, nz_a is not None, spec["sp_args"])
-                    runner.begin(list(ctx.saved_tensors), names, frame, table)
-                    for b0 in range(0, n_all, block):
-                        sl = slice(b0, min(n_all, b0 + block))
-                        runner.run(pts_a[sl], qs_a[sl], qv_a[sl], knn_a[sl], None if nz_a is None else nz_a[sl], None if nz2_a is None else nz2_a[sl],
-                                   d_a[sl], None if d2_a is None else d2_a[sl])
-                    res = runner.results()
-                    accumulate(res[:-1])
-                    g_table += res[-1]
-                    continue
-                for b0 in range(0, n_all, block):
-                    sl = slice(b0, min(n_all, b0 + block))
-                    noise = None if nz_a is None else nz_a[sl]
-                    if nz2_a is not None:
-                        noise = (noise, nz2_a[sl])
-                    outs_b = networks_at(P, dict(frame, table29=table), pts_a[sl], qs_a[sl], qv_a[sl], knn_a[sl].long(), noise, spec["sp_args"])
-                    if nz2_a is not None:
-                        g_block = torch.autograd.grad(list(outs_b), loc + [table], [d_a[sl], d2_a[sl]], allow_unused=True)
-                    else:
-                        g_block = torch.autograd.grad(outs_b, loc + [table], d_a[sl], allow_unused=True)
-                    del outs_b
-                    accumulate(g_block[:-1])
-                    if g_block[-1] is not None:
-                        g_table += g_block[-1]
-            if hip_state is not None:
-                from . import hip_backward as HB
-                sc = hip_state["scatter"]
-                by_name = dict(HB.parameter_gradients(hip_state["ws"], P))
-                by_name["@feat_geo0"], by_name["@feat_geo1"], by_name["@feat_tex"] = sc.map_gradient("map0"), sc.map_gradient("map1"), sc.map_gradient("tex")
-                accumulate([by_name.get(n) for n in names])
-                # the per-vertex tables are bilinear samples of the maps at the projected vertices (src/networks.py:86-87, 94-95): their gradient goes
-                # back through that gather (and table29's through the per-frame stacks below)
-                vert_xy = project_vertices(frame["verts"], frame["cam"])
-                tabs = [sample_map(frame["feat_geo"][0], vert_xy), sample_map(frame["feat_geo"][1], vert_xy)]
-                accumulate(torch.autograd.grad(tabs, loc, [sc.acc["vtab0"], sc.acc["vtab1"]], allow_unused=True))
-                g_table = g_table + sc.acc["table29"]
-            mark("parameter gradients")
-            accumulate(torch.autograd.grad(table_graph, loc, g_table, allow_unused=True))
-            mark("per-frame stacks backward")
-        if marks:
-            print("PassGradient.backward sections (ms):", [(b[0], round(1e3 * (b[1] - a[1]), 2)) for a, b in zip(marks, marks[1:])])
-        return (None, *total)
