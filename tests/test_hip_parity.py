@@ -384,7 +384,7 @@ def test_ray_setup(R):
 @pytest.mark.parametrize("beta", [0.1, 0.01, 1e-3])
 def test_composite(R, beta):
     g = torch.Generator().manual_seed(4)
-    Rn, S = 500, 128
+    Rn, S = 501, 128  # not a multiple of the 4 rays of a block: the last block is partial
     rgba = torch.rand(Rn, S, 5, generator=g)
     rgba[..., 0] = torch.relu(torch.randn(Rn, S, generator=g)) * 0.05
     z = torch.sort(torch.rand(Rn, S, generator=g) * 0.3 + 0.8, -1)[0]

@@ -281,7 +281,7 @@ __global__ __launch_bounds__(IM_BLOCK) void importance_merge_kernel(const float*
         float den = cn - cp;
         if (den < 1e-5f) den = 1.0f;
         const float s = zp + ((uk - cp) / den) * (zq - zp);
-        smp[(size_t)k * IM_BLOCK] = s;
+        if (!MID) smp[(size_t)k * IM_BLOCK] = s; // only the merge reads the draws back (the mid-point form has no LDS for them)
         z_new[(size_t)r * Sf + k] = s;
         if (idx_out) idx_out[(size_t)r * Sf + k] = in;
         sorted = sorted && (s >= prev);
@@ -901,8 +901,8 @@ extern "C" int vanerf_importance_sample(const float* contrib_inner, const float*
         if (!u && !t_lin) throw_error("vanerf_importance_sample: need u (random) or t_lin (uniform)");
         if (R <= 0 || n_bins < 1 || Sf < 1) throw_error("vanerf_importance_sample: R=%d bins=%d Sf=%d", R, n_bins, Sf);
         const int Sc = n_bins + 2;
-        const size_t lds = (size_t)IM_BLOCK * sizeof(float) * (2 * (size_t)(Sc - 1) + 2 * (size_t)Sf);
-        if (lds > 160 * 1024) throw_error("vanerf_importance_sample: %d bins + %d samples per ray exceed LDS", n_bins, Sf);
+        const size_t lds = (size_t)IM_BLOCK * sizeof(float) * 2 * (size_t)(Sc - 1); // cdf and mid-points; the draws go straight to z_new
+        if (lds > 160 * 1024) throw_error("vanerf_importance_sample: %d bins per ray exceed LDS", n_bins);
         if (lds > 64 * 1024)
             HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(importance_merge_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         hipLaunchKernelGGL(importance_merge_kernel<true>, dim3((R + IM_BLOCK - 1) / IM_BLOCK), dim3(IM_BLOCK), lds, (hipStream_t)stream,
