@@ -196,6 +196,36 @@ def test_hip_backward_matches_the_pytorch_graph(precision):
     print(f"HIP backward vs PyTorch graph [{precision}]: worst relative L2 {worst[0]:.2e}, worst cosine {worst[1]:.6f}")
 
 
+def test_the_clamp_of_sigmoid_beta_in_the_step():
+    """sdf_activation clamps sigmoid_beta at 2e-3.  The torch stage gets the clamp's derivative from torch.clamp itself, the HIP stage applies it
+    on the host to the kernel's d / d clamp(sigmoid_beta) (pass_gradient._composite_gradients_hip): below the clamp both give exactly 0 and every
+    other gradient agrees as in test_hip_backward_matches_the_pytorch_graph (the composites run at 1 / beta^2 = 2.5e5); above it the two
+    gradients of sigmoid_beta agree within that test's bar."""
+    frame = synth.to_device(synth.make_frame(seed=3, tar_h=64, tar_w=64), "cuda")
+
+    def both_backends(beta):
+        res = []
+        for hip in (True, False):
+            net = _net(0.01)
+            with torch.no_grad():
+                net.sigmoid_beta.fill_(beta)
+            net.kwargs["hip_backward"] = hip
+            res.append(_grads_of_a_step(net, frame))
+            assert float(net.sigmoid_beta) == float(torch.tensor(beta))  # the step left the parameter where it was: below the clamp
+        return res
+
+    below = both_backends(1e-3)
+    for g, name in zip(below, ("hip", "torch")):
+        assert g["sigmoid_beta"] is not None and torch.equal(g["sigmoid_beta"], torch.zeros_like(g["sigmoid_beta"])), (name, g["sigmoid_beta"])
+    worst = _compare_backends(below[0], below[1], 2e-3, 0.9999)
+    print(f"sigmoid_beta = 1e-3 (clamped): worst relative L2 {worst[0]:.2e}, worst cosine {worst[1]:.6f}")
+    above = both_backends(0.01)
+    a, b = above[0]["sigmoid_beta"], above[1]["sigmoid_beta"]
+    print(f"sigmoid_beta = 0.01: d loss / d sigmoid_beta {a.item():.6e} (HIP stage) {b.item():.6e} (torch stage)")
+    assert a.abs().item() > 0.0 and b.abs().item() > 0.0
+    _compare_backends(above[0], above[1], 2e-3, 0.9999)  # sigmoid_beta among them: |a - b| <= 2e-3 max(|a|, |b|) + 1e-4 + 1e-5 gmax
+
+
 def test_hip_backward_at_the_real_patch_size():
     """The same comparison at the training configuration of configs/vanerf.json: a 64x64 patch, 64 + 64 samples per ray (524 288 network
     evaluations, eight blocks of 65 536 samples through the HIP backward)."""

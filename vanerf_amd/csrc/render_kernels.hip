@@ -546,6 +546,9 @@ extern "C" int vanerf_eval_func(const float* raw_a, const uint8_t* valid_a, cons
 // ray, the forward quantities recomputed as composite_wave_kernel computes them, then with gw_i = dL/dw_i
 //   dL/dsigma_i = dist_i (gw_i T_{i+1} - sum_{k>i} gw_k w_k)        (T_{i+1} = T_i (1 - c_i); no division by (1 - c_i): exact zeros stay zeros, which is what
 //                                                                   torch.cumprod's backward branches -- and blocks the host -- for)
+// T_{i+1} is built from exp(-sigma_i dist_i) itself, not from 1 - c_i with c_i already rounded next to 1: behind a nearly opaque sample (the last one has
+// dist = 1e10) 1 - c_i keeps no more than 6e-8 absolute, and gw_i T_{i+1} -- what autograd gets from exp's own saved result -- was up to 1e-3 of the ray's
+// largest gradient off.
 //   dL/dx_i = -dL/dsigma_i s(1 - s) / beta^2,  x = rgba0 + mesh_sdf, s = sigmoid(-x / beta);   dL/dbeta = sum_i dL/dsigma_i (s(1 - s) x / beta^3 - s / beta^2)
 //   dL/drgb_i = g_color w_i,   dL/drgba1_i = g_sdf w_i / (acc + 1e-8)
 // with gw_i = g_color . rgb_i + g_alpha + g_depth (z_i - depth) / (acc + 1e-8) + g_sdf (rgba1_i - sdf) / (acc + 1e-8).  The gradients go back to the table a
@@ -568,13 +571,13 @@ __global__ __launch_bounds__(256) void composite_backward_kernel(const float* __
     const float* mb = msdf_b ? msdf_b + (size_t)r * Sb : nullptr;
     const int32_t* sr = src ? src + (size_t)r * S : nullptr;
     const float* zr = z + (size_t)r * S;
-    float c[SPL], zi[SPL], dist[SPL], x[SPL], sg[SPL], q1[SPL], q2[SPL], q3[SPL], q4[SPL];
+    float keep[SPL], zi[SPL], dist[SPL], x[SPL], sg[SPL], q1[SPL], q2[SPL], q3[SPL], q4[SPL]; // keep_i = 1 - c_i = exp(-sigma_i dist_i)
     int from[SPL]; // where the sample's gradient goes: >= 0 entry of table a, < 0 entry ~from of table b
     float lane_keep = 1.0f;
 #pragma unroll
     for (int k = 0; k < SPL; ++k) {
         const int i = lane * SPL + k;
-        c[k] = 0.0f; zi[k] = 0.0f; dist[k] = 0.0f; x[k] = 0.0f; sg[k] = 0.0f; q1[k] = q2[k] = q3[k] = q4[k] = 0.0f; from[k] = 0;
+        keep[k] = 1.0f; zi[k] = 0.0f; dist[k] = 0.0f; x[k] = 0.0f; sg[k] = 0.0f; q1[k] = q2[k] = q3[k] = q4[k] = 0.0f; from[k] = 0;
         if (i < S) {
             zi[k] = zr[i];
             dist[k] = i + 1 < S ? zr[i + 1] - zi[k] : 1e10f;
@@ -590,10 +593,10 @@ __global__ __launch_bounds__(256) void composite_backward_kernel(const float* __
             }
             x[k] = q[0] + m;
             sg[k] = 1.0f / (1.0f + expf(-(-x[k] / beta))); // sigmoid(-x / beta)
-            c[k] = 1.0f - expf(-(sg[k] / beta) * dist[k]);
+            keep[k] = expf(-(sg[k] / beta) * dist[k]);
             q1[k] = q[1]; q2[k] = q[2]; q3[k] = q[3]; q4[k] = q[4];
         }
-        lane_keep *= 1.0f - c[k];
+        lane_keep *= keep[k];
     }
     float incl = lane_keep;
 #pragma unroll
@@ -609,8 +612,8 @@ __global__ __launch_bounds__(256) void composite_backward_kernel(const float* __
         float T = T0;
 #pragma unroll
         for (int k = 0; k < SPL; ++k) {
-            w[k] = c[k] * T;
-            T = T * (1.0f - c[k]);
+            w[k] = (1.0f - keep[k]) * T;
+            T = T * keep[k];
             Tn[k] = T;
             ca += w[k]; cs += q1[k] * w[k]; cd += zi[k] * w[k];
         }
