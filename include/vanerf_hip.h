@@ -494,6 +494,53 @@ int vanerf_surface_emit(const float* f, const float* rgb, const float origin[3],
                         const void* scratch, int64_t scratch_bytes, int64_t n_verts, int64_t n_tris, float* verts, float* colors, int32_t* tris,
                         int64_t cap_verts, int64_t cap_tris, void* stream);
 
+/* The learned surface along lines: sample f on n lines base[i] + t dir[i] (base[n][3], dir[n][3] fp32), bracket the
+ * crossing of f = iso nearest to t = 0 on every line and refine it with further values of f.  surface.register_surface runs these calls on the
+ * lines through the MANO vertices along their vertex normals and moves every vertex to its crossing.  All pointers are DEVICE pointers.
+ *
+ *     vanerf_vertex_normals: normals[nv][3] = the unit vertex normals of the mesh (verts[nv][3], faces[nf][3] int32) with the arithmetic of the
+ *         vertex pass of vanerf_render_vis: the face normal cross(v2 - v1, v0 - v1) added once per corner that names the vertex, a face with an
+ *         index outside [0, nv) left out; one wave per vertex, lane l summing faces l, l + 64, ... in ascending order, a fixed xor butterfly over
+ *         the lanes, then x / max(|x|, 1e-6).  The bits are those of floats 12..14 of vanerf_render_vis's scratch record.  One launch.
+ *     vanerf_line_points: pts[n K][3], line-major.  t_dev == NULL: t_k = fmaf((float)k, dt, t0), k = 0 ... K - 1 (t0 finite, dt finite and
+ *         positive), and the point is fmaf(t_k, dir, base) per axis.  t_dev != NULL: K must be 1, t = t_dev[i] (t0 and dt are not read), and a
+ *         non-finite t is read as 0: the point is the base, bit for bit.  1 <= K <= VANERF_LINE_MAX_SAMPLES, n >= 0 (n = 0: a no-op),
+ *         n K < 2^31.  One launch.
+ *     vanerf_line_bracket: f[n][K] (and rgb[n][K][3], or NULL) at the points of the first form, 2 <= K -> state[n][VANERF_LINE_STATE_FLOATS].
+ *         - clean value g = isfinite(f) ? f : FLT_MAX; a sample is INSIDE iff g < iso (the extractor's rule, so f == iso is outside);
+ *         - a pair (k, k + 1) is a crossing iff exactly one of its ends is inside; its weight is w = clamp((iso - g_k) / (g_k+1 - g_k), 0, 1)
+ *           in fp32, clamp(x, lo, hi) = fminf(fmaxf(x, lo), hi), and its parameter tc = fmaf(w, dt, t_k);
+ *         - the line's crossing is the pair with the smallest |tc|, a tie going to the smaller k;
+ *         - the record (floats, by the VANERF_LS_* offsets below): ta, tb = t_k, t_k+1; ga, gb = g_k, g_k+1; rgb_a, rgb_b = the rgb of the
+ *           two samples (zeros without rgb); found = 1; t_est = fmaf(w, tb - ta, ta); rgb_est = rgb_a + w (rgb_b - rgb_a), product and sum
+ *           rounded separately; t_next = fmaf(clamp(w, 0.125, 0.875), tb - ta, ta): where f is to be evaluated next;
+ *         - a line without a crossing: found = 0, t_est = t_next = NaN, zeros elsewhere.
+ *         One wave per line, the samples over the lanes (K > 64 in rounds of 64); one launch.  state must be 16-byte aligned.
+ *     vanerf_line_refine: f_new[n] (and rgb_new[n][3], or NULL: the colours of the record stay) = the field at every line's t_next.  On a found
+ *         line, with g the clean value: if g is on the same side of iso as ga, (ta, ga, rgb_a) <- (t_next, g, rgb_new), otherwise (tb, gb, rgb_b)
+ *         take them; then w, t_est, rgb_est and t_next are recomputed with the expressions above.  Other lines are left as they are.  The bracket
+ *         always has exactly one end inside, and it shrinks to at most 7/8 of its width per call (up to the rounding of t_next).  One launch.
+ *     vanerf_line_state_floats: VANERF_LINE_STATE_FLOATS, for a binding that does not read this header.
+ * All work goes to `stream`; no allocation, no host synchronisation, no atomics: every record is a function of its own line, the same bits
+ * every call whatever state held.  Arguments are checked before any launch.                                                                */
+#define VANERF_LINE_MAX_SAMPLES 256
+#define VANERF_LINE_STATE_FLOATS 16
+#define VANERF_LS_TA 0
+#define VANERF_LS_TB 1
+#define VANERF_LS_GA 2
+#define VANERF_LS_GB 3
+#define VANERF_LS_RGB_A 4   /* 4..6 */
+#define VANERF_LS_FOUND 7   /* 1.0f or 0.0f */
+#define VANERF_LS_RGB_B 8   /* 8..10 */
+#define VANERF_LS_T_EST 11
+#define VANERF_LS_RGB_EST 12 /* 12..14 */
+#define VANERF_LS_T_NEXT 15
+int vanerf_line_state_floats(void);
+int vanerf_vertex_normals(const float* verts, int nv, const int32_t* faces, int nf, float* normals, void* stream);
+int vanerf_line_points(const float* base, const float* dir, int n, int K, float t0, float dt, const float* t_dev, float* pts, void* stream);
+int vanerf_line_bracket(const float* f, const float* rgb, int n, int K, float t0, float dt, float iso, float* state, void* stream);
+int vanerf_line_refine(const float* f_new, const float* rgb_new, int n, float iso, float* state, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

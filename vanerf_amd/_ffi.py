@@ -124,6 +124,11 @@ _SIGS = {
     "vanerf_surface_count": (c_int, [_FP, c_int, c_int, c_int, c_float, c_void_p, c_int64, _FP, c_void_p]),
     "vanerf_surface_emit": (c_int, [_FP, _FP, POINTER(c_float), POINTER(c_float), c_int, c_int, c_int, c_float, c_void_p, c_int64, c_int64, c_int64,
                                     _FP, _FP, _FP, c_int64, c_int64, c_void_p]),
+    "vanerf_line_state_floats": (c_int, []),
+    "vanerf_vertex_normals": (c_int, [_FP, c_int, _FP, c_int, _FP, c_void_p]),
+    "vanerf_line_points": (c_int, [_FP, _FP, c_int, c_int, c_float, c_float, _FP, _FP, c_void_p]),
+    "vanerf_line_bracket": (c_int, [_FP, _FP, c_int, c_int, c_float, c_float, c_float, _FP, c_void_p]),
+    "vanerf_line_refine": (c_int, [_FP, _FP, c_int, c_float, _FP, c_void_p]),
 }
 EXPORTS = tuple(_SIGS)
 

@@ -5,6 +5,7 @@
 // pytorch3d is not a dependency, so parity against it is unpinned (as for the mesh queries, mesh_kernels.hip).  The restatement the tests
 // hold these kernels to is the fp64 `ref_render` of tests/test_vis_render.py.  Built with -ffp-contract=off.
 #include "common.h"
+#include "vertex_normal.h"
 
 using namespace vanerf;
 
@@ -14,23 +15,11 @@ constexpr int VR_VERT_FLOATS = 16; // scratch record per vertex, see vanerf_rend
 constexpr int VR_BLOCK = 256;
 constexpr int VR_T = 16;           // pixel tile edge: one block per 16 x 16 tile
 
-__device__ __forceinline__ bool face_ok(int i0, int i1, int i2, int nv)
-{
-    return (unsigned)i0 < (unsigned)nv && (unsigned)i1 < (unsigned)nv && (unsigned)i2 < (unsigned)nv;
-}
-
-// x / max(|x|, 1e-6) (torch.nn.functional.normalize, eps 1e-6)
-__device__ __forceinline__ float3 normalize_eps(float3 a)
-{
-    const float n = fmaxf(sqrtf((a.x * a.x + a.y * a.y) + a.z * a.z), 1e-6f);
-    return make_float3(a.x / n, a.y / n, a.z / n);
-}
-
 __device__ __forceinline__ float dot3(float3 a, float3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
 
-// Vertex pass: one wave per vertex.  Lane 0 projects the vertex; the wave sums the normals of the vertex's faces (Meshes.verts_normals_packed:
-// n_f = cross(v2 - v1, v0 - v1) added into each corner), lane l taking faces l, l + 64, ... in ascending order, then a fixed butterfly over the
-// lanes -- no atomics, the same bits every call.  A face with a vertex index outside [0, nv) is left out here and draws nothing in the raster pass.
+// Vertex pass: one wave per vertex.  Lane 0 projects the vertex; the wave sums the normals of the vertex's faces (wave_normal_sum,
+// vertex_normal.h, which vanerf_vertex_normals shares) -- no atomics, the same bits every call.  A face with a vertex index outside [0, nv) is
+// left out here and draws nothing in the raster pass.
 __global__ __launch_bounds__(VR_BLOCK) void vis_vertex_kernel(const float* __restrict__ V, int nv, const int32_t* __restrict__ F, int nf,
                                                               const float* __restrict__ vert_vis, const float* __restrict__ Rm,
                                                               const float* __restrict__ Tv, const float* __restrict__ focal,
@@ -39,24 +28,7 @@ __global__ __launch_bounds__(VR_BLOCK) void vis_vertex_kernel(const float* __res
     const int lane = threadIdx.x & 63;
     const int v = blockIdx.x * (VR_BLOCK / 64) + (threadIdx.x >> 6);
     if (v >= nv) return; // whole waves leave together
-    float3 n = make_float3(0.0f, 0.0f, 0.0f);
-    for (int f = lane; f < nf; f += 64) {
-        const int i0 = F[3 * f], i1 = F[3 * f + 1], i2 = F[3 * f + 2];
-        if ((i0 != v && i1 != v && i2 != v) || !face_ok(i0, i1, i2, nv)) continue;
-        const float3 a = make_float3(V[3 * i0], V[3 * i0 + 1], V[3 * i0 + 2]);
-        const float3 b = make_float3(V[3 * i1], V[3 * i1 + 1], V[3 * i1 + 2]);
-        const float3 c = make_float3(V[3 * i2], V[3 * i2 + 1], V[3 * i2 + 2]);
-        const float3 e1 = make_float3(c.x - b.x, c.y - b.y, c.z - b.z), e2 = make_float3(a.x - b.x, a.y - b.y, a.z - b.z);
-        const float3 nf3 = make_float3(e1.y * e2.z - e1.z * e2.y, e1.z * e2.x - e1.x * e2.z, e1.x * e2.y - e1.y * e2.x);
-        // a face that names the vertex twice adds its normal twice (index_add over the three corners)
-        const float k = (float)((i0 == v) + (i1 == v) + (i2 == v));
-        n.x += k * nf3.x; n.y += k * nf3.y; n.z += k * nf3.z;
-    }
-    for (int m = 32; m >= 1; m >>= 1) {
-        n.x += __shfl_xor(n.x, m);
-        n.y += __shfl_xor(n.y, m);
-        n.z += __shfl_xor(n.z, m);
-    }
+    float3 n = wave_normal_sum(V, nv, F, nf, v, lane);
     if (lane != 0) return;
     n = normalize_eps(n);
     const float3 p = make_float3(V[3 * v], V[3 * v + 1], V[3 * v + 2]);

@@ -626,6 +626,13 @@ class VANeRF(nn.Module):
         from . import surface
         return surface.extract_surface(self, tr_batch, resolution=resolution, voxel_size=voxel_size, iso=iso, colors=colors, **kwargs)
 
+    @torch.no_grad()
+    def register_surface(self, tr_batch, **kwargs):
+        """The frame's MANO mesh with every vertex moved along its normal onto the learned surface (vanerf_amd.surface.register_surface,
+        DESIGN.md section 0f): the same 1558 vertices and faces for every frame, with the learned colour and the displacement per vertex."""
+        from . import surface
+        return surface.register_surface(self, tr_batch, **kwargs)
+
     def attach_autograd(self, out, img_in, feat_geo, feat_tex, targets, sp_data, fg_mask):
         """Replaces the differentiable entries of `out` (a batch_render_pifu_nerf result computed with _autograd=True) by tensors that
         carry the HIP values and, in backward, the gradients of the networks evaluated at the same samples (same points, same importance

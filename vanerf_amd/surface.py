@@ -5,6 +5,10 @@ f = alpha + mesh_sdf into a density (src/model.py:1158, 1480-1481), so the hand 
 regular grid with the calls the render pass makes per sample (mesh query, validity partition, per-sample networks); extract_surface runs
 marching tetrahedra over it (vanerf_surface_count / vanerf_surface_emit) and returns an indexed, welded mesh on the device.  The only wait
 for the GPU is the read of the two counts between those calls (and of `bounds` when it is a device tensor: it goes to the kernels by value).
+
+register_surface (vanerf_amd/csrc/surface_lines.hip) answers "where did each MANO vertex move to": it samples f on the
+line through every vertex along its normal (field_at_points), brackets the crossing of f = iso nearest to the vertex (line_bracket), refines
+it (line_refine) and returns the input mesh with its vertices moved there: the same faces for every frame, no host read of its own.
 """
 import math
 from ctypes import c_float, c_void_p
@@ -115,15 +119,44 @@ def _default_bounds(fd, bounds, given):
     return frame_bounds(fd.verts3)  # what the dataset hands the ray clip and mask_at_box: the vertices' box, z widened by 0.05
 
 
+def field_at_points(net, frame, pts, want_rgb=False, slab_points=SLAB_POINTS, out=None):
+    """f = alpha + mesh_sdf at arbitrary points: pts (n, 3) fp32 on the device -> f (n,) fp32[, rgb (n, 3)].  net, frame: as field_on_grid takes
+    them.  Per chunk of at most slab_points points: vanerf_mesh_query_accel with the 1-NN vertex -> vanerf_query_order -> vanerf_query_samples
+    (raw = 0, no noise) -> vanerf_field_values.  Every step is a per-point function, so neither the chunk size nor a point's neighbours change
+    a bit.  out: (f, rgb or None), contiguous device tensors to fill instead of new ones."""
+    from . import renderer as R
+    slab_points = int(slab_points)
+    if slab_points < 1:
+        raise ValueError(f"slab_points: expected a positive number of points, got {slab_points}")
+    weights, fd, _ = _resolve(net, frame)
+    if not (torch.is_tensor(pts) and pts.dim() == 2 and pts.shape[1] == 3):
+        raise ValueError("pts: expected a tensor (n, 3)")
+    _dev_ptr(pts, torch.float32, "pts")
+    dev, n = fd.verts3.device, pts.shape[0]
+    if pts.device != dev:
+        raise ValueError(f"pts: expected a tensor on the frame's device {dev}")
+    with torch.cuda.device(dev), torch.no_grad():
+        f, rgb = out if out is not None else (torch.empty(n, dtype=torch.float32, device=dev),
+                                              torch.empty(n, 3, dtype=torch.float32, device=dev) if want_rgb else None)
+        if tuple(f.shape) != (n,) or (rgb is not None and tuple(rgb.shape) != (n, 3)):
+            raise ValueError(f"out: expected f ({n},) and rgb ({n}, 3) or None")
+        fp, rp = _dev_ptr(f, torch.float32, "out f"), _dev_ptr(rgb, torch.float32, "out rgb")
+        for a in range(0, n, slab_points):
+            p = pts[a:a + slab_points]
+            sdf, vis, knn = R.mesh_query_accel(fd.accel, fd.verts3, fd.faces, fd.vert_vis, p)
+            o = R.query_samples(weights, fd, p, sdf, vis, knn, order=R.query_order(fd, p))
+            check(lib.vanerf_field_values(c_void_p(o.data_ptr()), c_void_p(sdf.data_ptr()), p.shape[0], c_void_p(fp.value + 4 * a),
+                                          None if rp is None else c_void_p(rp.value + 12 * a), _stream()))
+    return (f, rgb) if want_rgb else f
+
+
 def field_on_grid(net, frame, bounds=None, dims=None, voxel_size=None, want_rgb=False, slab_points=SLAB_POINTS):
     """f = alpha + mesh_sdf on a regular grid -> (nz, ny, nx) fp32 on the device[, rgb (nz, ny, nx, 3)].
 
     net, frame: a VANeRF module and a tr_batch of device tensors, or a renderer.PackedWeights handle and a renderer.FrameData: the handle and
     frame data of the render pass, in the handle's precision.  bounds: (2, 3)-shaped, default the frame's own (dr_data['bounds'], or the
     vertices' box as mask_at_box.frame_bounds gives it); dims / voxel_size: grid_spec.  Per slab of whole z-layers with at most slab_points
-    points (at least one layer): vanerf_grid_points -> vanerf_mesh_query_accel with the 1-NN vertex -> vanerf_query_order ->
-    vanerf_query_samples (raw = 0, no noise) -> vanerf_field_values.  Every step is a per-point function, so the slab size changes no bit."""
-    from . import renderer as R
+    points (at least one layer): vanerf_grid_points -> field_at_points.  Every step is a per-point function, so the slab size changes no bit."""
     if (dims is None) == (voxel_size is None):
         raise ValueError("give exactly one of dims and voxel_size")
     slab_points = int(slab_points)
@@ -139,10 +172,7 @@ def field_on_grid(net, frame, bounds=None, dims=None, voxel_size=None, want_rgb=
         for z0 in range(0, nz, layers):
             k = min(layers, nz - z0)
             pts = grid_points(origin, spacing, (nx, ny, nz), z0, k, dev)
-            sdf, vis, knn = R.mesh_query_accel(fd.accel, fd.verts3, fd.faces, fd.vert_vis, pts)
-            out = R.query_samples(weights, fd, pts, sdf, vis, knn, order=R.query_order(fd, pts))
-            check(lib.vanerf_field_values(c_void_p(out.data_ptr()), c_void_p(sdf.data_ptr()), pts.shape[0], c_void_p(f[z0:z0 + k].data_ptr()),
-                                          None if rgb is None else c_void_p(rgb[z0:z0 + k].data_ptr()), _stream()))
+            field_at_points(weights, fd, pts, want_rgb, pts.shape[0], out=(f[z0:z0 + k].view(-1), None if rgb is None else rgb[z0:z0 + k].view(-1, 3)))
     return (f, rgb) if want_rgb else f
 
 
@@ -200,6 +230,135 @@ def extract_surface(net, tr_batch, resolution=128, voxel_size=None, iso=0.0, col
     return {"verts": verts, "faces": faces, "colors": cols, "mano_verts": fd.verts3, "mano_faces": fd.faces}
 
 
+LINE_STATE_FLOATS = 16  # VANERF_LINE_STATE_FLOATS
+_LINE_FIELDS = {"ta": 0, "tb": 1, "ga": 2, "gb": 3, "rgb_a": slice(4, 7), "found": 7, "rgb_b": slice(8, 11), "t_est": 11, "rgb_est": slice(12, 15),
+                "t_next": 15}  # the VANERF_LS_* offsets of include/vanerf_hip.h
+MAX_LINE_SAMPLES = 256  # VANERF_LINE_MAX_SAMPLES
+
+
+def _lines(t, what, n=None):
+    if not (torch.is_tensor(t) and t.dim() == 2 and t.shape[1] == 3 and (n is None or t.shape[0] == n)):
+        raise ValueError(f"{what}: expected a tensor ({'n' if n is None else n}, 3)")
+    return _dev_ptr(t, torch.float32, what)
+
+
+def vertex_normals(verts, faces):
+    """vanerf_vertex_normals: the unit vertex normals (nv, 3) of a mesh, verts (nv, 3) fp32 and faces (nf, 3) int32 on the device, with the
+    bits render_vis's vertex pass computes."""
+    vp = _lines(verts, "verts")
+    if not (torch.is_tensor(faces) and faces.dim() == 2 and faces.shape[1] == 3):
+        raise ValueError("faces: expected a tensor (nf, 3)")
+    fp = _dev_ptr(faces, torch.int32, "faces")
+    if faces.device != verts.device:
+        raise ValueError("faces: expected a tensor on the vertices' device")
+    with torch.cuda.device(verts.device):
+        normals = torch.empty_like(verts)
+        check(lib.vanerf_vertex_normals(vp, verts.shape[0], fp, faces.shape[0], c_void_p(normals.data_ptr()), _stream()))
+    return normals
+
+
+def line_points(base, direction, samples=1, t0=0.0, dt=1.0, t=None):
+    """vanerf_line_points: the points base + t direction of n lines (base, direction: (n, 3) fp32 on the device) as (n samples, 3), line-major.
+    t = None: t_k = fmaf(k, dt, t0), k < samples.  t: (n,) fp32 on the device, one parameter per line (samples must be 1); a non-finite
+    entry gives the base itself."""
+    samples = int(samples)
+    bp = _lines(base, "base")
+    n = base.shape[0]
+    dp = _lines(direction, "direction", n)
+    if t is not None and not (torch.is_tensor(t) and tuple(t.shape) == (n,)):
+        raise ValueError(f"t: expected a tensor ({n},)")
+    tp = _dev_ptr(t, torch.float32, "t")
+    if any(x is not None and x.device != base.device for x in (direction, t)):
+        raise ValueError("direction and t: expected tensors on the device of base")
+    with torch.cuda.device(base.device):
+        pts = torch.empty(n * max(samples, 0), 3, dtype=torch.float32, device=base.device)
+        check(lib.vanerf_line_points(bp, dp, n, samples, float(t0), float(dt), tp, c_void_p(pts.data_ptr()), _stream()))
+    return pts
+
+
+def line_bracket(f, t0, dt, iso=0.0, rgb=None):
+    """vanerf_line_bracket: f (n, K) fp32 on the device, the field at line_points(..., K, t0, dt)[, rgb (n, K, 3)] -> the state tensor
+    (n, LINE_STATE_FLOATS) with the bracket of the crossing of f = iso nearest to t = 0 on every line (line_state names its columns)."""
+    if not (torch.is_tensor(f) and f.dim() == 2):
+        raise ValueError("f: expected a tensor (n, K)")
+    n, K = (int(d) for d in f.shape)
+    fp = _dev_ptr(f, torch.float32, "f")
+    if rgb is not None and (tuple(rgb.shape) != (n, K, 3) or rgb.device != f.device):
+        raise ValueError(f"rgb: expected ({n}, {K}, 3) on {f.device}")
+    rp = _dev_ptr(rgb, torch.float32, "rgb")
+    with torch.cuda.device(f.device):
+        state = torch.empty(n, LINE_STATE_FLOATS, dtype=torch.float32, device=f.device)
+        check(lib.vanerf_line_bracket(fp, rp, n, K, float(t0), float(dt), float(iso), c_void_p(state.data_ptr()), _stream()))
+    return state
+
+
+def line_refine(state, f_new, iso=0.0, rgb_new=None):
+    """vanerf_line_refine: one round in place on `state` (returned) with f_new (n,) fp32[, rgb_new (n, 3)], the field at state's t_next."""
+    if not (torch.is_tensor(state) and state.dim() == 2 and state.shape[1] == LINE_STATE_FLOATS):
+        raise ValueError(f"state: expected a tensor (n, {LINE_STATE_FLOATS})")
+    sp = _dev_ptr(state, torch.float32, "state")
+    n = state.shape[0]
+    if not (torch.is_tensor(f_new) and tuple(f_new.shape) == (n,)):
+        raise ValueError(f"f_new: expected a tensor ({n},)")
+    fp = _dev_ptr(f_new, torch.float32, "f_new")
+    if rgb_new is not None and tuple(rgb_new.shape) != (n, 3):
+        raise ValueError(f"rgb_new: expected ({n}, 3)")
+    rp = _dev_ptr(rgb_new, torch.float32, "rgb_new")
+    if any(x is not None and x.device != state.device for x in (f_new, rgb_new)):
+        raise ValueError("f_new and rgb_new: expected tensors on the device of state")
+    with torch.cuda.device(state.device):
+        check(lib.vanerf_line_refine(fp, rp, n, float(iso), sp, _stream()))
+    return state
+
+
+def line_state(state):
+    """Named views of a state tensor (n, LINE_STATE_FLOATS): ta, tb, ga, gb, found, t_est, t_next (n,) and rgb_a, rgb_b, rgb_est (n, 3)."""
+    if not (torch.is_tensor(state) and state.dim() == 2 and state.shape[1] == LINE_STATE_FLOATS):
+        raise ValueError(f"state: expected a tensor (n, {LINE_STATE_FLOATS})")
+    return {k: state[:, at] for k, at in _LINE_FIELDS.items()}
+
+
+def register_surface(net, tr_batch, band=0.004, samples=9, refine=4, iso=0.0, colors=True):
+    """The MANO mesh registered onto the learned surface: every vertex v moves along its vertex normal n to the crossing of f = iso nearest to
+    it on the line v + t n, |t| <= band.  Steps: vertex_normals -> line_points (t0 = -band, dt = 2 band / (samples - 1)) -> field_at_points ->
+    line_bracket -> `refine` rounds of (line_points at t_next -> field_at_points -> line_refine) -> line_points at t_est.
+
+    -> {"verts" (nv, 3): a vertex without a crossing keeps its MANO position bit for bit; "faces": the frame's own (nf, 3) int32;
+    "colors" (nv, 3) or None: the learned colour at the crossing, zeros without one; "displacement" (nv,): t_est, NaN without a crossing;
+    "found" (nv,) bool; "normals" (nv, 3); "mano_verts" (nv, 3); "state" (nv, LINE_STATE_FLOATS): the final brackets (line_state names its
+    columns)}, all on the device.  net, tr_batch: as field_on_grid takes them, in the
+    handle's precision.  samples is odd, so t = 0 is a sample.  Beyond what resolving the frame does, nothing is read back to the host."""
+    band, iso, samples, refine = float(band), float(iso), int(samples), int(refine)
+    if not (math.isfinite(band) and band > 0.0):
+        raise ValueError(f"band: expected a positive number, got {band}")
+    if samples < 3 or samples % 2 == 0 or samples > MAX_LINE_SAMPLES:
+        raise ValueError(f"samples: expected an odd number from 3 to {MAX_LINE_SAMPLES - 1}, got {samples}")
+    if refine < 0:
+        raise ValueError(f"refine: expected a number of rounds >= 0, got {refine}")
+    if not math.isfinite(iso):
+        raise ValueError("iso must be finite")
+    t0, dt = float(np.float32(-band)), float(np.float32(2.0 * band / (samples - 1)))
+    if not dt > 0.0:
+        raise ValueError(f"the step {dt} underflows fp32")
+    weights, fd, _ = _resolve(net, tr_batch)
+    want = bool(colors)
+    with torch.cuda.device(fd.verts3.device), torch.no_grad():
+        verts, nv = fd.verts3, fd.verts3.shape[0]
+        normals = vertex_normals(verts, fd.faces)
+        res = field_at_points(weights, fd, line_points(verts, normals, samples, t0, dt), want_rgb=want)
+        f, rgb = res if want else (res, None)
+        state = line_bracket(f.view(nv, samples), t0, dt, iso, None if rgb is None else rgb.view(nv, samples, 3))
+        S = line_state(state)
+        for _ in range(refine):
+            res = field_at_points(weights, fd, line_points(verts, normals, t=S["t_next"].contiguous()), want_rgb=want)
+            f, rgb = res if want else (res, None)
+            line_refine(state, f, iso, rgb)
+        t_est = S["t_est"].contiguous()
+        out = line_points(verts, normals, t=t_est)
+    return {"verts": out, "faces": fd.faces, "colors": S["rgb_est"].contiguous() if want else None, "displacement": t_est,
+            "found": S["found"] != 0, "normals": normals, "mano_verts": verts, "state": state}
+
+
 def save_ply(path, verts, faces, colors=None):
     """Binary little-endian PLY: float x y z[, uchar red green blue] per vertex, `list uchar int vertex_indices` per face.  colors in
     [0, 1] (clamped, rounded to 8 bits).  Tensors (any device) or arrays."""
@@ -237,4 +396,5 @@ def save_ply(path, verts, faces, colors=None):
     return path
 
 
-__all__ = ["SLAB_POINTS", "grid_spec", "grid_points", "field_on_grid", "march", "extract_surface", "save_ply"]
+__all__ = ["SLAB_POINTS", "LINE_STATE_FLOATS", "grid_spec", "grid_points", "field_at_points", "field_on_grid", "march", "extract_surface", "vertex_normals",
+           "line_points", "line_bracket", "line_refine", "line_state", "register_surface", "save_ply"]
