@@ -541,6 +541,37 @@ int vanerf_line_points(const float* base, const float* dir, int n, int K, float 
 int vanerf_line_bracket(const float* f, const float* rgb, int n, int K, float t0, float dt, float iso, float* state, void* stream);
 int vanerf_line_refine(const float* f_new, const float* rgb_new, int n, float iso, float* state, void* stream);
 
+/* The learned field baked into a voxel grid, and views rendered from it.  At one source view the colour of a sample does
+ * not depend on the viewing direction, the density is a function of f = alpha + mesh_sdf alone and `valid` depends on the source camera only,
+ * so (f, r, g, b) on a regular grid -- what vanerf_grid_points ... vanerf_field_values produce -- serves every camera of an orbit.  Rendering
+ * from it is an APPROXIMATION of the pass (a grid resolution and uniform samples in place of the networks at 64 + 64 importance samples).
+ * The grid is the one described above: origin[3], spacing[3] (HOST), nx, ny, nz >= 2, 7 nx ny nz < 2^31, x fastest.
+ *
+ *     vanerf_volume_pack: f[n], rgb[n][3] -> voxels[n][4] = (f, r, g, b), so a corner of a cell is one 16-byte load.  A non-finite f is stored as
+ *         +1e30f: it reads as outside (sigmoid(-1e30 / beta) is exactly 0) and is finite, so eight weights that sum to 1 neither overflow nor
+ *         meet 0 * inf.  A non-finite colour channel is stored as 0.  Everything else is copied bit for bit.  0 <= n < 2^31 (0: a no-op);
+ *         voxels 16-byte aligned.  One launch.
+ *     vanerf_volume_render: the rays vanerf_ray_setup writes for V views -- rays_d[R][3], cam_pos[V][4], z[R][S], hit[R], R = V rays_per_view
+ *         rays, view-major; row_rays: the rays of one pixel row of a view (rays_per_view is a whole number of rows; it only decides which rays
+ *         share a block) -> color[R][3], depth[R], alpha[R].  sigmoid_beta: from the handle w's device copy (already clamped at 2e-3), or, with
+ *         w == NULL, `beta` by value (finite, > 0; clamped at 2e-3).  Per ray:
+ *         - hit == 0: colour, depth and alpha are 0 and nothing else happens;
+ *         - sample i is at p = o + d z_i per axis (vanerf_sample_points' expression); its grid coordinate per axis is u = (p - origin) / spacing,
+ *           clamped to [0, n - 1] (border padding; a NaN clamps to 0), its cell i0 = min((int)floorf(u), n - 2) and its weight w = u - i0;
+ *         - the four channels are interpolated from the eight corners in fp32, (1 - w) a + w b along x, then y, then z;
+ *         - the composite is vanerf_composite's with a = the interpolated f in the place of rgba[0] + mesh_sdf:
+ *           sg = (1 / (1 + expf(a / beta))) / beta, dist = z_i+1 - z_i (1e10f for the last sample), c = 1 - expf(-sg dist), w_i = c T,
+ *           T *= 1 - c; colour, alpha and the z-weighted sum are accumulated in fp64 from fp32 products, depth = sum / (alpha + 1e-8f).
+ *         One wave per ray, the samples over the lanes in rounds of 64 with the transmittance carried between rounds (an exclusive prefix
+ *         product with a fixed shuffle pattern inside a round, a fixed xor butterfly for the sums), the waves of a block on a 2 x 2 pixel tile
+ *         of one view.  Any S >= 1; V <= 65535; R == 0 is a no-op.  One launch.
+ * All pointers but origin and spacing are DEVICE pointers.  All work goes to `stream`; no allocation, no host synchronisation, no atomics, no
+ * device-side state: the same bits every call.  Arguments are checked before any launch.                                                 */
+int vanerf_volume_pack(const float* f, const float* rgb, int64_t n, float* voxels, void* stream);
+int vanerf_volume_render(const float* voxels, const float origin[3], const float spacing[3], int nx, int ny, int nz, const VanerfWeights* w, float beta,
+                         const float* rays_d, const float* cam_pos, const float* z, const uint8_t* hit, int R, int rays_per_view, int row_rays, int S,
+                         float* color, float* depth, float* alpha, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -633,6 +633,14 @@ class VANeRF(nn.Module):
         from . import surface
         return surface.register_surface(self, tr_batch, **kwargs)
 
+    @torch.no_grad()
+    def bake_volume(self, tr_batch, **kwargs):
+        """The learned field of one frame baked into a voxel grid of (f, r, g, b) (vanerf_amd.baked.bake_volume): what
+        baked.render_volume / render_baked_views march orbit cameras through, an approximation of the pass with no network and no mesh query
+        per view."""
+        from . import baked
+        return baked.bake_volume(self, tr_batch, **kwargs)
+
     def attach_autograd(self, out, img_in, feat_geo, feat_tex, targets, sp_data, fg_mask):
         """Replaces the differentiable entries of `out` (a batch_render_pifu_nerf result computed with _autograd=True) by tensors that
         carry the HIP values and, in backward, the gradients of the networks evaluated at the same samples (same points, same importance
