@@ -163,7 +163,10 @@ int vanerf_mesh_query(const float* verts, int nv, const int32_t* faces, int nf, 
                       const float* pts, int64_t n, float* sdf, uint8_t* vis, int32_t* face, void* stream);
 
 /* Acceleration structure for vanerf_mesh_query_accel, built per source frame by vanerf_mesh_accel_build below.
- * Results are bit-identical to vanerf_mesh_query.                                                                        */
+ * Results are bit-identical to vanerf_mesh_query.  Tested (tests/test_mesh_geometry.py, also against an fp64 definition of distance,
+ * sign, arg-min face, visibility and 1-NN) on closed meshes in metres within a few metres of the origin -- |coordinate| up to 3.3 for the
+ * hand meshes, 7 for ray samples about a 1 m torus -- at 0.5x, 1x and 2x the scale of a hand: star-shaped blobs, lobed (concave) hands of
+ * 779 to 2 402 vertices, two interpenetrating hands, a torus, a sphere with a cavity, and cell grids of 1 to 256 cells a side.          */
 /* Triangles / vertices per cluster the library was built with. */
 int vanerf_mesh_cluster_size(void);
 

@@ -70,13 +70,57 @@ __device__ __forceinline__ float point_tri_dist2(f3 p, f3 a, f3 b, f3 c)
 }
 
 // canonical (index-ordered) edge function in the (y,z) plane, see oracle/mesh_oracle.c:edge_side
-__device__ __forceinline__ bool edge_side(f3 va, f3 vb, int ia, int ib, float qy, float qz, float& E)
+__device__ __forceinline__ float edge_fn(f3 va, f3 vb, int ia, int ib, float qy, float qz)
+{
+    const bool fwd = ia < ib;
+    const f3 lo = fwd ? va : vb, hi = fwd ? vb : va;
+    const float e = (hi.y - lo.y) * (qz - lo.z) - (hi.z - lo.z) * (qy - lo.y);
+    return fwd ? e : -e;
+}
+
+// the side of an edge whose function ties (== 0): as if q were moved by (eps^2, eps) in (y,z), the same displaced point for every edge
+__device__ __forceinline__ bool edge_tie_side(f3 va, f3 vb, int ia, int ib)
+{
+    const bool fwd = ia < ib;
+    const f3 lo = fwd ? va : vb, hi = fwd ? vb : va;
+    const float dy = hi.y - lo.y, dz = hi.z - lo.z;
+    return fwd == ((dy > 0.0f) || (dy == 0.0f && dz < 0.0f));
+}
+
+// do the three edge functions of triangle (a, b, c) put (qy, qz) on one side (oracle/mesh_oracle.c:point_inside)?  E0..E2 are the weights of
+// a, b, c.  Ties are rare (the +x ray meets an edge's line exactly): all of them are settled in one branch, the common path compares once per edge.
+// `by_index` is the answer of the earlier tie rule (a tie goes to the traversal from the lower to the higher vertex index), which a point at
+// distance exactly 0 keeps: its sign has no meaning, and the fixtures recorded that one.
+__device__ __forceinline__ bool edges_agree(f3 a, f3 b, f3 c, int i0, int i1, int i2, float qy, float qz, float& E0, float& E1, float& E2, bool& by_index)
+{
+    E0 = edge_fn(b, c, i1, i2, qy, qz);
+    E1 = edge_fn(c, a, i2, i0, qy, qz);
+    E2 = edge_fn(a, b, i0, i1, qy, qz);
+    bool s0 = E0 > 0.0f, s1 = E1 > 0.0f, s2 = E2 > 0.0f;
+    bool agree = (s0 && s1 && s2) || (!s0 && !s1 && !s2);
+    by_index = agree;
+    if (__builtin_expect(E0 == 0.0f || E1 == 0.0f || E2 == 0.0f, 0)) {
+        const bool o0 = E0 == 0.0f ? i1 < i2 : s0, o1 = E1 == 0.0f ? i2 < i0 : s1, o2 = E2 == 0.0f ? i0 < i1 : s2;
+        by_index = (o0 && o1 && o2) || (!o0 && !o1 && !o2);
+        if (E0 == 0.0f) s0 = edge_tie_side(b, c, i1, i2);
+        if (E1 == 0.0f) s1 = edge_tie_side(c, a, i2, i0);
+        if (E2 == 0.0f) s2 = edge_tie_side(a, b, i0, i1);
+        agree = (s0 && s1 && s2) || (!s0 && !s1 && !s2);
+    }
+    return agree;
+}
+
+// The accelerated kernel's first pass over a point's triangles: the earlier tie rule (a tie goes to the traversal from the lower to the higher
+// vertex index) at the price it always had, plus a note in `tie` that some edge function was exactly 0.  Only a point with such a note that
+// does not lie on the surface is counted again with edges_agree (mesh_query_accel_kernel): ties stay out of the common path altogether.
+__device__ __forceinline__ bool edge_side_by_index(f3 va, f3 vb, int ia, int ib, float qy, float qz, float& E, bool& tie)
 {
     const bool fwd = ia < ib;
     const f3 lo = fwd ? va : vb, hi = fwd ? vb : va;
     float e = (hi.y - lo.y) * (qz - lo.z) - (hi.z - lo.z) * (qy - lo.y);
     if (!fwd) e = -e;
     E = e;
+    tie |= e == 0.0f;
     return (e > 0.0f) || (e == 0.0f && fwd);
 }
 
@@ -95,7 +139,7 @@ __global__ __launch_bounds__(MQ_BLOCK) void mesh_query_kernel(const float* __res
     const long long ii = live ? i : n - 1;
     const f3 p = {P[3 * ii], P[3 * ii + 1], P[3 * ii + 2]};
     float best = INFINITY;
-    int bf = 0, cnt = 0;
+    int bf = 0, cnt = 0, cnt0 = 0; // cnt0: crossings by the earlier tie rule, for a point at distance exactly 0 (edges_agree)
     for (int f0 = 0; f0 < nf; f0 += MQ_TILE) {
         const int m = min(MQ_TILE, nf - f0);
         __syncthreads();
@@ -114,20 +158,20 @@ __global__ __launch_bounds__(MQ_BLOCK) void mesh_query_kernel(const float* __res
             // +x ray parity (oracle/mesh_oracle.c:point_inside)
             const int i0 = s_idx[f][0], i1 = s_idx[f][1], i2 = s_idx[f][2];
             float E0, E1, E2;
-            const bool s0 = edge_side(b, c, i1, i2, p.y, p.z, E0);
-            const bool s1 = edge_side(c, a, i2, i0, p.y, p.z, E1);
-            const bool s2 = edge_side(a, b, i0, i1, p.y, p.z, E2);
-            if ((s0 && s1 && s2) || (!s0 && !s1 && !s2)) {
+            bool by_index;
+            const bool agree = edges_agree(a, b, c, i0, i1, i2, p.y, p.z, E0, E1, E2, by_index);
+            if (agree || by_index) {
                 const float den = (E0 + E1) + E2;
                 if (den != 0.0f) {
                     const float xh = ((E0 * a.x + E1 * b.x) + E2 * c.x) / den;
-                    if (xh > p.x) ++cnt;
+                    if (xh > p.x) { cnt += agree; cnt0 += by_index; }
                 }
             }
         }
     }
     if (!live) return;
     const float dist = sqrtf(best + 1e-6f);
+    if (best == 0.0f) cnt = cnt0;
     sdf[i] = (cnt & 1) ? -dist : dist;
     if (face) face[i] = bf;
     // barycentric_coordinates_of_projection (mesh_util.py:321-356) on the closest face
@@ -979,8 +1023,9 @@ __global__ __launch_bounds__(MA_BLOCK) void mesh_query_accel_kernel(const Vanerf
             // (|edge| x distance against 1e-7 relative rounding) cannot all agree in sign, so the exhaustive scan counts no crossing either.
             // (Points within a cell of the border keep going through the border cells' lists, as before.)
             const bool beside = fy < -1.0f || fy > (float)grid_G || fz < -1.0f || fz > (float)grid_G;
-            const int e = beside ? 0 : A.cell_start[cell + 1];
-            for (int k = beside ? 0 : A.cell_start[cell]; k < e; ++k) {
+            const int k0 = beside ? 0 : A.cell_start[cell], e = beside ? 0 : A.cell_start[cell + 1];
+            bool tie = false;
+            for (int k = k0; k < e; ++k) {
                 // one 48-byte record per list entry (vertex ids for the canonical edge orientation, then the corners: copies of F and V), so that
                 // an entry costs one independent load instead of the chain face id -> vertex ids -> corners
                 const float4 r0 = reinterpret_cast<const float4*>(A.cell_rec)[3 * k], r1 = reinterpret_cast<const float4*>(A.cell_rec)[3 * k + 1],
@@ -988,14 +1033,34 @@ __global__ __launch_bounds__(MA_BLOCK) void mesh_query_accel_kernel(const Vanerf
                 const int i0 = __float_as_int(r0.x), i1 = __float_as_int(r0.y), i2 = __float_as_int(r0.z);
                 const f3 a = {r0.w, r1.x, r1.y}, b = {r1.z, r1.w, r2.x}, c3 = {r2.y, r2.z, r2.w};
                 float E0, E1, E2;
-                const bool s0 = edge_side(b, c3, i1, i2, p.y, p.z, E0);
-                const bool s1 = edge_side(c3, a, i2, i0, p.y, p.z, E1);
-                const bool s2 = edge_side(a, b, i0, i1, p.y, p.z, E2);
+                const bool s0 = edge_side_by_index(b, c3, i1, i2, p.y, p.z, E0, tie);
+                const bool s1 = edge_side_by_index(c3, a, i2, i0, p.y, p.z, E1, tie);
+                const bool s2 = edge_side_by_index(a, b, i0, i1, p.y, p.z, E2, tie);
                 if ((s0 && s1 && s2) || (!s0 && !s1 && !s2)) {
                     const float den = (E0 + E1) + E2;
                     if (den != 0.0f) {
                         const float xh = ((E0 * a.x + E1 * b.x) + E2 * c3.x) / den;
                         if (xh > p.x) ++cnt;
+                    }
+                }
+            }
+            // Some edge function tied and the point is not on the surface (where the count above stands, edges_agree): the ray meets an edge's
+            // line or a vertex' projection exactly.  Counted again with the ties decided for one displaced point.  Rare: never on ray samples.
+            if (__builtin_expect(tie && best != 0.0f, 0)) {
+                cnt = 0;
+                for (int k = k0; k < e; ++k) {
+                    const float4 r0 = reinterpret_cast<const float4*>(A.cell_rec)[3 * k], r1 = reinterpret_cast<const float4*>(A.cell_rec)[3 * k + 1],
+                                 r2 = reinterpret_cast<const float4*>(A.cell_rec)[3 * k + 2];
+                    const int i0 = __float_as_int(r0.x), i1 = __float_as_int(r0.y), i2 = __float_as_int(r0.z);
+                    const f3 a = {r0.w, r1.x, r1.y}, b = {r1.z, r1.w, r2.x}, c3 = {r2.y, r2.z, r2.w};
+                    float E0, E1, E2;
+                    bool by_index;
+                    if (edges_agree(a, b, c3, i0, i1, i2, p.y, p.z, E0, E1, E2, by_index)) {
+                        const float den = (E0 + E1) + E2;
+                        if (den != 0.0f) {
+                            const float xh = ((E0 * a.x + E1 * b.x) + E2 * c3.x) / den;
+                            if (xh > p.x) ++cnt;
+                        }
                     }
                 }
             }

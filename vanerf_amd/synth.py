@@ -63,6 +63,63 @@ def two_hand_mesh(seed=0, radius=0.05, offset=0.04, depth=1.0, bumpy=True):
     return verts, faces
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# closed meshes that are NOT star-shaped (tests/test_mesh_geometry.py): thin lobes with deep gaps, a handle, a cavity.  All are centred at the
+# origin; the tests place them (offset, scale).  Vertices float32, faces int64, outward CCW winding (an inner cavity wall keeps the winding of
+# the sphere it copies: a point inside both shells is wound twice and counts as outside by parity).
+# ---------------------------------------------------------------------------------------------------------------------
+def _fingered(sv, seed):
+    phi0 = np.random.RandomState(seed).uniform(0.0, 2.0 * math.pi)
+    phi = np.arctan2(sv[:, 1], sv[:, 0])
+    r = 0.35 + 0.65 * np.abs(np.cos(2.5 * (phi + phi0))) ** 6 * (1.0 - sv[:, 2] ** 2)
+    return sv * r[:, None] * np.array([1.0, 1.0, 0.3]) * 0.07
+
+
+def fingered_hand(seed=0):
+    """(779,3) / (1554,3): the topology of uv_sphere() with radius 0.35 + 0.65 |cos(2.5 (phi + phi0(seed)))|^6 (1 - z^2), flattened by
+    (1, 1, 0.3), times 0.07 m -- a palm with five thin lobes and deep gaps between them (the surfaces of two lobes lie millimetres apart)."""
+    sv, sf = uv_sphere()
+    return _fingered(sv, seed).astype(np.float32), sf.copy()
+
+
+def two_fingered_hands(seed=0):
+    """(1558,3) / (3108,3): two fingered hands 6 cm apart along x -- the counts of two_hand_mesh, so the mesh can stand in a frame.  Lobes of the
+    two hands may interpenetrate; a point inside both is outside by parity."""
+    sv, sf = uv_sphere()
+    hands = [_fingered(sv, 2 * seed + h) + np.array([cx, 0.0, 0.0]) for h, cx in enumerate((-0.03, 0.03))]
+    return np.concatenate(hands, 0).astype(np.float32), np.concatenate([sf, sf + NV_HAND], 0)
+
+
+def fingered_hand_fine(seed=0):
+    """(2402,3) / (4800,3): the fingered hand on uv_sphere(40, 60) (the accelerated query's LDS tables exceed the 64 KB default limit)."""
+    sv, sf = uv_sphere(40, 60)
+    return _fingered(sv, seed).astype(np.float32), sf
+
+
+def torus(n_major=48, n_minor=20, major=1.0, minor=0.3):
+    """(n_major * n_minor, 3) / (2 * n_major * n_minor, 3): a torus about the z axis (genus 1, not star-shaped); 960 / 1 920 by default."""
+    u = 2.0 * math.pi * np.arange(n_major) / n_major
+    v = 2.0 * math.pi * np.arange(n_minor) / n_minor
+    uu, vv = np.meshgrid(u, v, indexing="ij")
+    rad = major + minor * np.cos(vv)
+    verts = np.stack([rad * np.cos(uu), rad * np.sin(uu), minor * np.sin(vv)], -1).reshape(-1, 3)
+    idx = lambda i, j: (i % n_major) * n_minor + (j % n_minor)
+    faces = []
+    for i in range(n_major):
+        for j in range(n_minor):
+            a, b, c, d = idx(i, j), idx(i + 1, j), idx(i + 1, j + 1), idx(i, j + 1)
+            faces.append((a, b, c))
+            faces.append((a, c, d))
+    return verts.astype(np.float32), np.asarray(faces, dtype=np.int64)
+
+
+def nested_shells():
+    """(244,3) / (480,3): uv_sphere(10, 12) and a copy of it scaled 0.55 and shifted by (0.1, 0.05, 0) inside it.  The inner cavity is outside."""
+    sv, sf = uv_sphere(10, 12)
+    inner = sv * 0.55 + np.array([0.1, 0.05, 0.0])
+    return np.concatenate([sv, inner], 0).astype(np.float32), np.concatenate([sf, sf + sv.shape[0]], 0)
+
+
 def look_at_extrinsic(eye, target, up=(0.0, -1.0, 0.0)):
     """World->camera 4x4 (x right, y down, z forward)."""
     eye, target, up = (np.asarray(a, dtype=np.float64) for a in (eye, target, up))
