@@ -575,6 +575,34 @@ int vanerf_volume_render(const float* voxels, const float origin[3], const float
                          const float* rays_d, const float* cam_pos, const float* z, const uint8_t* hit, int R, int rays_per_view, int row_rays, int S,
                          float* color, float* depth, float* alpha, void* stream);
 
+/* The surface of the baked volume as a camera sees it: depth, normal and colour maps from the voxels of
+ * vanerf_volume_pack and the rays of vanerf_ray_setup, with no network, no mesh query and no triangle.  The grid, the rays, their layouts and
+ * row_rays are vanerf_volume_render's; voxels and normal 16-byte aligned; iso finite; 0 <= refine <= 4; any S >= 1; V <= 65535; R == 0 is a
+ * no-op.  -> depth[R], normal[R][4] = (nx, ny, nz, n . v), color[R][3], found[R] (0, 1 or 2).  Per ray, all in fp32:
+ *     - hit == 0: found = 0 and every output is 0.
+ *     - g(zz) is channel 0 of vanerf_volume_render's trilinear interpolation at p = o + d zz (the same u, clamp, cell and (1 - w) a + w b order
+ *       along x, then y, then z).  A point is INSIDE iff g < iso (vanerf_surface_count's rule: g == iso is outside).
+ *     - sample 0 inside: found = 2 and z* = z_0 (the clipped ray starts inside the hand, as at the wrist, which the box cuts).  With S == 1 this
+ *       is the only way to be found.
+ *     - otherwise the smallest k with sample k outside and sample k + 1 inside: found = 1 and the bracket is (za, zb, ga, gb) =
+ *       (z_k, z_k+1, g_k, g_k+1).  None: found = 0 and every output is 0.
+ *     - `refine` rounds of a 65-way split: t_l = za + ((float)(l + 1) / 65.0f) * (zb - za), l = 0..63, g_l = g(t_l); the first adjacent pair of
+ *       a, t_0 .. t_63, b that is (outside, inside) becomes the bracket (one always exists).
+ *     - w = fminf(fmaxf((iso - ga) / (gb - ga), 0), 1), z* = za + w * (zb - za); depth = z*, in the units of z.
+ *     - at p* = o + d z*: color = channels 1..3 of the interpolation.  The gradient is a central difference in grid coordinates with clamped
+ *       steps: with u the clamped grid coordinate of p*, per axis a: u+ = fminf(u_a + 1, n_a - 1), u- = fmaxf(u_a - 1, 0),
+ *       G_a = (f(u with u_a = u+) - f(u with u_a = u-)) / ((u+ - u-) * spacing_a) -- exact for an affine field, the border included.
+ *       m = max |G_a|; m == 0 or not finite: the normal and n . v are 0.  Otherwise G /= m (so 1e30 voxels cannot overflow the squares),
+ *       n = G / sqrtf(Gx^2 + Gy^2 + Gz^2), which points towards growing f (outward), and n . v = fmaxf(0, -((n . d) / |d|)).
+ * One wave per ray, the samples over the lanes in rounds of 64 (the last value of a round carried into the next), "outside, then inside" a
+ * 64-bit ballot whose lowest set bit is the crossing; the march stops at the first round that finds one.  March and refinement read channel 0
+ * only.  All pointers but origin and spacing are DEVICE pointers.  All work goes to `stream`; no allocation, no host synchronisation, no
+ * atomics, no device-side state; every output element is written on every call: the same bits every call.  Arguments are checked before any
+ * launch.  One launch.                                                                                                                     */
+int vanerf_volume_surface(const float* voxels, const float origin[3], const float spacing[3], int nx, int ny, int nz, float iso, int refine,
+                          const float* rays_d, const float* cam_pos, const float* z, const uint8_t* hit, int R, int rays_per_view, int row_rays, int S,
+                          float* depth, float* normal, float* color, uint8_t* found, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

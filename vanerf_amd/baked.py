@@ -8,6 +8,10 @@ marches the pass's own rays through the grid: trilinear gathers and the pass's c
 This is an APPROXIMATION of the pass, not a replacement: a grid resolution and uniform samples stand in for the networks evaluated at 64 + 64
 importance samples.  It is the preview / interactive path, and a cheap source of depth and alpha maps of the learned hand from any camera.
 baked_views_fn plugs it into novel_views.render_novel_views / render_video through their render_views_fn hook.
+
+The same volume also shows its geometry (vanerf_amd/csrc/volume_surface.hip): march_surface / render_volume_surface find,
+per ray, where the trilinear field first crosses f = iso and return the depth, the normal and the colour there; render_baked_surface_views
+turns them into depth, normal-map, clay and shaded frames, and surface_views_fn is baked_views_fn's twin for geometry orbits.
 """
 import dataclasses
 from ctypes import c_void_p
@@ -96,13 +100,8 @@ def _check_volume(volume):
     return nx, ny, nz
 
 
-def march_volume(volume, rays_d, cam_pos, z, hit, row_rays=None, out=None):
-    """vanerf_volume_render on rays laid out as renderer.ray_setup_views lays them out: rays_d (V, R, 3), cam_pos (V, 4), z (V, R, S) fp32 and
-    hit (V, R) uint8 on the volume's device -> color (V, R, 3), depth (V, R), alpha (V, R).  row_rays: the rays of one pixel row (default R:
-    it only decides which rays share a block).  out: (color, depth, alpha), contiguous fp32 device tensors to fill instead of new ones: every
-    element is written, whatever they held.  One launch."""
-    from . import renderer as R
-    nx, ny, nz = _check_volume(volume)
+def _check_rays(volume, rays_d, cam_pos, z, hit):
+    """The rays of march_volume / march_surface, as renderer.ray_setup_views lays them out, on the volume's device -> V, R, S and their pointers."""
     if not (torch.is_tensor(z) and z.dim() == 3):
         raise ValueError("z: expected a tensor (V, R, S)")
     V, Rn, S = (int(d) for d in z.shape)
@@ -116,6 +115,29 @@ def march_volume(volume, rays_d, cam_pos, z, hit, row_rays=None, out=None):
         raise ValueError(f"rays_d, cam_pos, z and hit: expected tensors on the volume's device {dev}")
     ptrs = [_dev_ptr(rays_d, torch.float32, "rays_d"), _dev_ptr(cam_pos, torch.float32, "cam_pos"), _dev_ptr(z, torch.float32, "z"),
             _dev_ptr(hit, torch.uint8, "hit")]
+    return V, Rn, S, ptrs
+
+
+def _check_out(out, shapes, dev):
+    """out: the tensors to fill, against (shape, dtype, name) each: contiguous, on dev."""
+    if len(out) != len(shapes):
+        raise ValueError(f"out: expected {len(shapes)} tensors ({', '.join(what for _, _, what in shapes)})")
+    for t, (shape, dtype, what) in zip(out, shapes):
+        if not (torch.is_tensor(t) and tuple(t.shape) == shape and t.device == dev):
+            raise ValueError(f"out {what}: expected a tensor {shape} on {dev}")
+        _dev_ptr(t, dtype, f"out {what}")
+    return out
+
+
+def march_volume(volume, rays_d, cam_pos, z, hit, row_rays=None, out=None):
+    """vanerf_volume_render on rays laid out as renderer.ray_setup_views lays them out: rays_d (V, R, 3), cam_pos (V, 4), z (V, R, S) fp32 and
+    hit (V, R) uint8 on the volume's device -> color (V, R, 3), depth (V, R), alpha (V, R).  row_rays: the rays of one pixel row (default R:
+    it only decides which rays share a block).  out: (color, depth, alpha), contiguous fp32 device tensors to fill instead of new ones: every
+    element is written, whatever they held.  One launch."""
+    from . import renderer as R
+    nx, ny, nz = _check_volume(volume)
+    V, Rn, S, ptrs = _check_rays(volume, rays_d, cam_pos, z, hit)
+    dev = volume.voxels.device
     row_rays = Rn if row_rays is None else int(row_rays)
     by_handle = isinstance(volume.beta, R.PackedWeights)
     if by_handle and volume.beta.device_index is not None and volume.beta.device_index != dev.index:
@@ -123,11 +145,7 @@ def march_volume(volume, rays_d, cam_pos, z, hit, row_rays=None, out=None):
     with torch.cuda.device(dev):
         if out is None:
             out = (torch.empty(V, Rn, 3, dtype=torch.float32, device=dev), *(torch.empty(V, Rn, dtype=torch.float32, device=dev) for _ in range(2)))
-        color, depth, alpha = out
-        for t, shape, what in ((color, (V, Rn, 3), "out color"), (depth, (V, Rn), "out depth"), (alpha, (V, Rn), "out alpha")):
-            if not (torch.is_tensor(t) and tuple(t.shape) == shape and t.device == dev):
-                raise ValueError(f"{what}: expected a tensor {shape} on {dev}")
-            _dev_ptr(t, torch.float32, what)
+        color, depth, alpha = _check_out(out, (((V, Rn, 3), torch.float32, "color"), ((V, Rn), torch.float32, "depth"), ((V, Rn), torch.float32, "alpha")), dev)
         check(lib.vanerf_volume_render(c_void_p(volume.voxels.data_ptr()), _f3(volume.origin), _f3(volume.spacing), nx, ny, nz,
                                        volume.beta.handle if by_handle else None, 0.0 if by_handle else float(volume.beta), *ptrs, V * Rn, Rn, row_rays, S,
                                        c_void_p(color.data_ptr()), c_void_p(depth.data_ptr()), c_void_p(alpha.data_ptr()), _stream()))
@@ -152,11 +170,9 @@ def _cameras(volume, cam_tars):
     return [dict(c, znear=c.get("znear", volume.znear), zfar=c.get("zfar", volume.zfar)) for c in cam_tars], sizes.pop()
 
 
-def render_volume(volume, cam_tars, samples=128, x0=0, y0=0, step=1, nx=None, ny=None):
-    """V target cameras of one size through a BakedVolume: renderer.ray_setup_views(cam_tars, volume.bounds, ..., S=samples) -- so rays, clip,
-    hit and the uniform depths are the pass's own bits -- followed by one vanerf_volume_render.  Two launches per group of views.
-    x0, y0, step, nx, ny: the pixel grid (default the whole frame).  samples = 1 puts the one sample at the near end of the clipped ray.
-    -> {"color" (V, R, 3), "depth" (V, R), "alpha" (V, R), "hit" (V, R) uint8, "index" (V, R) int64}, R = nx ny."""
+def _view_rays(volume, cam_tars, samples, x0, y0, step, nx, ny):
+    """renderer.ray_setup_views for render_volume / render_volume_surface: the rays of V cameras of one size on the pixel grid (x0, y0, step,
+    nx, ny; default the whole frame) with `samples` uniform depths each -> (its outputs, with "row_rays" = nx added, and z (V, R, samples))."""
     from . import renderer as R
     samples = int(samples)
     if samples < 1:
@@ -172,10 +188,29 @@ def render_volume(volume, cam_tars, samples=128, x0=0, y0=0, step=1, nx=None, ny
         raise ValueError(f"an empty pixel grid ({nx} x {ny})")
     dev = volume.voxels.device
     with torch.cuda.device(dev), torch.no_grad():
-        rays = R.ray_setup_views(cams, volume.bounds, x0, y0, step, nx, ny, max(samples, 2), device=dev)  # (the ray setup takes S >= 2)
+        rays = dict(R.ray_setup_views(cams, volume.bounds, x0, y0, step, nx, ny, max(samples, 2), device=dev), row_rays=nx)  # (the ray setup takes S >= 2)
         z = rays["z"] if samples >= 2 else rays["z"][..., :1].contiguous()  # linspace(0, 1, 1) is [0]: the near end, the first of any S
-        color, depth, alpha = march_volume(volume, rays["rays_d"], rays["cam_pos"], z, rays["hit"], row_rays=nx)
+    return rays, z
+
+
+def render_volume(volume, cam_tars, samples=128, x0=0, y0=0, step=1, nx=None, ny=None):
+    """V target cameras of one size through a BakedVolume: renderer.ray_setup_views(cam_tars, volume.bounds, ..., S=samples) -- so rays, clip,
+    hit and the uniform depths are the pass's own bits -- followed by one vanerf_volume_render.  Two launches per group of views.
+    x0, y0, step, nx, ny: the pixel grid (default the whole frame).  samples = 1 puts the one sample at the near end of the clipped ray.
+    -> {"color" (V, R, 3), "depth" (V, R), "alpha" (V, R), "hit" (V, R) uint8, "index" (V, R) int64}, R = nx ny."""
+    rays, z = _view_rays(volume, cam_tars, samples, x0, y0, step, nx, ny)
+    with torch.cuda.device(volume.voxels.device), torch.no_grad():
+        color, depth, alpha = march_volume(volume, rays["rays_d"], rays["cam_pos"], z, rays["hit"], row_rays=rays["row_rays"])
     return {"color": color, "depth": depth, "alpha": alpha, "hit": rays["hit"], "index": rays["index"]}
+
+
+def _add_vert_xy(ret, volume, cam_tar):
+    """ret["vert_xy"] (1, nv, 2): the frame's vertices in the target image, when the volume carries them."""
+    if volume.verts is not None and "KRT" in cam_tar:
+        vimg = volume.verts[None] @ cam_tar["KRT"][:, :3, :3].transpose(1, 2) + cam_tar["KRT"][:, :3, 3][:, None]
+        ret["vert_xy"] = vimg[..., :2] / (vimg[..., 2:3] + 1e-8)
+        if "transf" in cam_tar:  # src/model.py:1093-1095
+            ret["vert_xy"] = ret["vert_xy"] @ cam_tar["transf"][:, :2, :2].transpose(1, 2) + cam_tar["transf"][:, :, 2][:, None]
 
 
 def render_baked_views(volume, cam_tars, samples=128):
@@ -190,11 +225,7 @@ def render_baked_views(volume, cam_tars, samples=128):
         ret = {"tex_fg": o["color"][v].view(height, width, 3).permute(2, 0, 1), "depth": o["depth"][v].view(1, height, width),
                "alpha": o["alpha"][v].view(1, height, width)}
         ret["tex_fg_fine"] = ret["tex_fg"]
-        if volume.verts is not None and "KRT" in cam_tar:
-            vimg = volume.verts[None] @ cam_tar["KRT"][:, :3, :3].transpose(1, 2) + cam_tar["KRT"][:, :3, 3][:, None]
-            ret["vert_xy"] = vimg[..., :2] / (vimg[..., 2:3] + 1e-8)
-            if "transf" in cam_tar:  # src/model.py:1093-1095
-                ret["vert_xy"] = ret["vert_xy"] @ cam_tar["transf"][:, :2, :2].transpose(1, 2) + cam_tar["transf"][:, :, 2][:, None]
+        _add_vert_xy(ret, volume, cam_tar)
         outs.append(ret)
     return outs
 
@@ -215,4 +246,131 @@ def baked_views_fn(resolution=128, samples=128):
     return render_views
 
 
-__all__ = ["CLIP_PAD", "BakedVolume", "pack_volume", "bake_volume", "march_volume", "render_volume", "render_baked_views", "baked_views_fn"]
+# ------------------------------------------------------------------------------------------------
+# the surface of the volume as a camera sees it (csrc/volume_surface.hip)
+# ------------------------------------------------------------------------------------------------
+SURFACE_MODES = ("shaded", "clay", "normal", "depth")
+MAX_REFINE = 4
+
+
+def _check_surface(iso, refine):
+    iso, refine = float(iso), int(refine)
+    if not np.isfinite(iso):
+        raise ValueError(f"iso: expected a finite level, got {iso}")
+    if not 0 <= refine <= MAX_REFINE:
+        raise ValueError(f"refine: expected 0 .. {MAX_REFINE} rounds, got {refine}")
+    return iso, refine
+
+
+def march_surface(volume, rays_d, cam_pos, z, hit, iso=0.0, refine=1, row_rays=None, out=None):
+    """vanerf_volume_surface on the rays march_volume takes (rays_d (V, R, 3), cam_pos (V, 4), z (V, R, S), hit (V, R) uint8, on the volume's
+    device) -> depth (V, R), normal (V, R, 4) = (nx, ny, nz, n . v), color (V, R, 3) fp32 and found (V, R) uint8.  Per ray the first sample
+    pair (outside, inside) of f < iso, refined by `refine` (0 .. 4) 65-way splits and one linear step; depth in the units of z, the normal
+    the normalised gradient of the trilinear field (outward), the colour interpolated there.  found: 1 a crossing, 2 the ray starts inside
+    (depth = its first sample), 0 nothing (a miss included): every output 0.  out: (depth, normal, color, found) to fill instead of new
+    tensors: every element is written, whatever they held.  One launch."""
+    iso, refine = _check_surface(iso, refine)
+    nx, ny, nz = _check_volume(volume)
+    V, Rn, S, ptrs = _check_rays(volume, rays_d, cam_pos, z, hit)
+    dev = volume.voxels.device
+    row_rays = Rn if row_rays is None else int(row_rays)
+    with torch.cuda.device(dev):
+        if out is None:
+            out = (torch.empty(V, Rn, dtype=torch.float32, device=dev), torch.empty(V, Rn, 4, dtype=torch.float32, device=dev),
+                   torch.empty(V, Rn, 3, dtype=torch.float32, device=dev), torch.empty(V, Rn, dtype=torch.uint8, device=dev))
+        depth, normal, color, found = _check_out(out, (((V, Rn), torch.float32, "depth"), ((V, Rn, 4), torch.float32, "normal"),
+                                                       ((V, Rn, 3), torch.float32, "color"), ((V, Rn), torch.uint8, "found")), dev)
+        check(lib.vanerf_volume_surface(c_void_p(volume.voxels.data_ptr()), _f3(volume.origin), _f3(volume.spacing), nx, ny, nz, iso, refine, *ptrs,
+                                        V * Rn, Rn, row_rays, S, c_void_p(depth.data_ptr()), c_void_p(normal.data_ptr()), c_void_p(color.data_ptr()),
+                                        c_void_p(found.data_ptr()), _stream()))
+    return depth, normal, color, found
+
+
+def render_volume_surface(volume, cam_tars, samples=128, iso=0.0, refine=1, x0=0, y0=0, step=1, nx=None, ny=None):
+    """render_volume's rays (renderer.ray_setup_views on volume.bounds, `samples` uniform depths; samples = 1: the near end of the clipped ray)
+    followed by one vanerf_volume_surface.  Two launches per group of views.
+    -> {"depth" (V, R), "normal" (V, R, 4), "color" (V, R, 3), "found" (V, R) uint8, "hit" (V, R) uint8, "index" (V, R) int64}, R = nx ny."""
+    iso, refine = _check_surface(iso, refine)
+    rays, z = _view_rays(volume, cam_tars, samples, x0, y0, step, nx, ny)
+    with torch.cuda.device(volume.voxels.device), torch.no_grad():
+        depth, normal, color, found = march_surface(volume, rays["rays_d"], rays["cam_pos"], z, rays["hit"], iso, refine, row_rays=rays["row_rays"])
+    return {"depth": depth, "normal": normal, "color": color, "found": found, "hit": rays["hit"], "index": rays["index"]}
+
+
+def _rotation(rt, dev):
+    """RT[:3, :3] of a camera's (1, 4, 4) / (4, 4) / (3, 4) world-to-camera matrix, on dev."""
+    rt = torch.as_tensor(rt).to(device=dev, dtype=torch.float32)
+    return rt.reshape(-1, *rt.shape[-2:])[0, :3, :3]
+
+
+def _per_view(values, dev):
+    """znear / zfar of the cameras of a group, numbers or one-element tensors -> (V, 1, 1, 1) on dev; no host read."""
+    if any(torch.is_tensor(x) for x in values):
+        return torch.stack([torch.as_tensor(x).to(device=dev, dtype=torch.float32).reshape(()) for x in values]).view(-1, 1, 1, 1)
+    return torch.tensor([float(x) for x in values], dtype=torch.float32, device=dev).view(-1, 1, 1, 1)
+
+
+def render_baked_surface_views(volume, cam_tars, samples=128, iso=0.0, refine=1, mode="shaded", ambient=0.25, background=0.0):
+    """Whole geometry frames from a BakedVolume, one dict per camera: depth (1, H, W), found (1, H, W) uint8 and normal (3, H, W) in world
+    space are the kernel's outputs (0 where nothing is found);
+        normal_img (3, H, W) = 0.5 + 0.5 (n_cam.x, -n_cam.y, -n_cam.z), n_cam = RT[:3, :3] n (the usual normal-map colours: towards the camera is blue),
+        shade (1, H, W) = ambient + (1 - ambient) n . v (a headlight),
+        tex_fg (3, H, W) by `mode`: "shaded" colour x shade, "clay" 0.8 shade, "normal" normal_img, "depth" (zfar - depth) / (zfar - znear);
+    these three hold `background` where found == 0.  tex_fg_fine is the same tensor as tex_fg (what novel_views.arrange_nerf_images reads),
+    vert_xy as in render_baked_views.  The images are elementwise torch ops on H x W; no host read."""
+    if mode not in SURFACE_MODES:
+        raise ValueError(f"mode: expected one of {SURFACE_MODES}, got {mode!r}")
+    cam_tars = list(cam_tars)
+    o = render_volume_surface(volume, cam_tars, samples, iso, refine)
+    cams, (width, height) = _cameras(volume, cam_tars)
+    dev = volume.voxels.device
+    ambient, background = float(ambient), float(background)
+    V = len(cams)
+    with torch.cuda.device(dev), torch.no_grad():  # (the whole group at once: a dozen launches per group, not per view)
+        seen = (o["found"] != 0).view(V, 1, height, width)
+        depth = o["depth"].view(V, 1, height, width)
+        n4 = o["normal"].view(V, height, width, 4).permute(0, 3, 1, 2)
+        rot = torch.stack([_rotation(cam["RT"], dev) for cam in cams])
+        n_cam = (rot[:, :, :, None, None] * n4[:, None, :3]).sum(2)
+        normal_img = torch.where(seen, 0.5 + torch.tensor([0.5, -0.5, -0.5], device=dev).view(1, 3, 1, 1) * n_cam, background)
+        lit = ambient + (1.0 - ambient) * n4[:, 3:]
+        if mode == "shaded":
+            tex = o["color"].view(V, height, width, 3).permute(0, 3, 1, 2) * lit
+        elif mode == "clay":
+            tex = (0.8 * lit).expand(V, 3, height, width)
+        elif mode == "normal":
+            tex = normal_img
+        else:
+            znear, zfar = (_per_view([cam[k] for cam in cams], dev) for k in ("znear", "zfar"))
+            tex = ((zfar - depth) / (zfar - znear)).expand(V, 3, height, width)
+        shade, tex = torch.where(seen, lit, background), torch.where(seen, tex, background)
+    outs = []
+    for v, cam_tar in enumerate(cam_tars):
+        ret = {"depth": depth[v], "found": o["found"][v].view(1, height, width), "normal": n4[v, :3], "normal_img": normal_img[v], "shade": shade[v],
+               "tex_fg": tex[v]}
+        ret["tex_fg_fine"] = ret["tex_fg"]
+        _add_vert_xy(ret, volume, cam_tar)
+        outs.append(ret)
+    return outs
+
+
+def surface_views_fn(resolution=128, samples=128, mode="shaded", **kw):
+    """baked_views_fn's twin for geometry orbits: a render_views_fn(net, tr_batch, cam_tars, level) for novel_views.render_novel_views /
+    render_video that bakes the source frame once per tr_batch OBJECT and renders every group of cameras with render_baked_surface_views
+    (kw: its iso, refine, ambient, background)."""
+    if mode not in SURFACE_MODES:
+        raise ValueError(f"mode: expected one of {SURFACE_MODES}, got {mode!r}")
+    _check_surface(kw.get("iso", 0.0), kw.get("refine", 1))
+    state = {"batch": None, "volume": None}
+
+    def render_views(net, tr_batch, cam_tars, level):
+        if state["batch"] is not tr_batch:
+            state["volume"] = bake_volume(net, tr_batch, resolution=resolution)
+            state["batch"] = tr_batch
+        return render_baked_surface_views(state["volume"], cam_tars, samples, mode=mode, **kw)
+
+    return render_views
+
+
+__all__ = ["CLIP_PAD", "BakedVolume", "pack_volume", "bake_volume", "march_volume", "render_volume", "render_baked_views", "baked_views_fn",
+           "SURFACE_MODES", "march_surface", "render_volume_surface", "render_baked_surface_views", "surface_views_fn"]

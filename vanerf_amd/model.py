@@ -641,6 +641,13 @@ class VANeRF(nn.Module):
         from . import baked
         return baked.bake_volume(self, tr_batch, **kwargs)
 
+    @torch.no_grad()
+    def render_surface_views(self, tr_batch, cam_tars, resolution=128, **kwargs):
+        """Depth, normal and shaded views of the learned hand from the target cameras: the frame baked at `resolution`
+        (bake_volume) and vanerf_amd.baked.render_baked_surface_views (kwargs: its samples, iso, refine, mode, ambient, background) on it."""
+        from . import baked
+        return baked.render_baked_surface_views(baked.bake_volume(self, tr_batch, resolution=resolution), cam_tars, **kwargs)
+
     def attach_autograd(self, out, img_in, feat_geo, feat_tex, targets, sp_data, fg_mask):
         """Replaces the differentiable entries of `out` (a batch_render_pifu_nerf result computed with _autograd=True) by tensors that
         carry the HIP values and, in backward, the gradients of the networks evaluated at the same samples (same points, same importance
