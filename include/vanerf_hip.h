@@ -214,6 +214,24 @@ int vanerf_mesh_query_accel(const VanerfMeshAccel* accel, const float* verts, in
                             const float* vert_vis, const float* pts, int64_t n, float* sdf, uint8_t* vis, int32_t* face,
                             int32_t* knn_idx, int grid_nx, int grid_ny, int grid_s, void* queue_word, void* stream);
 
+/* The same query with an item order on top of the ray-grid hint (which it needs).  By the hint alone a wave takes depth k of an 8 x 8 pixel
+ * tile -- 64 neighbouring points only where the 64 rays put their k-th sample at one depth.  Importance samples and rays with different clip
+ * ranges (the silhouette of the bounding box) do not; their tiles are searched over a needlessly wide range.
+ *     item_order[ntx * nty * 64 * grid_s] (ntx = ceil(grid_nx / 8), nty = ceil(grid_ny / 8)), tile after tile, or NULL: lane l of depth k of a
+ *         tile then works on sample item_order[(tile * grid_s + k) * 64 + l]; a slot that holds -1 names no sample.  Every sample index of
+ *         [0, n) has to appear once (anywhere in the table: the kernel does not assume that it is sorted, nor that a tile names its own rays).
+ *         Inputs are read and outputs written at the sample's own index either way: the results do not depend on `item_order`, only the
+ *         time does.  NULL is vanerf_mesh_query_accel.
+ * vanerf_mesh_tile_order writes the table the pass uses: z[grid_nx * grid_ny][grid_s] are the depths the points were made from; every tile's
+ * sample indices in ascending z, equal depths in index order (for finite z exactly a stable sort of the tile's depths; with a NaN in a tile,
+ * some permutation of that tile), the slots of rays beyond the grid border at the end of their tile, -1.  One launch, one block per tile,
+ * sorted in LDS, no atomics (the same table on every run).  grid_s <= 128, more is refused.                                              */
+int vanerf_mesh_query_accel_ordered(const VanerfMeshAccel* accel, const float* verts, int nv, const int32_t* faces, int nf,
+                                    const float* vert_vis, const float* pts, int64_t n, float* sdf, uint8_t* vis, int32_t* face,
+                                    int32_t* knn_idx, int grid_nx, int grid_ny, int grid_s, void* queue_word, const int32_t* item_order,
+                                    void* stream);
+int vanerf_mesh_tile_order(const float* z, int grid_nx, int grid_ny, int grid_s, int32_t* order, void* stream);
+
 /* a10 knn_points K=1 (src/networks.py:28): verts[NV][4], pts[N][3] -> idx[N] int32 (first minimum). */
 int vanerf_knn1(const float* verts4, int nv, const float* pts, int64_t n, int32_t* idx, void* stream);
 

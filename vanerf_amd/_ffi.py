@@ -86,6 +86,9 @@ _SIGS = {
     "vanerf_mesh_query": (c_int, [_FP, c_int, _FP, c_int, _FP, _FP, c_int64, _FP, _FP, _FP, c_void_p]),
     "vanerf_mesh_query_accel": (c_int, [POINTER(VanerfMeshAccel), _FP, c_int, _FP, c_int, _FP, _FP, c_int64, _FP, _FP, _FP, _FP, c_int, c_int, c_int,
                                         _FP, c_void_p]),
+    "vanerf_mesh_query_accel_ordered": (c_int, [POINTER(VanerfMeshAccel), _FP, c_int, _FP, c_int, _FP, _FP, c_int64, _FP, _FP, _FP, _FP, c_int, c_int,
+                                                c_int, _FP, _FP, c_void_p]),
+    "vanerf_mesh_tile_order": (c_int, [_FP, c_int, c_int, c_int, _FP, c_void_p]),
     "vanerf_knn1": (c_int, [_FP, c_int, _FP, c_int64, _FP, c_void_p]),
     "vanerf_query_samples": (c_int, [c_void_p, POINTER(VanerfFrame), _FP, _FP, _FP, _FP, _FP, _FP, c_int, c_int64, _FP, _FP, _FP, _FP, c_void_p]),
     "vanerf_vertex_products": (c_int, [c_void_p, POINTER(VanerfFrame), _FP, c_int64, c_void_p]),

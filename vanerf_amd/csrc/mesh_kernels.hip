@@ -370,7 +370,8 @@ __global__ __launch_bounds__(MA_BLOCK) void mesh_query_accel_kernel(const Vanerf
                                                                     const float* __restrict__ P, long long n, float* __restrict__ sdf,
                                                                     uint8_t* __restrict__ vis, int32_t* __restrict__ face,
                                                                     int32_t* __restrict__ knn, int gnx, int gny, int gS,
-                                                                    unsigned long long* __restrict__ queue)
+                                                                    unsigned long long* __restrict__ queue,
+                                                                    const int32_t* __restrict__ item_order)
 {
     // dynamic LDS: [nvc*16] sorted vertices (float4) | [nvc][6] vertex-cluster boxes | [nc][6] triangle-cluster boxes
     extern __shared__ float4 s_dyn[];
@@ -391,6 +392,10 @@ __global__ __launch_bounds__(MA_BLOCK) void mesh_query_accel_kernel(const Vanerf
     // ray-grid hint (gnx x gny rays, gS samples per ray, sample index = ray * gS + depth) a wave takes one depth of an 8 x 8
     // pixel tile: 64 points a few millimetres apart that prune almost identically.  Without the hint (gnx == 0) consecutive
     // lanes take consecutive samples (one whole ray per wave: its points span the bounding box, ~4x more work per wave).
+    // With an item order on top of the hint (vanerf_mesh_tile_order: the tile's 64 x gS sample indices sorted by depth, 64 gS slots per tile)
+    // depth k of a tile is the k-th 64-slot slab of its table instead: 64 points of one depth range wherever the rays put their k-th sample
+    // (importance samples, rays with different clip ranges).  Nothing below locate() knows which grouping it works on: every point's answer
+    // is exact, so any table that names every sample once gives the same bits.
     const int lane = threadIdx.x & 63;
     // the lane number as a value the compiler must take afresh: index and address arithmetic on it is then redone where it is used instead of
     // being hoisted out of the work loop into registers that stay occupied for the whole kernel (the kernel lives at the 128-register limit)
@@ -414,16 +419,27 @@ __global__ __launch_bounds__(MA_BLOCK) void mesh_query_accel_kernel(const Vanerf
         // repeats a neighbour's point and does not store
         // sample index of depth k of this item for this lane, and whether the lane stores it (recomputed where needed rather than kept)
         // (the item's depth group and pixel tile: wave-uniform, divided out once; the host checks that the item count fits 32 bits)
-        int item_d0 = 0, item_x0 = 0, item_y0 = 0;
+        int item_d0 = 0, item_x0 = 0, item_y0 = 0, item_tile = 0;
         if (gnx > 0) {
             const unsigned wu = (unsigned)w, tile = wu / (unsigned)gD;
+            item_tile = __builtin_amdgcn_readfirstlane((int)tile);
             item_d0 = __builtin_amdgcn_readfirstlane((int)(wu % (unsigned)gD) * ND);
             item_x0 = __builtin_amdgcn_readfirstlane((int)(tile % (unsigned)ntx) * 8);
             item_y0 = __builtin_amdgcn_readfirstlane((int)(tile / (unsigned)ntx) * 8);
         }
         auto locate = [&](int k, bool& act) -> long long {
             long long i;
-            if (gnx > 0) {
+            if (gnx > 0 && item_order) {
+                // slot `lane` of slab d of the tile's table.  A slot without a sample (-1: a ray beyond the grid border; anything outside
+                // [0, n) is treated alike) repeats the first sample of its slab -- of the launch, if the slab names none -- and stores nothing.
+                const int d = item_d0 + k;
+                int idx = item_order[((long long)item_tile * gS + min(d, gS - 1)) * 64 + lane_now()];
+                const bool named = (unsigned long long)(unsigned)idx < (unsigned long long)n;
+                const unsigned long long m = __ballot(named);
+                const int first = __builtin_amdgcn_readlane(idx, m ? __builtin_ctzll(m) : 0);
+                act = named && d < gS;
+                i = named ? idx : m ? first : 0;
+            } else if (gnx > 0) {
                 const int d = item_d0 + k;
                 const int l = lane_now();
                 const int rx = item_x0 + (l & 7), ry = item_y0 + (l >> 3);
@@ -1139,12 +1155,16 @@ extern "C" int vanerf_knn1(const float* verts4, int nv, const float* pts, int64_
     });
 }
 
-extern "C" int vanerf_mesh_query_accel(const VanerfMeshAccel* accel, const float* verts, int nv, const int32_t* faces, int nf,
-                                       const float* vert_vis, const float* pts, int64_t n, float* sdf, uint8_t* vis, int32_t* face,
-                                       int32_t* knn_idx, int grid_nx, int grid_ny, int grid_s, void* queue_word, void* stream)
+// One body for both query entries: vanerf_mesh_query_accel is the NULL-order case (its messages name that entry for either).
+extern "C" int vanerf_mesh_query_accel_ordered(const VanerfMeshAccel* accel, const float* verts, int nv, const int32_t* faces, int nf,
+                                               const float* vert_vis, const float* pts, int64_t n, float* sdf, uint8_t* vis, int32_t* face,
+                                               int32_t* knn_idx, int grid_nx, int grid_ny, int grid_s, void* queue_word,
+                                               const int32_t* item_order, void* stream)
 {
     return guarded([&] {
         if (n == 0) return; // an empty batch is valid (and has null data pointers)
+        if (item_order && grid_nx <= 0) throw_error("vanerf_mesh_query_accel_ordered: an item order needs the ray-grid hint");
+        if (item_order && n > 0x7fffffffLL) throw_error("vanerf_mesh_query_accel_ordered: n = %lld does not fit the table's 32-bit sample indices", (long long)n);
         if (!accel || !verts || !faces || !vert_vis || !pts || !sdf || !vis) throw_error("vanerf_mesh_query_accel: null argument");
         const VanerfMeshAccel& A = *accel;
         if (!A.tri || !A.sphere || !A.tnorm || !A.orig || !A.cbox || !A.cdisc || !A.cell_start || !A.cell_tri || !A.cell_rec || !A.grid) throw_error("vanerf_mesh_query_accel: accel has a null pointer");
@@ -1186,12 +1206,20 @@ extern "C" int vanerf_mesh_query_accel(const VanerfMeshAccel* accel, const float
         const long long waves = (long long)resident * (MA_BLOCK / 64), items_nd = (n + 64 * ND_MAX - 1) / (64 * ND_MAX);
         if (ND_MAX > 1 && items_nd >= 4 * waves)
             hipLaunchKernelGGL(mesh_query_accel_kernel<ND_MAX>, dim3((unsigned)blocks), dim3(MA_BLOCK), lds, (hipStream_t)stream, A, verts, faces, vert_vis,
-                               pts, (long long)n, sdf, vis, face, knn_idx, grid_nx, grid_ny, grid_s, queue);
+                               pts, (long long)n, sdf, vis, face, knn_idx, grid_nx, grid_ny, grid_s, queue, item_order);
         else
             hipLaunchKernelGGL(mesh_query_accel_kernel<1>, dim3((unsigned)blocks), dim3(MA_BLOCK), lds, (hipStream_t)stream, A, verts, faces, vert_vis,
-                               pts, (long long)n, sdf, vis, face, knn_idx, grid_nx, grid_ny, grid_s, queue);
+                               pts, (long long)n, sdf, vis, face, knn_idx, grid_nx, grid_ny, grid_s, queue, item_order);
         HIP_CHECK(hipGetLastError());
     });
+}
+
+extern "C" int vanerf_mesh_query_accel(const VanerfMeshAccel* accel, const float* verts, int nv, const int32_t* faces, int nf,
+                                       const float* vert_vis, const float* pts, int64_t n, float* sdf, uint8_t* vis, int32_t* face,
+                                       int32_t* knn_idx, int grid_nx, int grid_ny, int grid_s, void* queue_word, void* stream)
+{
+    return vanerf_mesh_query_accel_ordered(accel, verts, nv, faces, nf, vert_vis, pts, n, sdf, vis, face, knn_idx, grid_nx, grid_ny, grid_s, queue_word,
+                                           nullptr, stream);
 }
 
 #ifdef VANERF_MESH_PHASES
@@ -1205,6 +1233,126 @@ extern "C" int vanerf_debug_mesh_phases(unsigned long long* out8, int reset)
 #endif
 
 extern "C" int vanerf_mesh_cluster_size(void) { return CL; }
+
+// ---------------------------------------------------------------------------------------------------------------
+// vanerf_mesh_tile_order: the item order of vanerf_mesh_query_accel_ordered.  One block per 8 x 8 pixel tile sorts the tile's 64 S samples by
+// the depth they were made from, in LDS, by a merge sort by ranks: every element finds its place in the merged run by a search of the
+// sibling run, and the passes go from one pair of LDS arrays (32-bit keys: the depth as an ordered integer; 16-bit index within the tile)
+// to the other.  Stable without the index in the key: the first runs are in index order, and of equal keys the one from the earlier run goes
+// first (a key of the earlier run counts the sibling's keys below it, a key of the later run those not above it) -- ties keep ray-major
+// index order, the table is the same on every run, no atomics.
+//   * A ray's depths nearly always ascend already (linspace, sorted importance samples): then the first runs are the rays themselves (6
+//     passes instead of log2(64 S)); a tile with a ray that does not (or with a NaN) starts from runs of one element.  Runs need not be
+//     powers of two.
+//   * The kernel is bound by its LDS reads, counted per WAVE: a loop runs as long as its slowest lane (measured on the benchmark view: 64-bit
+//     keys and a bisection per element, 57 reads each, 0.32 ms; 32-bit keys and a search that gallops from the element's own offset, short
+//     in most lanes but long in some lane of nearly every wave, 0.26 ms).  So a thread takes four consecutive keys of a run: a bisection
+//     for the first -- the same trip count in every lane -- and for the others a gallop upwards from the previous key's rank, which
+//     neighbouring rays (samples at nearly the same depths) end within a step or two.
+namespace {
+
+constexpr int TO_BLOCK = 1024;
+constexpr int TO_MAX_S = 128; // 64 S elements of 2 x (4 + 2) bytes: 96 KB of the CU's 160 KB
+static_assert(64 * TO_MAX_S <= 65536, "the index within a tile is kept in 16 bits");
+
+__global__ __launch_bounds__(TO_BLOCK) void mesh_tile_order_kernel(const float* __restrict__ z, int gnx, int gny, int S, int32_t* __restrict__ order)
+{
+    extern __shared__ unsigned s_tile[]; // [2][64 S] keys, then [2][64 S] 16-bit indices
+    const int N = 64 * S;
+    // (Measured and dropped: four dwords of padding per 32 keys against the power-of-two strides of the bisections' probes: 0.21 / 0.24 ms
+    //  against 0.18 / 0.20 on the coarse / fine depths of the benchmark view.)
+    unsigned* src = s_tile;
+    unsigned* dst = s_tile + N;
+    unsigned short* src_i = reinterpret_cast<unsigned short*>(s_tile + 2 * N);
+    unsigned short* dst_i = src_i + N;
+    const int ntx = (gnx + 7) >> 3;
+    const int x0 = (int)(blockIdx.x % (unsigned)ntx) * 8, y0 = (int)(blockIdx.x / (unsigned)ntx) * 8;
+    for (int e = threadIdx.x; e < N; e += TO_BLOCK) {
+        const int l = e / S, d = e - l * S;
+        const int rx = x0 + (l & 7), ry = y0 + (l >> 3);
+        unsigned u = 0xffffffffu; // a ray beyond the grid border: behind every sample
+        if (rx < gnx && ry < gny) {
+            u = __float_as_uint(z[((long long)ry * gnx + rx) * S + d] + 0.0f); // (-0 becomes +0: they compare equal)
+            u ^= (u >> 31) ? 0xffffffffu : 0x80000000u;                         // ascending as unsigned
+            u = min(u, 0xfffffffeu);                                            // (only a NaN of the last payload gets there)
+        }
+        src[e] = u;
+        src_i[e] = (unsigned short)e;
+    }
+    __syncthreads();
+    int descends = 0;
+    for (int e = threadIdx.x; e < N; e += TO_BLOCK) descends |= (e % S != 0) && src[e - 1] > src[e];
+    for (int L = __syncthreads_or(descends) ? 1 : S; L < N; L *= 2) {
+        // four consecutive keys of a run per thread (one where the runs are no multiple of four), read in one 16-byte read
+        const int E = (L & 3) ? 1 : 4;
+        for (int c = threadIdx.x * E; c < N; c += TO_BLOCK * E) {
+            unsigned key4[4] = {};
+            unsigned idx4[4] = {};
+            if (E == 4) {
+                const uint4 k = *reinterpret_cast<const uint4*>(src + c);
+                const uint2 i = *reinterpret_cast<const uint2*>(src_i + c);
+                key4[0] = k.x; key4[1] = k.y; key4[2] = k.z; key4[3] = k.w;
+                idx4[0] = i.x & 0xffffu; idx4[1] = i.x >> 16; idx4[2] = i.y & 0xffffu; idx4[3] = i.y >> 16;
+            } else {
+                key4[0] = src[c];
+                idx4[0] = src_i[c];
+            }
+            const int a0 = c / (2 * L) * (2 * L), b0 = min(a0 + L, N), end = min(a0 + 2 * L, N);
+            const bool in_a = c < b0;
+            const unsigned* const sib = src + (in_a ? b0 : a0); // the sibling run
+            const int len = in_a ? end - b0 : L;
+            // a0 + (offset in the own run) + rank: e + rank for a key of the earlier run, a0 + (e - b0) + rank for one of the later
+            const int place0 = c - b0 + (in_a ? b0 : a0);
+            int lo = 0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if (j >= E) break;
+                const unsigned key = key4[j];
+                // `below`: the sibling's keys that go in front of this one; the rank is the first index that is not below (they ascend)
+                auto below = [&](int i) { return in_a ? sib[i] < key : sib[i] <= key; };
+                int hi = len; // the rank is in [lo, hi]
+                if (j > 0) {  // gallop up from the previous key's rank: 1, 2, 4, ... until the rank is bracketed
+                    for (int step = 1; lo + step - 1 < hi; step *= 2) {
+                        const int p = lo + step - 1;
+                        if (below(p)) lo = p + 1; else { hi = p; break; }
+                    }
+                }
+                while (lo < hi) { // bisection: the whole sibling run for a thread's first key (the same trip count in every lane)
+                    const int mid = (lo + hi) >> 1;
+                    if (below(mid)) lo = mid + 1; else hi = mid;
+                }
+                dst[place0 + j + lo] = key;
+                dst_i[place0 + j + lo] = (unsigned short)idx4[j];
+            }
+        }
+        __syncthreads();
+        unsigned* const t = src; src = dst; dst = t;
+        unsigned short* const ti = src_i; src_i = dst_i; dst_i = ti;
+    }
+    for (int e = threadIdx.x; e < N; e += TO_BLOCK) {
+        const int local = src_i[e], l = local / S, d = local - l * S;
+        const int rx = x0 + (l & 7), ry = y0 + (l >> 3);
+        order[(long long)blockIdx.x * N + e] = (rx < gnx && ry < gny) ? (ry * gnx + rx) * S + d : -1;
+    }
+}
+
+} // namespace
+
+extern "C" int vanerf_mesh_tile_order(const float* z, int grid_nx, int grid_ny, int grid_s, int32_t* order, void* stream)
+{
+    return guarded([&] {
+        if (!z || !order) throw_error("vanerf_mesh_tile_order: null argument");
+        if (grid_nx <= 0 || grid_ny <= 0 || grid_s <= 0) throw_error("vanerf_mesh_tile_order: grid %d x %d x %d", grid_nx, grid_ny, grid_s);
+        if (grid_s > TO_MAX_S) throw_error("vanerf_mesh_tile_order: %d samples per ray (limit %d: a tile is sorted in LDS)", grid_s, TO_MAX_S);
+        const long long tiles = (long long)((grid_nx + 7) >> 3) * ((grid_ny + 7) >> 3);
+        if (tiles * 64 * grid_s > 0x7fffffffLL) throw_error("vanerf_mesh_tile_order: grid %d x %d x %d does not fit 32-bit sample indices", grid_nx, grid_ny, grid_s);
+        const size_t lds = (sizeof(unsigned) + sizeof(unsigned short)) * 2 * 64 * (size_t)grid_s;
+        if (lds > 64 * 1024) // above the default dynamic-LDS limit
+            HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(mesh_tile_order_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(mesh_tile_order_kernel, dim3((unsigned)tiles), dim3(TO_BLOCK), lds, (hipStream_t)stream, z, grid_nx, grid_ny, grid_s, order);
+        HIP_CHECK(hipGetLastError());
+    });
+}
 
 // ---------------------------------------------------------------------------------------------------------------
 // vanerf_mesh_accel_build: the tables of VanerfMeshAccel, built on the device without a host synchronisation (one per source frame).

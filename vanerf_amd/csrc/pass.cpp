@@ -4,6 +4,8 @@
 // caller-provided scratch block -- no allocation, no host synchronisation, nothing kept between calls.
 #include "common.h"
 
+#include <cstdlib>
+
 using namespace vanerf;
 
 namespace {
@@ -29,7 +31,8 @@ struct Layout {
     float *raw_c, *rgba_cf;      // noisy reuse: the coarse points' raw outputs, and their eval_func with the fine batch's draws
     uint8_t *valid_c, *valid_f;
     uint8_t *q_vis;
-    int32_t *knn, *order, *src;
+    int32_t *knn, *order, *src, *tile_order;
+    int64_t tile_order_slots;
     unsigned long long* queue_words; // work-queue heads of the pass's four big launches (mesh query and per-sample networks, coarse and fine)
     void* order_scratch;
     int64_t order_scratch_bytes, total;
@@ -53,6 +56,11 @@ Layout carve(void* base, int R, int Sc, int Sf, int fine, int reuse, int n_views
     L.order = c.take<int32_t>(nmax);
     L.order_scratch_bytes = vanerf_query_order_scratch(nmax);
     L.order_scratch = c.take<uint8_t>(L.order_scratch_bytes);
+    // The mesh query's item order (vanerf_mesh_tile_order) pads every 8 x 8 pixel tile to 64 rays, and L.order is still needed behind it.  The
+    // size query does not know the grid's sides: a quarter on top holds any grid with both sides >= 64 or multiples of 8; a launch whose
+    // table would not fit (small, ragged grids) keeps the index grouping.
+    L.tile_order_slots = (5 * nmax + 3) / 4;
+    L.tile_order = c.take<int32_t>(L.tile_order_slots);
     L.q_sdf_c = c.take<float>(nc);
     L.rgba_c = c.take<float>(5 * nc);
     L.contrib = c.take<float>(nc);
@@ -75,6 +83,17 @@ Layout carve(void* base, int R, int Sc, int Sf, int fine, int reuse, int n_views
     return L;
 }
 
+constexpr int MESH_TILE_ORDER_MAX_S = 128; // vanerf_mesh_tile_order sorts a tile in LDS: it refuses more samples per ray
+constexpr int MESH_TILE_ORDER_DEFAULT = 3;
+
+// VANERF_MESH_TILE_ORDER (read at every pass, for tests and A/B runs): which mesh launches group their tiles' samples by depth.  0: none (the
+// index grouping), 1: the coarse launch, 2: the fine launch, 3: both; unset or anything else: the default.  The results do not depend on it.
+int mesh_tile_order_mode()
+{
+    const char* e = std::getenv("VANERF_MESH_TILE_ORDER");
+    return (e && e[0] >= '0' && e[0] <= '3' && !e[1]) ? e[0] - '0' : MESH_TILE_ORDER_DEFAULT;
+}
+
 void ok(int rc, const char* what)
 {
     if (rc != VANERF_OK) {
@@ -94,12 +113,21 @@ void run_marches(const VanerfWeights* w, const VanerfFrame* frame, const VanerfM
     const int grid_nx = d.pixels_xy ? 0 : d.nx, grid_ny = d.pixels_xy ? 0 : d.n_views * d.ny;
     // one march: points, mesh query (+ 1-NN), validity partition, per-sample networks
     int marches = 0; // every launch with a work queue gets a word of its own from the scratch block (nothing is shared between launches in flight)
+    const int tile_order_mode = mesh_tile_order_mode();
     auto march = [&](const float* z, int S, const float* noise, float* q_sdf, float* rgba, uint8_t* valid_raw = nullptr) { // valid_raw: raw outputs + flags
+        const bool fine_launch = marches > 0;
         unsigned long long* const qw = L.queue_words + 2 * marches++;
         const int64_t n = (int64_t)R * S;
         ok(vanerf_sample_points(L.rays_d, L.cam_pos, z, R, rays_per_view, S, L.pts, stream), "sample points");
-        ok(vanerf_mesh_query_accel(accel, verts, nv, faces, nf, frame->vert_vis, L.pts, n, q_sdf, L.q_vis, nullptr, L.knn, grid_nx, grid_ny, grid_nx ? S : 0, qw,
-                                   stream), "mesh query");
+        // the tile's samples in depth order (z: the depths L.pts were just made from); a table that does not fit: no order, same results
+        const int32_t* tile_order = nullptr;
+        const int64_t slots = (int64_t)((grid_nx + 7) / 8) * ((grid_ny + 7) / 8) * 64 * S;
+        if (grid_nx && S <= MESH_TILE_ORDER_MAX_S && slots <= L.tile_order_slots && (tile_order_mode & (fine_launch ? 2 : 1))) {
+            ok(vanerf_mesh_tile_order(z, grid_nx, grid_ny, S, L.tile_order, stream), "mesh tile order");
+            tile_order = L.tile_order;
+        }
+        ok(vanerf_mesh_query_accel_ordered(accel, verts, nv, faces, nf, frame->vert_vis, L.pts, n, q_sdf, L.q_vis, nullptr, L.knn, grid_nx, grid_ny,
+                                           grid_nx ? S : 0, qw, tile_order, stream), "mesh query");
         const int32_t* order = nullptr;
         if (n >= PARTITION_MIN_SAMPLES) {
             ok(vanerf_query_order(frame, L.pts, n, L.order, L.order_scratch, L.order_scratch_bytes, stream), "validity partition");

@@ -509,18 +509,45 @@ def _queue_word(dev):
     return torch.empty(2, dtype=torch.int32, device=dev)
 
 
-def mesh_query_accel(accel, verts3, faces_i32, vert_vis, pts, want_face=False, want_knn=True, grid=None):
+MESH_TILE_ORDER_MAX_S = 128  # vanerf_mesh_tile_order sorts a tile in LDS: it refuses more samples per ray
+MESH_TILE_ORDER_DEFAULT = 3
+
+
+def mesh_tile_order_mode():
+    """VANERF_MESH_TILE_ORDER (read at every pass, as csrc/pass.cpp does): which mesh launches of a pass group their tiles' samples by depth.
+    0: none (the index grouping), 1: the coarse launch, 2: the fine launch, 3: both; unset or anything else: the default."""
+    e = os.environ.get("VANERF_MESH_TILE_ORDER", "")
+    return int(e) if e in ("0", "1", "2", "3") else MESH_TILE_ORDER_DEFAULT
+
+
+def mesh_tile_order(z, nx, ny):
+    """vanerf_mesh_tile_order: z (nx * ny, S) depths of a ray grid -> int32 table (tiles, S, 64): per 8 x 8 pixel tile its sample indices in
+    ascending depth (stable), -1 for the rays beyond the grid border, at the end of their tile."""
+    S = z.shape[1]
+    if z.shape[0] != nx * ny:
+        raise ValueError(f"mesh_tile_order: {z.shape[0]} rays for a {nx} x {ny} grid")
+    order = torch.empty(((nx + 7) // 8) * ((ny + 7) // 8), S, 64, dtype=torch.int32, device=z.device)
+    check(lib.vanerf_mesh_tile_order(_ptr(z, torch.float32), int(nx), int(ny), int(S), _ptr(order), _stream()))
+    return order
+
+
+def mesh_query_accel(accel, verts3, faces_i32, vert_vis, pts, want_face=False, want_knn=True, grid=None, item_order=None):
     """Same results as mesh_query (+ knn1), through the per-frame acceleration structure: sdf, vis[, face][, knn].
-    grid = (nx, ny, S): pts are the samples of an nx x ny ray grid, S per ray, ray-major (speed hint only)."""
+    grid = (nx, ny, S): pts are the samples of an nx x ny ray grid, S per ray, ray-major (speed hint only).
+    item_order: with a grid, the int32 table of mesh_tile_order (vanerf_mesh_query_accel_ordered; speed only: any table that names every
+    sample once gives the same bits)."""
     gnx, gny, gs = grid if grid is not None else (0, 0, 0)
+    if item_order is not None and item_order.numel() != ((gnx + 7) // 8) * ((gny + 7) // 8) * 64 * gs:
+        raise ValueError("mesh_query_accel: item_order does not have 64 * S slots per 8 x 8 pixel tile of the grid")
     n = pts.shape[0]
     sdf = torch.empty(n, dtype=torch.float32, device=pts.device)
     vis = torch.empty(n, dtype=torch.uint8, device=pts.device)
     face = torch.empty(n, dtype=torch.int32, device=pts.device) if want_face else None
     knn = torch.empty(n, dtype=torch.int32, device=pts.device) if want_knn else None
-    check(lib.vanerf_mesh_query_accel(byref(accel.c), _ptr(verts3, torch.float32), verts3.shape[0], _ptr(faces_i32, torch.int32),
-                                      faces_i32.shape[0], _ptr(vert_vis, torch.float32), _ptr(pts, torch.float32), n, _ptr(sdf), _ptr(vis),
-                                      _ptr(face), _ptr(knn), int(gnx), int(gny), int(gs), _ptr(_queue_word(pts.device)), _stream()))
+    check(lib.vanerf_mesh_query_accel_ordered(byref(accel.c), _ptr(verts3, torch.float32), verts3.shape[0], _ptr(faces_i32, torch.int32),
+                                              faces_i32.shape[0], _ptr(vert_vis, torch.float32), _ptr(pts, torch.float32), n, _ptr(sdf), _ptr(vis),
+                                              _ptr(face), _ptr(knn), int(gnx), int(gny), int(gs), _ptr(_queue_word(pts.device)),
+                                              _ptr(item_order, torch.int32), _stream()))
     return tuple(t for t in (sdf, vis, face, knn) if t is not None)
 
 
@@ -880,10 +907,15 @@ def render_pass(weights, frame, cam_tar, bounds, x0, y0, step, nx, ny, sample_pe
                                    float(frame.c.invalid_sdf), _ptr(out), None, _stream()))
         return out
 
-    def evaluate(z, draws=None, raw=False):
+    tile_order_mode = mesh_tile_order_mode()
+
+    def evaluate(z, draws=None, raw=False, fine_launch=False):
         pts = sample_points(rays["rays_d"], rays["cam_pos"], z)
         grid = (nx, ny, z.shape[1]) if pixels is None else None
-        q_sdf, q_vis, knn = mesh_query_accel(frame.accel, frame.verts3, frame.faces, frame.vert_vis, pts, grid=grid)
+        # the tiles' samples in depth order (z: the depths pts were just made from), as csrc/pass.cpp does
+        use_order = grid is not None and z.shape[1] <= MESH_TILE_ORDER_MAX_S and tile_order_mode & (2 if fine_launch else 1)
+        item_order = mesh_tile_order(z, nx, ny) if use_order else None
+        q_sdf, q_vis, knn = mesh_query_accel(frame.accel, frame.verts3, frame.faces, frame.vert_vis, pts, grid=grid, item_order=item_order)
         noise = scaled(draws, pts.shape[0]) if noise_std > 0.0 and not raw else None
         order = query_order(frame, pts) if pts.shape[0] >= PARTITION_MIN_SAMPLES else None
         if kernel_events is not None:  # HIP events around the dominant kernel alone (the partition kernels are outside), on the stream it is launched on
@@ -924,7 +956,7 @@ def render_pass(weights, frame, cam_tar, bounds, x0, y0, step, nx, ny, sample_pe
             ids = torch.where(src >= 0, src, Sc + (-src - 1)).long()
             pos = torch.empty_like(ids).scatter_(1, ids, torch.arange(Sc + Sf, device=ids.device).expand(R, -1))
             noise_f = scaled(None if noise_draws is None else noise_draws[1], R * (Sc + Sf)).view(R, Sc + Sf)
-            f = evaluate(z_new, raw=True)
+            f = evaluate(z_new, raw=True, fine_launch=True)
             f["noise"] = noise_f.gather(1, pos[:, Sc:]).reshape(-1).contiguous()
             f["rgba"] = eval_func(f["raw"], f["valid"], f["noise"]).view(R, Sf, 5)
             cf = {"noise": noise_f.gather(1, pos[:, :Sc]).reshape(-1).contiguous()}  # the coarse points as the fine batch sees them
@@ -932,11 +964,11 @@ def render_pass(weights, frame, cam_tar, bounds, x0, y0, step, nx, ny, sample_pe
             f["color"], f["depth"], f["alpha"], f["contrib"], f["sdf"] = composite_merged(cf["rgba"], c["q_sdf"], f["rgba"], f["q_sdf"], src,
                                                                                           z_fine, weights, want_contrib=debug)
         elif reuse_coarse:
-            f = evaluate(z_new)
+            f = evaluate(z_new, fine_launch=True)
             f["color"], f["depth"], f["alpha"], f["contrib"], f["sdf"] = composite_merged(c["rgba"], c["q_sdf"], f["rgba"], f["q_sdf"], src,
                                                                                           z_fine, weights, want_contrib=debug)
         else:
-            f = evaluate(z_fine, None if noise_draws is None else noise_draws[1])
+            f = evaluate(z_fine, None if noise_draws is None else noise_draws[1], fine_launch=True)
             f["color"], f["depth"], f["alpha"], f["contrib"], f["sdf"] = composite(f["rgba"], z_fine, f["q_sdf"], weights, want_contrib=debug)
         out.update({"color_fine": f["color"], "depth_fine": f["depth"], "alpha_fine": f["alpha"], "sdf": f["sdf"], "z_fine": z_fine, "z_new": z_new})
         if debug:
