@@ -117,10 +117,14 @@ int vanerf_weights_short_groups(const VanerfWeights* w, uint64_t* count);
 int vanerf_weights_pack_host(const VanerfWeightTable* w, float* out, int64_t cap, int64_t* n_out, unsigned* offsets);
 /* Host-only view of any stream a handle can carry: which = 0 the fp32 forward stream, 1 the bf16x3 forward stream (32-bit words of two bf16
  * each, copied raw), 2 the transposed fp32 stream of the fused backward pass, 3 the hoisted bf16x3 stream a bf16x3 handle carries behind
- * stream 1 (what vanerf_query_samples runs on when it is given vertex_products: three first layers packed with their per-sample k-pairs only).  out[cap] or NULL: the size. */
+ * stream 1 (three first layers packed with their per-sample k-pairs only), 4 the lean bf16x3 stream behind that (what vanerf_query_samples
+ * runs on when it is given vertex_products: the hoisted stream with geo_vis_fusion.fconv_ated.2 / fconv_ated1.2 multiplied into
+ * mlp_geo.layers1's layers 0 / 2, no bias k-pair in five layers, one k-pair less in TexVisFusion's input), 5 the lean stream's fp32 bias table
+ * (five layers' biases in accumulator-register order), 6 its two folded matrices in fp32 ([128][64], then [120][8]).  out[cap] or NULL: the size. */
 int vanerf_weights_stream_host(const VanerfWeightTable* w, int which, float* out, int64_t cap, int64_t* n_out);
 /* The streams a handle holds on the device, copied back to host memory (blocking; for tests of vanerf_weights_update): which = 0 the forward
- * stream of the handle's mode, 2 the backward stream (fp32 handles only), 3 the hoisted bf16x3 stream (bf16x3 handles only).                     */
+ * stream of the handle's mode, 2 the backward stream (fp32 handles only), 3 / 4 / 5 / 6 the hoisted bf16x3 stream, the lean bf16x3 stream, its
+ * bias table and its folded matrices (bf16x3 handles only).                                                                                      */
 int vanerf_weights_download(const VanerfWeights* w, int which, float* out, int64_t cap, int64_t* n_out);
 
 /* a1-a4  Pixel grid, ray generation, bbox clipping, coarse depths (src/model.py:1191-1238, 1496-1570), described by a VanerfPassDesc (below).
@@ -243,8 +247,11 @@ int vanerf_knn1(const float* verts4, int nv, const float* pts, int64_t n, int32_
  *     raw = 0 -> out[N][5] = [alpha, sdf, r, g, b] (eval_func applied);  raw = 1 -> [sdf_pred, rad, r, g, b] as VANeRF.query returns
  *     valid[N] (u8, may be NULL)
  *     vertex_products: the frame's table from vanerf_vertex_products below (built with the same handle, after its last update), or NULL.  With the
- *         table a bf16x3 handle runs the hoisted kernel: it starts the three layers' accumulators from the gathered table rows and runs their
- *         per-sample k-steps only (outputs within 1e-5 of the un-hoisted kernel's: summation order).  NULL selects the un-hoisted kernel.       */
+ *         table a bf16x3 handle runs the lean kernel on its lean stream (which = 4 above): it starts the three layers' accumulators from the
+ *         gathered table rows and runs their per-sample k-steps only, reads the two folded layers' products from the packed weights and starts
+ *         five more accumulators from the bias table (outputs within 2e-5 of the un-hoisted kernel's: summation order).  The environment
+ *         variable VANERF_LEAN_STREAM=0, read at every launch, selects the hoisted kernel on the hoisted stream instead (the lean kernel's
+ *         predecessor, for A/B runs).  NULL selects the un-hoisted kernel.                                                                    */
 int vanerf_query_samples(const VanerfWeights* w, const VanerfFrame* frame, const float* pts, const float* query_sdf,
                          const uint8_t* query_vis, const int32_t* knn_idx, const float* noise, const int32_t* order, int raw, int64_t n,
                          float* out, uint8_t* valid, void* queue_word /* as for vanerf_mesh_query_accel */, const float* vertex_products,

@@ -15,7 +15,7 @@ ap.add_argument("--iters", type=int, default=5)
 ap.add_argument("--rows", type=int, default=512)
 ap.add_argument("--mode", type=int, default=0, help="0 = fp32 MFMA, 1 = split-bf16 x3")
 ap.add_argument("--order", type=int, default=1, help="1: work order from the validity partition (what render_pass does), 0: natural order")
-ap.add_argument("--vertex-products", type=int, default=1, help="mode 1: 1 = the hoisted kernel on the frame's table of per-vertex products (the default path), 0 = the un-hoisted kernel")
+ap.add_argument("--vertex-products", type=int, default=1, help="mode 1: 1 = the lean kernel on the frame's table of per-vertex products (the default path; VANERF_LEAN_STREAM=0: the hoisted kernel), 0 = the un-hoisted kernel")
 args = ap.parse_args()
 sd = synth.make_full_weights(0)
 frame = synth.make_frame(seed=11, tar_h=512, tar_w=334, orbit_deg=15.0)

@@ -26,20 +26,25 @@ extern "C" int vanerf_weights_pack(const VanerfWeightTable* w, int mode, VanerfW
         constexpr size_t n_ptrs = offsetof(VanerfWeightTable, sigmoid_beta) / sizeof(const float*);
         for (size_t i = 0; i < n_ptrs; ++i)
             if (!ptrs[i]) throw_error("vanerf_weights_pack: weight pointer #%d is null", (int)i);
-        std::vector<float> host, host_bwd, host_h, eff;
+        std::vector<float> host, host_bwd, host_h, eff, host_l, bias;
         LayerOffsets offs{};
-        pack_weights_host(*w, host, offs, mode, mode == 0 ? &host_bwd : nullptr, mode == 1 ? &host_h : nullptr, mode == 1 ? &eff : nullptr);
+        pack_weights_host(*w, host, offs, mode, mode == 0 ? &host_bwd : nullptr, mode == 1 ? &host_h : nullptr, mode == 1 ? &eff : nullptr,
+                          mode == 1 ? &host_l : nullptr, mode == 1 ? &bias : nullptr);
+        host_l.insert(host_l.end(), bias.begin(), bias.end()); // the bias table rides behind the lean stream
         auto* h = new VanerfWeights();
         h->n_floats_bwd = host_bwd.size();
         h->n_floats = host.size();
         h->n_floats_h = host_h.size();
+        h->n_floats_l = host_l.size() - bias.size();
         h->offs = offs;
         h->mode = mode;
         h->beta = w->sigmoid_beta < 2e-3f ? 2e-3f : w->sigmoid_beta; // sdf_activation clamp (src/model.py:880)
         hipError_t e = hipGetDevice(&h->device);
-        if (e == hipSuccess) e = hipMalloc(&h->dev, (host.size() + host_h.size()) * sizeof(float));
+        if (e == hipSuccess) e = hipMalloc(&h->dev, (host.size() + host_h.size() + host_l.size()) * sizeof(float));
         if (e == hipSuccess) e = hipMemcpy(h->dev, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice);
         if (e == hipSuccess && !host_h.empty()) e = hipMemcpy(h->dev + host.size(), host_h.data(), host_h.size() * sizeof(float), hipMemcpyHostToDevice);
+        if (e == hipSuccess && !host_l.empty())
+            e = hipMemcpy(h->dev + host.size() + host_h.size(), host_l.data(), host_l.size() * sizeof(float), hipMemcpyHostToDevice);
         if (e == hipSuccess && !eff.empty()) e = hipMalloc(&h->dev_eff, eff.size() * sizeof(float));
         if (e == hipSuccess && !eff.empty()) e = hipMemcpy(h->dev_eff, eff.data(), eff.size() * sizeof(float), hipMemcpyHostToDevice);
         if (e == hipSuccess && !host_bwd.empty()) e = hipMalloc(&h->dev_bwd, host_bwd.size() * sizeof(float));
@@ -92,16 +97,21 @@ extern "C" int vanerf_weights_pack_host(const VanerfWeightTable* w, float* out, 
 }
 
 // Host-only view of any of the streams a handle can carry: which = 0 the fp32 forward stream, 1 the bf16x3 forward stream (32-bit words
-// of two bf16 each, returned as raw floats), 2 the transposed fp32 stream of the fused backward pass, 3 the hoisted bf16x3 stream (layer_spec.h).
+// of two bf16 each, returned as raw floats), 2 the transposed fp32 stream of the fused backward pass, 3 the hoisted bf16x3 stream, 4 the lean
+// bf16x3 stream, 5 the lean stream's fp32 bias table, 6 the two folded matrices of the lean stream in fp32, F0 [128][64] then F1 [120][8]
+// (layer_spec.h).
 extern "C" int vanerf_weights_stream_host(const VanerfWeightTable* w, int which, float* out, int64_t cap, int64_t* n_out)
 {
     return guarded([&] {
         if (!w || !n_out) throw_error("vanerf_weights_stream_host: null argument");
-        if (which < 0 || which > 3) throw_error("vanerf_weights_stream_host: which = %d (0 fp32, 1 bf16x3, 2 backward, 3 hoisted bf16x3)", which);
-        std::vector<float> host, bwd, hoisted;
+        if (which < 0 || which > 6)
+            throw_error("vanerf_weights_stream_host: which = %d (0 fp32, 1 bf16x3, 2 backward, 3 hoisted bf16x3, 4 lean bf16x3, 5 its bias table, 6 its folded matrices)", which);
+        std::vector<float> host, bwd, hoisted, lean, bias, eff;
         LayerOffsets offs{};
-        pack_weights_host(*w, host, offs, which == 1 ? 1 : 0, which == 2 ? &bwd : nullptr, which == 3 ? &hoisted : nullptr);
-        const std::vector<float>& src = which == 2 ? bwd : which == 3 ? hoisted : host;
+        pack_weights_host(*w, host, offs, which == 1 ? 1 : 0, which == 2 ? &bwd : nullptr, which == 3 ? &hoisted : nullptr, which == 6 ? &eff : nullptr,
+                          which == 4 ? &lean : nullptr, which == 5 ? &bias : nullptr);
+        if (which == 6) eff.erase(eff.begin(), eff.begin() + eff_fold_offset());
+        const std::vector<float>& src = which == 2 ? bwd : which == 3 ? hoisted : which == 4 ? lean : which == 5 ? bias : which == 6 ? eff : host;
         *n_out = (int64_t)src.size();
         if (out) {
             if (cap < (int64_t)src.size()) throw_error("vanerf_weights_stream_host: buffer too small");
@@ -111,14 +121,19 @@ extern "C" int vanerf_weights_stream_host(const VanerfWeightTable* w, int which,
 }
 
 // The streams a handle holds on the device, copied back (blocking; tests of vanerf_weights_update): which = 0 the forward stream of the handle's
-// mode, 2 the backward stream (fp32 handles).
+// mode, 2 the backward stream (fp32 handles), 3 / 4 / 5 / 6 the hoisted stream, the lean stream, its bias table and its folded matrices
+// (bf16x3 handles).
 extern "C" int vanerf_weights_download(const VanerfWeights* w, int which, float* out, int64_t cap, int64_t* n_out)
 {
     return guarded([&] {
         if (!w || !n_out) throw_error("vanerf_weights_download: null argument");
-        if (which != 0 && which != 2 && which != 3) throw_error("vanerf_weights_download: which = %d (0 forward, 2 backward, 3 hoisted bf16x3)", which);
-        const float* src = which == 2 ? w->dev_bwd : which == 3 ? (w->n_floats_h ? w->dev + w->n_floats : nullptr) : w->dev;
-        const size_t n = which == 2 ? w->n_floats_bwd : which == 3 ? w->n_floats_h : w->n_floats;
+        if (which != 0 && (which < 2 || which > 6))
+            throw_error("vanerf_weights_download: which = %d (0 forward, 2 backward, 3 hoisted bf16x3, 4 lean bf16x3, 5 its bias table, 6 its folded matrices)", which);
+        const float* lean = w->n_floats_l ? w->dev + w->n_floats + w->n_floats_h : nullptr;
+        const float* src = which == 2 ? w->dev_bwd : which == 3 ? (w->n_floats_h ? w->dev + w->n_floats : nullptr) : which == 4 ? lean
+                           : which == 5 ? (lean ? lean + w->n_floats_l : nullptr) : which == 6 ? (lean && w->dev_eff ? w->dev_eff + eff_fold_offset() : nullptr) : w->dev;
+        const size_t n = which == 2 ? w->n_floats_bwd : which == 3 ? w->n_floats_h : which == 4 ? w->n_floats_l : which == 5 ? (size_t)BIAS_TABLE_FLOATS
+                         : which == 6 ? (size_t)FOLD_FLOATS : w->n_floats;
         if (!src) throw_error("vanerf_weights_download: the handle carries no such stream");
         *n_out = (int64_t)n;
         if (out) {

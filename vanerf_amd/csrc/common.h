@@ -63,10 +63,13 @@ int guarded(F&& fn) noexcept
     }
 }
 
-// hoisted: the second bf16x3 stream (layer_spec.h), eff_out: the effective weights themselves (stage 1 below)
+// hoisted / lean: the second and third bf16x3 stream, bias: the lean level's fp32 bias table (layer_spec.h), eff_out: the effective weights
+// themselves (stage 1 below)
 void pack_weights_host(const VanerfWeightTable& w, std::vector<float>& out, LayerOffsets& offs, int mode = 0, std::vector<float>* bwd = nullptr,
-                       std::vector<float>* hoisted = nullptr, std::vector<float>* eff_out = nullptr);
+                       std::vector<float>* hoisted = nullptr, std::vector<float>* eff_out = nullptr, std::vector<float>* lean = nullptr,
+                       std::vector<float>* bias = nullptr);
 unsigned eff_layer_offset(int l); // where layer l's [nout][kin] matrix starts in eff
+unsigned eff_fold_offset();       // where the folded matrices F0, F1 of the lean stream start in eff (behind the last layer)
 // The packer's two stages (weights_pack.cpp): where a layer's parameters are and where its effective weights go in the flat array `eff` ...
 struct LayerSrc {
     const float* w; // [nout][kin] (weight-normed layers: weight_v)
@@ -80,6 +83,7 @@ void layer_sources(const VanerfWeightTable& w, LayerSrc out[NUM_LAYERS]);
 // the fused backward; fwd_b: the bf16x3 stream, two ints per 32-bit word (low half's id | part << 30, high half's id; part 0 = high bf16 part).
 struct PackTables {
     std::vector<int> fwd, bwd, fwd_b, fwd_bh; // fwd_bh: the hoisted bf16x3 stream (layer_spec.h)
+    std::vector<int> fwd_bl, bias;            // fwd_bl: the lean bf16x3 stream, as fwd_b; bias: its fp32 bias table, one id per float, as fwd
     LayerOffsets offs{};
     unsigned n_eff = 0;
 };
@@ -94,8 +98,9 @@ void check_camera_source(const char* who, const VanerfPassDesc& d); // render_ke
 } // namespace vanerf
 
 struct VanerfWeights {
-    float* dev = nullptr;   // packed fragment streams; bf16x3 handles: [the stream | the hoisted stream (layer_spec.h)]
+    float* dev = nullptr;   // packed fragment streams; bf16x3 handles: [the stream | the hoisted stream | the lean stream | its bias table] (layer_spec.h)
     size_t n_floats_h = 0;  // 32-bit words of the hoisted stream, which starts at dev + n_floats (bf16x3 handles only)
+    size_t n_floats_l = 0;  // 32-bit words of the lean stream, which starts at dev + n_floats + n_floats_h; BIAS_TABLE_FLOATS of bias table follow it
     float* dev_bwd = nullptr; // fp32 handles only: the transposed streams of the fused backward pass (query_backward.hip)
     size_t n_floats_bwd = 0;
     size_t n_floats = 0;

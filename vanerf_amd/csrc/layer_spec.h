@@ -69,20 +69,50 @@ constexpr unsigned layer_offset(int l)
 //   L_TEX_AT_A                   columns 11..68  = vfeat_tex[i] | vfeat_tex[tw(i)] rows  (29 of 49 k-pairs)
 // Those products come from a per-frame table (vertex_products.hip) as the accumulators' initial values; the hoisted stream of the three
 // layers holds the per-sample k-pairs only: [pix32 | (sdf, qvis) | (vis_nn, vis_tw)] and [query6 | latent12 | (qvis, vis_nn) | (vis_tw, -)].
-constexpr int kT_b(int l, bool hoist)
+//
+// A third, LEAN stream follows the hoisted one (level 2; level 0 = the plain stream, 1 = the hoisted stream).  It is the hoisted stream without
+// the work a sample's result does not need:
+//   - L_GEO_ATED0_B / L_GEO_ATED1_B have no steps: both are linear (no bias, no activation behind them) and feed the geo columns of L_MLP0 /
+//     L_MLP2 only, so the packer multiplies them into those columns (W_mlp0[:, 294:358] W_ated0_b, W_mlp2[:, 128:136] W_ated1_b) and the two
+//     consumers read relu(mid) of L_GEO_ATED*_A through the same k-pairs;
+//   - L_MLP1, L_HEAD0, L_HEAD1, L_HEAD2, L_IBR lose the bias k-pair that opened a bf16 step of its own: their accumulators start from the
+//     fp32 bias table below instead of zero;
+//   - the TexVisFusion input holds (qt[2] | vis_tw) in ONE k-pair instead of (qt[2] | 0) and (vis_tw | 0): L_TEX_A has 48 pairs (6 steps),
+//     L_TEX_AT_A 19 (still 3 steps).
+constexpr bool lean_no_bias_pair(int l) { return l == L_MLP1 || l == L_HEAD0 || l == L_HEAD1 || l == L_HEAD2 || l == L_IBR; }
+constexpr int kT_b(int l, int level)
 {
-    if (hoist && (l == L_GEO_AT0_A || l == L_GEO_ATED0_A)) return 32 + 2;
-    if (hoist && l == L_TEX_AT_A) return 6 + 12 + 2;
+    if (level >= 1 && (l == L_GEO_AT0_A || l == L_GEO_ATED0_A)) return 32 + 2;
+    if (level >= 1 && l == L_TEX_AT_A) return 6 + 12 + (level == 2 ? 1 : 2);
+    if (level == 2 && (l == L_GEO_ATED0_B || l == L_GEO_ATED1_B)) return 0;
+    if (level == 2 && lean_no_bias_pair(l)) return kT[l] - 1;
+    if (level == 2 && l == L_TEX_A) return 48;
     return kT[l];
 }
-constexpr int steps_b(int l, bool hoist = false) { return (kT_b(l, hoist) + 7) / 8; }
-constexpr unsigned layer_dwords_b(int l, bool hoist = false) { return (unsigned)steps_b(l, hoist) * (unsigned)kNB[l] * 2u * 64u * 4u; }
-constexpr unsigned layer_offset_b(int l, bool hoist = false)
+constexpr int steps_b(int l, int level = 0) { return (kT_b(l, level) + 7) / 8; }
+constexpr unsigned layer_dwords_b(int l, int level = 0) { return (unsigned)steps_b(l, level) * (unsigned)kNB[l] * 2u * 64u * 4u; }
+constexpr unsigned layer_offset_b(int l, int level = 0)
 {
     unsigned o = 0;
-    for (int i = 0; i < l; ++i) o += layer_dwords_b(i, hoist);
+    for (int i = 0; i < l; ++i) o += layer_dwords_b(i, level);
     return o;
 }
+// The lean level's bias table, fp32, directly behind the lean stream's slack: the five layers above in enum order, each
+// [lane half h][block ob][register r] = bias of output row 32 ob + (r & 3) + 8 (r >> 2) + 4 h (the D-register order, as the vertex-product rows
+// below); rows beyond the layer's outputs hold 0.
+constexpr unsigned bias_table_floats(int l) { return lean_no_bias_pair(l) ? 2u * (unsigned)kNB[l] * 16u : 0u; }
+constexpr unsigned bias_table_offset(int l)
+{
+    unsigned o = 0;
+    for (int i = 0; i < l; ++i) o += bias_table_floats(i);
+    return o;
+}
+constexpr unsigned BIAS_TABLE_FLOATS = bias_table_offset(NUM_LAYERS);
+constexpr unsigned STREAM_SLACK_DW = 2u * 64u * 4u; // zero words behind the last layer of every stream
+// The folded matrices live behind the layers' own effective weights in `eff` (weights_pack.cpp): F0 [128][64], then F1 [120][8], each element
+// one fmaf chain over the inner index in ascending order (host and device agree bit for bit).
+constexpr unsigned FOLD0_ROWS = 128u, FOLD0_COLS = 64u, FOLD1_ROWS = 120u, FOLD1_COLS = 8u;
+constexpr unsigned FOLD_FLOATS = FOLD0_ROWS * FOLD0_COLS + FOLD1_ROWS * FOLD1_COLS;
 
 // The table of per-vertex products (vanerf_vertex_products), fp32, four sub-tables one after the other.  A vertex's row of a sub-table with NB
 // output blocks is [lane half h][block ob][register r] = output row 32 ob + (r & 3) + 8 (r >> 2) + 4 h of the layer: the D-register order, so

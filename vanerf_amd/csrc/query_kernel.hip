@@ -10,12 +10,15 @@
 // The fp32 kernel uses no LDS beyond its control words: key points come through the scalar cache, weights stream from L2 as pre-permuted
 // MFMA A-fragments (weights_pack.cpp).  The split-bf16 kernel owns its CU's LDS: key points, the resident fragments of the last layers and
 // the ring the eight waves of a block share the streamed fragments through (see the LDS map below).  The 1-NN vertex index arrives from
-// vanerf_mesh_query_accel.  query_kernel<1, false, true> is the HOISTED split-bf16 kernel: three first layers start from the per-vertex
-// products of vertex_products.hip and run their per-sample k-steps only (layer_spec.h).
+// vanerf_mesh_query_accel.  query_kernel<1, false, 1> is the HOISTED split-bf16 kernel: three first layers start from the per-vertex
+// products of vertex_products.hip and run their per-sample k-steps only (layer_spec.h).  query_kernel<1, false, 2> is the LEAN kernel: the
+// hoisted one on the lean stream -- two linear layers folded into their consumers, five accumulators started from a bias table, one k-pair
+// less in the TexVisFusion input, the two last head layers resident (layer_spec.h).
 //
 // Built with -ffp-contract=off: the integer-valued outputs (1-NN index) depend on fp32 compare
 // results and must match oracle/mesh_oracle.c bit for bit; fused multiply-adds are spelled fmaf().
 #include <algorithm>
+#include <cstdlib>
 #include <utility>
 
 #include "common.h"
@@ -97,32 +100,40 @@ struct FragB { u32x4 hi, lo; }; // A fragments (hi and lo parts) of one 32-row o
 // fragment stream loads most (profiles/r02_a_*): ds_read_b128 has four times that width and a fifth of the latency.
 // Layers LDS_FIRST .. NUM_LAYERS-1 are copied once per block: ibr_compress and the four TexVisFusion layers (126 KB: what the all-invalid
 // groups need).  The layers in front of them are SHARED by the block's waves through an LDS ring of 32 KB (below).
-constexpr int LDS_FIRST = L_IBR;
-// (HOIST: the hoisted stream of layer_spec.h -- three layers are shorter, so every offset, the ring's phases and the resident size differ)
-template <bool HOIST> constexpr unsigned RES_BASE_DW = layer_offset_b(LDS_FIRST, HOIST);
-template <bool HOIST> constexpr unsigned RES_DW = layer_offset_b(NUM_LAYERS, HOIST) - layer_offset_b(LDS_FIRST, HOIST);
+// The lean stream is short enough for L_HEAD1 and L_HEAD2 to stay as well (24 KB more): four ring phases and their barriers less per round.
+// (LEVEL: the stream of layer_spec.h the kernel walks, 0 plain, 1 hoisted, 2 lean -- layers differ in length, so every offset, the ring's phases
+// and the resident size differ)
+template <int LEVEL> constexpr int LDS_FIRST = LEVEL == 2 ? L_HEAD1 : L_IBR;
+template <int LEVEL> constexpr unsigned RES_BASE_DW = layer_offset_b(LDS_FIRST<LEVEL>, LEVEL);
+template <int LEVEL> constexpr unsigned RES_DW = layer_offset_b(NUM_LAYERS, LEVEL) - layer_offset_b(LDS_FIRST<LEVEL>, LEVEL);
 // (The key points live in LDS because 256 registers per wave hold nothing long-lived: one ds_read_b128 per key point and group.)
 // LDS map of the split-bf16 kernel (all of it in the dynamic region, which then starts at LDS address 0: no static __shared__ in this kernel):
 //   [0, 672)      the 42 key points as float4                              [672, 768)  control words: s_base[2], s_valid[2][waves per block]
 //   [1024, 1024 + 32 KB)     fragment ring                                 [LDS_RES, LDS_RES + RES_DW * 4)  resident fragments
+//   lean kernel: [LDS_RES + RES_DW * 4, + 1280)  the bias table (layer_spec.h)
 constexpr unsigned RING_PHASE_PIECES = 16u, RING_BYTES = 2u * RING_PHASE_PIECES * 1024u; // two halves of one 16 KB phase each
 constexpr unsigned LDS_KPT = 0u, LDS_CTRL = 2u * PE_KPT_PER_HALF * 16u, LDS_LAT0 = 768u, LDS_RING = 1024u, LDS_RES = LDS_RING + RING_BYTES;
 // [768, 896): ibr_compress of an all-zero pooled latent (its bias through the same MFMA chain), [lane half][16 registers]: what every sample of an
 // all-invalid group gets from that layer -- computed once per block, read by the short path instead of 27 MFMAs per group
-template <bool HOIST> constexpr unsigned DYN_LDS_BYTES = LDS_RES + RES_DW<HOIST> * 4u;
+template <int LEVEL> constexpr unsigned LDS_BIAS = LDS_RES + RES_DW<LEVEL> * 4u;
+template <int LEVEL> constexpr unsigned DYN_LDS_BYTES = LDS_BIAS<LEVEL> + (LEVEL == 2 ? BIAS_TABLE_FLOATS * 4u : 0u);
 // The streamed part of the fragment stream (layers 0 .. LDS_FIRST-1) as 1 KB pieces (one (k-step, output block, hi | lo) fragment each = one
 // LDS-DMA wave instruction), in the order the layers consume them; a PHASE is 16 consecutive pieces.
-template <bool HOIST> constexpr unsigned RING_PIECES = RES_BASE_DW<HOIST> / 256u;
+template <int LEVEL> constexpr unsigned RING_PIECES = RES_BASE_DW<LEVEL> / 256u;
 // RING_PHASES is even (phase P lives in half P % 2, and phase 0 of the next round must not land on the half the last phase is read from).  When the
 // stream has an odd number of phases (the hoisted stream: 31) nobody reads the last, padding phase, so no read begins it: the kernel begins it by
 // hand behind the last streamed layer (ring_close), which is what issues phase 0 of the next round.
-template <bool HOIST> constexpr unsigned RING_STREAM_PHASES = (RING_PIECES<HOIST> + RING_PHASE_PIECES - 1u) / RING_PHASE_PIECES;
-template <bool HOIST> constexpr unsigned RING_PHASES = (RING_STREAM_PHASES<HOIST> + 1u) / 2u * 2u;
+template <int LEVEL> constexpr unsigned RING_STREAM_PHASES = (RING_PIECES<LEVEL> + RING_PHASE_PIECES - 1u) / RING_PHASE_PIECES;
+template <int LEVEL> constexpr unsigned RING_PHASES = (RING_STREAM_PHASES<LEVEL> + 1u) / 2u * 2u;
 static_assert(WPB<1> == 8, "the ring's DMA schedule deals 2 pieces of a phase to each of 8 waves");
-static_assert(RING_PHASES<false> * RING_PHASE_PIECES * 256u <= layer_offset_b(NUM_LAYERS), "the last phase's DMA must stay inside the stream");
-static_assert(RING_PHASES<true> * RING_PHASE_PIECES * 256u <= layer_offset_b(NUM_LAYERS, true), "the last phase's DMA must stay inside the hoisted stream");
+static_assert(RING_PHASES<0> * RING_PHASE_PIECES * 256u <= layer_offset_b(NUM_LAYERS), "the last phase's DMA must stay inside the stream");
+static_assert(RING_PHASES<1> * RING_PHASE_PIECES * 256u <= layer_offset_b(NUM_LAYERS, 1), "the last phase's DMA must stay inside the hoisted stream");
+static_assert(RING_PHASES<2> * RING_PHASE_PIECES * 256u <= layer_offset_b(NUM_LAYERS, 2), "the last phase's DMA must stay inside the lean stream");
+static_assert(RING_STREAM_PHASES<1> == 31u && RING_STREAM_PHASES<2> == 27u, "the streamed parts: 486 KB hoisted, 426 KB lean");
 static_assert(LDS_CTRL + 8u + 2u * 4u * WPB<1> <= LDS_LAT0 && LDS_LAT0 + 128u <= LDS_RING, "control words / constant latent overlap their neighbours");
-static_assert(DYN_LDS_BYTES<false> <= 160u * 1024u && DYN_LDS_BYTES<true> <= DYN_LDS_BYTES<false>, "key points + control words + ring + resident fragments must fit the CU's 160 KB");
+static_assert(DYN_LDS_BYTES<0> <= 160u * 1024u && DYN_LDS_BYTES<1> <= DYN_LDS_BYTES<0> && DYN_LDS_BYTES<2> <= 160u * 1024u,
+              "key points + control words + ring + resident fragments (+ bias table) must fit the CU's 160 KB");
+static_assert(LDS_BIAS<2> % 16u == 0, "the bias table is read 16 bytes at a time");
 extern __shared__ __attribute__((aligned(16))) u32x4 s_dyn[];
 typedef __attribute__((address_space(3))) u32x4 lds_u32x4_t;
 typedef __attribute__((address_space(3))) unsigned lds_u32_t;
@@ -176,23 +187,23 @@ template <unsigned P> __device__ __forceinline__ void ring_dma(WRsrc rs, const L
                  : "s"(la.dma_lds), "s"(la.dma_src), "i"(lds_off), "i"(src_off), "v"(la.w[0]), "s"(rs)
                  : "memory");
 }
-template <bool HOIST, unsigned P> __device__ __forceinline__ void phase_begin(WRsrc rs, const LAddr& la)
+template <int LEVEL, unsigned P> __device__ __forceinline__ void phase_begin(WRsrc rs, const LAddr& la)
 {
-    constexpr unsigned RING_PHASES = ::RING_PHASES<HOIST>;
+    constexpr unsigned RING_PHASES = ::RING_PHASES<LEVEL>;
     if constexpr (P > 0) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
     ring_dma<(P + 1u) % RING_PHASES>(rs, la);
 }
 
 // behind the last streamed layer of a full round: begins the padding phase of a stream with an odd number of phases (see RING_PHASES)
-template <bool HOIST> __device__ __forceinline__ void ring_close(WRsrc rs, const LAddr& la)
+template <int LEVEL> __device__ __forceinline__ void ring_close(WRsrc rs, const LAddr& la)
 {
-    if constexpr (RING_STREAM_PHASES<HOIST> % 2u == 1u) phase_begin<HOIST, RING_PHASES<HOIST> - 1u>(rs, la);
+    if constexpr (RING_STREAM_PHASES<LEVEL> % 2u == 1u) phase_begin<LEVEL, RING_PHASES<LEVEL> - 1u>(rs, la);
 }
 
 // DW: dword offset of the block's hi part in the stream (the lo part follows 1 KB later); the lane's 16 bytes sit at lane * 16
-template <bool HOIST, bool RES, unsigned DW> __device__ __forceinline__ FragB wload_blk(WRsrc rs, const LAddr& la)
+template <int LEVEL, bool RES, unsigned DW> __device__ __forceinline__ FragB wload_blk(WRsrc rs, const LAddr& la)
 {
-    constexpr unsigned RING_PHASES = ::RING_PHASES<HOIST>, RES_BASE_DW = ::RES_BASE_DW<HOIST>;
+    constexpr unsigned RING_PHASES = ::RING_PHASES<LEVEL>, RES_BASE_DW = ::RES_BASE_DW<LEVEL>;
     static_assert(RES == (DW >= RES_BASE_DW), "a layer's fragments are either resident or streamed through the ring: nothing is fetched per wave");
     FragB r;
     if constexpr (RES) { // resident layer
@@ -201,7 +212,7 @@ template <bool HOIST, bool RES, unsigned DW> __device__ __forceinline__ FragB wl
     } else { // streamed layer, through the ring
         constexpr unsigned q = DW / 256u; // piece index of the hi part
         static_assert(q % 2u == 0 && q + 1u < RING_PHASES * RING_PHASE_PIECES, "block fragments are two consecutive pieces inside the streamed part");
-        if constexpr (q % RING_PHASE_PIECES == 0) phase_begin<HOIST, q / RING_PHASE_PIECES>(rs, la);
+        if constexpr (q % RING_PHASE_PIECES == 0) phase_begin<LEVEL, q / RING_PHASE_PIECES>(rs, la);
         r.hi = lds_frag<LDS_RING + (q % (2u * RING_PHASE_PIECES)) * 1024u>(la);
         r.lo = lds_frag<LDS_RING + ((q + 1u) % (2u * RING_PHASE_PIECES)) * 1024u>(la);
     }
@@ -209,13 +220,13 @@ template <bool HOIST, bool RES, unsigned DW> __device__ __forceinline__ FragB wl
 }
 
 // Block fragment i of a layer = (k-step i / NB, output block i % NB) lies i * 512 dwords into the layer's stream.
-template <bool HOIST, int NB, int T, bool RES, unsigned SBASE_DW> __device__ __forceinline__ RingB<NB> ring_start_b(WRsrc rs, const LAddr& la)
+template <int LEVEL, int NB, int T, bool RES, unsigned SBASE_DW> __device__ __forceinline__ RingB<NB> ring_start_b(WRsrc rs, const LAddr& la)
 {
     constexpr int D = RingDepthB<NB>::value, S = (T + 7) / 8;
     RingB<NB> r;
     static_for<D>([&](auto ic) {
         constexpr int i = decltype(ic)::value;
-        if constexpr (i < S * NB) r.b[i] = wload_blk<HOIST, RES, SBASE_DW + i * 512u>(rs, la);
+        if constexpr (i < S * NB) r.b[i] = wload_blk<LEVEL, RES, SBASE_DW + i * 512u>(rs, la);
     });
     __builtin_amdgcn_sched_barrier(0x000F); // keep the ring fill where it is written: ahead of the previous layer's epilogue
     return r;
@@ -239,7 +250,7 @@ struct NoPre { template <class C> __device__ __forceinline__ void operator()(C) 
 // So: step s's MFMAs are cut into four chunks, after each chunk comes one pair-split of step s+1's operands (5 VALU), the re-load of
 // the consumed ring slot is issued before the first chunk, and a sched_barrier(0) after every chunk keeps that order.
 // (sched_group_barrier could request the same interleave, but its solver did not finish on this 10 k-instruction block in 15 min.)
-template <bool HOIST, int NB, int T, bool RES, unsigned SBASE_DW, class Op, class Pre = NoPre>
+template <int LEVEL, int NB, int T, bool RES, unsigned SBASE_DW, class Op, class Pre = NoPre>
 __device__ __forceinline__ void run_layer_b(f32x16 (&acc)[NB], RingB<NB>& ring, WRsrc rs, const LAddr& la, Op&& operand,
                                             Pre&& pre = Pre{})
 {
@@ -277,7 +288,7 @@ __device__ __forceinline__ void run_layer_b(f32x16 (&acc)[NB], RingB<NB>& ring, 
                 if constexpr (m * NCH / (3 * NB) == c) {
                     if constexpr (pr == 0) {
                         a[ob] = ring.b[idx % D];
-                        if constexpr (idx + D < S * NB) ring.b[idx % D] = wload_blk<HOIST, RES, SBASE_DW + (idx + D) * 512u>(rs, la);
+                        if constexpr (idx + D < S * NB) ring.b[idx % D] = wload_blk<LEVEL, RES, SBASE_DW + (idx + D) * 512u>(rs, la);
                     }
                     const bf16x8 wh = __builtin_bit_cast(bf16x8, a[ob].hi), wl = __builtin_bit_cast(bf16x8, a[ob].lo);
                     acc[ob] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pr == 2 ? wl : wh, pr == 1 ? xl : xh, acc[ob], 0, 0, 0);
@@ -321,13 +332,13 @@ template <int K> __device__ __forceinline__ void spill_aux(const LLane& la, floa
 template <int MODE> struct LaneSel { using type = LLane; };
 template <> struct LaneSel<1> { using type = LAddr; };
 __device__ __forceinline__ unsigned lane_of(const LLane& la) { return (unsigned)la.lane; }
-template <int MODE, bool HOIST, int NB, int T, int L> __device__ __forceinline__ typename RingSel<MODE, NB>::type ring_start_m(WRsrc rs, const typename LaneSel<MODE>::type& la)
+template <int MODE, int LEVEL, int NB, int T, int L> __device__ __forceinline__ typename RingSel<MODE, NB>::type ring_start_m(WRsrc rs, const typename LaneSel<MODE>::type& la)
 {
     if constexpr (MODE == 0) return ring_start<NB, T>(rs, layer_offset(L), lane_of(la) * NB * 4u);
-    else return ring_start_b<HOIST, NB, T, (L >= LDS_FIRST), layer_offset_b(L, HOIST)>(rs, la);
+    else return ring_start_b<LEVEL, NB, T, (L >= LDS_FIRST<LEVEL>), layer_offset_b(L, LEVEL)>(rs, la);
 }
 
-template <int MODE, bool HOIST, int NB, int T, int L, class Op>
+template <int MODE, int LEVEL, int NB, int T, int L, class Op>
 __device__ __forceinline__ void run_layer_m(f32x16 (&acc)[NB], typename RingSel<MODE, NB>::type& ring, WRsrc rs, const typename LaneSel<MODE>::type& la, Op&& operand)
 {
     if constexpr (MODE == 0)
@@ -336,7 +347,10 @@ __device__ __forceinline__ void run_layer_m(f32x16 (&acc)[NB], typename RingSel<
             spill_x<L, decltype(tc)::value>(la, b); // (spill mode only)
             return b;
         });
-    else run_layer_b<HOIST, NB, T, (L >= LDS_FIRST), layer_offset_b(L, HOIST)>(acc, ring, rs, la, static_cast<Op&&>(operand));
+    else {
+        static_assert(MODE == 0 || T == kT_b(L, LEVEL), "the kernel and the packed stream agree on the layer's k-pairs");
+        run_layer_b<LEVEL, NB, T, (L >= LDS_FIRST<LEVEL>), layer_offset_b(L, LEVEL)>(acc, ring, rs, la, static_cast<Op&&>(operand));
+    }
 }
 
 // lane id from v_mbcnt, not from a register that would have to stay live (or be spilled) across the whole sample loop
@@ -487,7 +501,8 @@ __device__ __forceinline__ Projected project_and_mask(const VanerfFrame& F, floa
 // one GeoVisFusion scale (src/networks.py:83-94 / 96-104): gates, gated 2-layer MLP.
 //   HC = channels per lane half (32 for the 64-channel map, 4 for the 8-channel map), NBO = output blocks,
 //   NREG_MID = registers of the last hidden block that carry real channels
-template <int MODE, bool HOIST, int HC, int NBO, int NREG_MID, int l_at_a>
+// Lean kernel: the scale ends at `mid` (before its ReLU) -- the last layer is folded into the consumer's weights, which reads relu(mid).
+template <int MODE, int LEVEL, int HC, int NBO, int NREG_MID, int l_at_a>
 __device__ __forceinline__ void geo_scale(WRsrc W, int lane, const typename LaneSel<MODE>::type& la, typename RingSel<MODE, 1>::type& ring_at,
                                           float (&pix)[HC], float (&nn)[HC], float (&tw)[HC], float s0, float s1,
                                           f32x16 (&outacc)[NBO])
@@ -504,13 +519,13 @@ __device__ __forceinline__ void geo_scale(WRsrc W, int lane, const typename Lane
     };
     f32x16 at[1];
     zero<1>(at);
-    run_layer_m<MODE, HOIST, 1, TIN, l_at_a>(at, ring_at, W, la, input);
-    auto r_gate = ring_start_m<MODE, HOIST, 1, 6, l_at_a + 1>(W, la);
-    auto r_mid = ring_start_m<MODE, HOIST, NBO, TIN, l_at_a + 2>(W, la);
+    run_layer_m<MODE, LEVEL, 1, TIN, l_at_a>(at, ring_at, W, la, input);
+    auto r_gate = ring_start_m<MODE, LEVEL, 1, 6, l_at_a + 1>(W, la);
+    auto r_mid = ring_start_m<MODE, LEVEL, NBO, TIN, l_at_a + 2>(W, la);
     if constexpr (MODE == 0) relu<1>(at);
     f32x16 gate[1];
     zero<1>(gate);
-    run_layer_m<MODE, HOIST, 1, 6, l_at_a + 1>(gate, r_gate, W, la, [&](auto tc) -> float { return lazy_act<MODE, ACT_RELU>(at[0][decltype(tc)::value]); });
+    run_layer_m<MODE, LEVEL, 1, 6, l_at_a + 1>(gate, r_gate, W, la, [&](auto tc) -> float { return lazy_act<MODE, ACT_RELU>(at[0][decltype(tc)::value]); });
     // gates live in rows 0..2 = registers 0..2 of the h = 0 lanes
     const float a0 = __shfl(sigmoid_f(gate[0][0]), lane & 31);
     const float a1 = __shfl(sigmoid_f(gate[0][1]), lane & 31);
@@ -518,20 +533,26 @@ __device__ __forceinline__ void geo_scale(WRsrc W, int lane, const typename Lane
     if constexpr (MODE == 0) { constexpr int A = HC == 32 ? AUX_G0 : AUX_G1; spill_aux<A>(la, a0); spill_aux<A + 1>(la, a1); spill_aux<A + 2>(la, a2); }
 #pragma unroll
     for (int t = 0; t < HC; ++t) { pix[t] *= a0; nn[t] *= a1; tw[t] *= a2; }
-    f32x16 mid[NBO];
-    zero<NBO>(mid);
-    run_layer_m<MODE, HOIST, NBO, TIN, l_at_a + 2>(mid, r_mid, W, la, input);
-    auto r_out = ring_start_m<MODE, HOIST, NBO, TOUT, l_at_a + 3>(W, la);
-    if constexpr (MODE == 0) relu<NBO>(mid);
-    zero<NBO>(outacc);
-    run_layer_m<MODE, HOIST, NBO, TOUT, l_at_a + 3>(outacc, r_out, W, la,
-                         [&](auto tc) -> float { constexpr int t = decltype(tc)::value; return lazy_act<MODE, ACT_RELU>(mid[t / 16][t % 16]); });
+    if constexpr (LEVEL == 2) {
+        zero<NBO>(outacc);
+        run_layer_m<MODE, LEVEL, NBO, TIN, l_at_a + 2>(outacc, r_mid, W, la, input);
+    } else {
+        f32x16 mid[NBO];
+        zero<NBO>(mid);
+        run_layer_m<MODE, LEVEL, NBO, TIN, l_at_a + 2>(mid, r_mid, W, la, input);
+        auto r_out = ring_start_m<MODE, LEVEL, NBO, TOUT, l_at_a + 3>(W, la);
+        if constexpr (MODE == 0) relu<NBO>(mid);
+        zero<NBO>(outacc);
+        run_layer_m<MODE, LEVEL, NBO, TOUT, l_at_a + 3>(outacc, r_out, W, la,
+                             [&](auto tc) -> float { constexpr int t = decltype(tc)::value; return lazy_act<MODE, ACT_RELU>(mid[t / 16][t % 16]); });
+    }
 }
 
 // Scale 0 of GeoVisFusion in the hoisted kernel.  The two vertex rows' share of both first layers comes from the table of per-vertex
 // products: `at` starts from A0[i] (registers 0..7, the rest of the block is rows >= 10), `mid` from a1 N0[i] + a2 T0[i] -- the gates scale the
 // products instead of the rows, W (a x) = a (W x) -- and the MFMAs run the 34 per-sample k-pairs [pix32 | (sdf, qvis) | (vis_nn, vis_tw)] only.
-template <int MODE>
+// Lean kernel: ends at `mid`, as geo_scale.
+template <int MODE, int LEVEL>
 __device__ __forceinline__ void geo_scale0_vp(WRsrc W, int lane, const typename LaneSel<MODE>::type& la, typename RingSel<MODE, 1>::type& ring_at,
                                               float (&pix)[32], const float (&a0s)[8], const float (&n0)[32], const float (&t0)[32], float s0, float s1,
                                               f32x16 (&outacc)[2])
@@ -547,23 +568,29 @@ __device__ __forceinline__ void geo_scale0_vp(WRsrc W, int lane, const typename 
     zero<1>(at);
 #pragma unroll
     for (int r = 0; r < 8; ++r) at[0][r] = a0s[r];
-    run_layer_m<MODE, true, 1, TIN, L_GEO_AT0_A>(at, ring_at, W, la, input);
-    auto r_gate = ring_start_m<MODE, true, 1, 6, L_GEO_AT0_B>(W, la);
-    auto r_mid = ring_start_m<MODE, true, 2, TIN, L_GEO_ATED0_A>(W, la);
+    run_layer_m<MODE, LEVEL, 1, TIN, L_GEO_AT0_A>(at, ring_at, W, la, input);
+    auto r_gate = ring_start_m<MODE, LEVEL, 1, 6, L_GEO_AT0_B>(W, la);
+    auto r_mid = ring_start_m<MODE, LEVEL, 2, TIN, L_GEO_ATED0_A>(W, la);
     f32x16 gate[1];
     zero<1>(gate);
-    run_layer_m<MODE, true, 1, 6, L_GEO_AT0_B>(gate, r_gate, W, la, [&](auto tc) -> float { return lazy_act<MODE, ACT_RELU>(at[0][decltype(tc)::value]); });
+    run_layer_m<MODE, LEVEL, 1, 6, L_GEO_AT0_B>(gate, r_gate, W, la, [&](auto tc) -> float { return lazy_act<MODE, ACT_RELU>(at[0][decltype(tc)::value]); });
     const float a0 = __shfl(sigmoid_f(gate[0][0]), lane & 31);
     const float a1 = __shfl(sigmoid_f(gate[0][1]), lane & 31);
     const float a2 = __shfl(sigmoid_f(gate[0][2]), lane & 31);
-    f32x16 mid[2];
+    if constexpr (LEVEL == 2) {
 #pragma unroll
-    for (int t = 0; t < 32; ++t) { pix[t] *= a0; mid[t / 16][t % 16] = fmaf(a2, t0[t], a1 * n0[t]); }
-    run_layer_m<MODE, true, 2, TIN, L_GEO_ATED0_A>(mid, r_mid, W, la, input);
-    auto r_out = ring_start_m<MODE, true, 2, 32, L_GEO_ATED0_B>(W, la);
-    zero<2>(outacc);
-    run_layer_m<MODE, true, 2, 32, L_GEO_ATED0_B>(outacc, r_out, W, la,
-                         [&](auto tc) -> float { constexpr int t = decltype(tc)::value; return lazy_act<MODE, ACT_RELU>(mid[t / 16][t % 16]); });
+        for (int t = 0; t < 32; ++t) { pix[t] *= a0; outacc[t / 16][t % 16] = fmaf(a2, t0[t], a1 * n0[t]); }
+        run_layer_m<MODE, LEVEL, 2, TIN, L_GEO_ATED0_A>(outacc, r_mid, W, la, input);
+    } else {
+        f32x16 mid[2];
+#pragma unroll
+        for (int t = 0; t < 32; ++t) { pix[t] *= a0; mid[t / 16][t % 16] = fmaf(a2, t0[t], a1 * n0[t]); }
+        run_layer_m<MODE, LEVEL, 2, TIN, L_GEO_ATED0_A>(mid, r_mid, W, la, input);
+        auto r_out = ring_start_m<MODE, LEVEL, 2, 32, L_GEO_ATED0_B>(W, la);
+        zero<2>(outacc);
+        run_layer_m<MODE, LEVEL, 2, 32, L_GEO_ATED0_B>(outacc, r_out, W, la,
+                             [&](auto tc) -> float { constexpr int t = decltype(tc)::value; return lazy_act<MODE, ACT_RELU>(mid[t / 16][t % 16]); });
+    }
 }
 
 // NB accumulator blocks straight from a table row in D-register order: 4 NB loads of 16 bytes
@@ -578,13 +605,34 @@ template <int NB> __device__ __forceinline__ void load_acc(const float* __restri
         }
 }
 
-template <int MODE, bool SPILL = false, bool HOIST = false>
+// Lean kernel: the accumulators of layer L start from its rows of the bias table in LDS ([lane half][block][register], layer_spec.h): 4 NB
+// ds_read_b128.  The address is formed here, opaque, so that it is neither hoisted out of the sample loop nor kept across layers.
+template <int L, int NB> __device__ __forceinline__ void load_bias(int h, f32x16 (&acc)[NB])
+{
+    static_assert(bias_table_floats(L) == 2u * NB * 16u, "the layer has a row in the bias table");
+    unsigned a = (unsigned)h * (NB * 64u) + (LDS_BIAS<2> + bias_table_offset(L) * 4u);
+    asm volatile("" : "+v"(a));
+#pragma unroll
+    for (int ob = 0; ob < NB; ++ob)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const u32x4 v = *reinterpret_cast<const lds_u32x4_t*>((size_t)(a + 64u * ob + 16u * i));
+            acc[ob][4 * i] = __uint_as_float(v.x); acc[ob][4 * i + 1] = __uint_as_float(v.y);
+            acc[ob][4 * i + 2] = __uint_as_float(v.z); acc[ob][4 * i + 3] = __uint_as_float(v.w);
+        }
+}
+
+template <int MODE, bool SPILL = false, int LEVEL = 0>
 __global__ __launch_bounds__(64 * WPB<MODE>, SPILL ? WAVES_PER_SIMD_SPILL : WAVES_PER_SIMD) void query_kernel(const QueryParams P)
 {
     static_assert(!SPILL || MODE == 0, "the training spill runs on the fp32 kernel");
-    static_assert(!HOIST || MODE == 1, "only the split-bf16 kernel has a hoisted variant");
-    [[maybe_unused]] constexpr unsigned RES_BASE_DW = ::RES_BASE_DW<HOIST>, RES_DW = ::RES_DW<HOIST>;
-    constexpr int T_GEO0 = kT_b(L_GEO_AT0_A, HOIST), T_TEX_AT = kT_b(L_TEX_AT_A, HOIST);
+    static_assert(LEVEL >= 0 && LEVEL <= 2 && (LEVEL == 0 || MODE == 1), "only the split-bf16 kernel has a hoisted and a lean variant");
+    constexpr bool HOIST = LEVEL >= 1, LEAN = LEVEL == 2;
+    [[maybe_unused]] constexpr unsigned RES_BASE_DW = ::RES_BASE_DW<LEVEL>, RES_DW = ::RES_DW<LEVEL>;
+    constexpr int LDS_FIRST = ::LDS_FIRST<LEVEL>;
+    constexpr int T_GEO0 = kT_b(L_GEO_AT0_A, LEVEL), T_TEX_AT = kT_b(L_TEX_AT_A, LEVEL), T_TEX = kT_b(L_TEX_A, LEVEL);
+    // (lean: no bias k-pair, the accumulator starts from the bias table)
+    constexpr int T_MLP1 = kT_b(L_MLP1, LEVEL), T_HEAD0 = kT_b(L_HEAD0, LEVEL), T_HEAD1 = kT_b(L_HEAD1, LEVEL), T_HEAD2 = kT_b(L_HEAD2, LEVEL), T_IBR = kT_b(L_IBR, LEVEL);
     constexpr int WAVES_PER_BLOCK = WPB<MODE>, BLOCK = 64 * WAVES_PER_BLOCK;
 
     const int lane_k = threadIdx.x & 63;
@@ -638,20 +686,25 @@ __global__ __launch_bounds__(64 * WPB<MODE>, SPILL ? WAVES_PER_SIMD_SPILL : WAVE
     if constexpr (MODE == 1) { // resident fragments: one copy per block (the launch is persistent: 256 blocks x 126 KB from L2, once)
         const u32x4* __restrict__ src = reinterpret_cast<const u32x4*>(P.w) + RES_BASE_DW / 4;
         for (unsigned i = threadIdx.x; i < RES_DW / 4; i += BLOCK) s_dyn[LDS_RES / 16 + i] = src[i];
+        if constexpr (LEAN) { // the bias table stands behind the stream's slack (layer_spec.h); here it goes right behind the resident fragments
+            const u32x4* __restrict__ bsrc = reinterpret_cast<const u32x4*>(P.w) + (layer_offset_b(NUM_LAYERS, LEVEL) + STREAM_SLACK_DW) / 4;
+            if (threadIdx.x < BIAS_TABLE_FLOATS / 4) s_dyn[LDS_BIAS<LEVEL> / 16 + threadIdx.x] = bsrc[threadIdx.x];
+        }
         // phase 0 of the ring, once: every full round re-issues it for its successor (see phase_begin)
         const LAddr la0 = make_laddr(lane, wv_u);
         ring_dma<0>(W, la0);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
     __syncthreads();
-    if constexpr (MODE == 1) { // the short path's constant latent (wave 0; the layer's fragments are resident by now)
+    if constexpr (MODE == 1) { // the short path's constant latent (wave 0; the layer's fragments -- and the bias table -- are resident by now)
         if (wv_u == 0u) {
             const LAddr la0 = make_laddr(lane, wv_u);
-            auto r0 = ring_start_m<MODE, HOIST, 1, 65, L_IBR>(W, la0);
+            auto r0 = ring_start_m<MODE, LEVEL, 1, T_IBR, L_IBR>(W, la0);
             f32x16 lat0[1];
-            zero<1>(lat0);
+            if constexpr (LEAN) load_bias<L_IBR, 1>(lane >> 5, lat0);
+            else zero<1>(lat0);
             const float one0 = (lane >> 5) ? 0.0f : 1.0f;
-            run_layer_m<MODE, HOIST, 1, 65, L_IBR>(lat0, r0, W, la0, [&](auto tc) -> float { return decltype(tc)::value < 64 ? 0.0f : one0; });
+            run_layer_m<MODE, LEVEL, 1, T_IBR, L_IBR>(lat0, r0, W, la0, [&](auto tc) -> float { return decltype(tc)::value < 64 ? 0.0f : one0; });
             if ((lane & 31) == 0)
                 static_for<16>([&](auto rc) { constexpr int r = decltype(rc)::value; reinterpret_cast<lds_u32_t*>((size_t)LDS_LAT0)[(lane >> 5) * 16 + r] = __float_as_uint(lat0[0][r]); });
         }
@@ -761,8 +814,8 @@ __global__ __launch_bounds__(64 * WPB<MODE>, SPILL ? WAVES_PER_SIMD_SPILL : WAVE
         // ibr_compress) survives.  When ALL 32 samples of the wave are such samples, GeoVisFusion, mlp_geo.layers1 and the head
         // (82 % of the MFMAs) are skipped -- same bits, wave-uniform branch.  With real foreground masks most samples are.
         if (any_valid) {
-            auto r_at0 = ring_start_m<MODE, HOIST, 1, T_GEO0, L_GEO_AT0_A>(W, la);
-            f32x16 g64[2], g8[1];
+            auto r_at0 = ring_start_m<MODE, LEVEL, 1, T_GEO0, L_GEO_AT0_A>(W, la);
+            f32x16 g64[2], g8[1]; // the outputs of the two GeoVisFusion scales (lean kernel: their hidden layers `mid` before the ReLU)
             float pix8[4], nn8[4], tw8[4];
             {
                 float pix[32], nn[32], tw[32];
@@ -785,8 +838,8 @@ __global__ __launch_bounds__(64 * WPB<MODE>, SPILL ? WAVES_PER_SIMD_SPILL : WAVE
                 };
                 if constexpr (MODE == 0) geo1_gathers();
                 STAMP(2); // geo gathers
-                if constexpr (HOIST) geo_scale0_vp<MODE>(W, lane, la, r_at0, pix, a0s, nn, tw, sc0, sc1, g64);
-                else geo_scale<MODE, HOIST, 32, 2, 16, L_GEO_AT0_A>(W, lane, la, r_at0, pix, nn, tw, sc0, sc1, g64);
+                if constexpr (HOIST) geo_scale0_vp<MODE, LEVEL>(W, lane, la, r_at0, pix, a0s, nn, tw, sc0, sc1, g64);
+                else geo_scale<MODE, LEVEL, 32, 2, 16, L_GEO_AT0_A>(W, lane, la, r_at0, pix, nn, tw, sc0, sc1, g64);
                 if constexpr (MODE == 1) geo1_gathers();
                 STAMP(3); // geo0 layers
             }
@@ -796,12 +849,12 @@ __global__ __launch_bounds__(64 * WPB<MODE>, SPILL ? WAVES_PER_SIMD_SPILL : WAVE
             WFrag<4> ring0[D0];
             RingB<4> ring0b;
             {
-                auto r_at1 = ring_start_m<MODE, HOIST, 1, 14, L_GEO_AT1_A>(W, la);
+                auto r_at1 = ring_start_m<MODE, LEVEL, 1, 14, L_GEO_AT1_A>(W, la);
                 if constexpr (MODE == 0) {
                     static_for<D0>([&](auto fc) { constexpr int f = decltype(fc)::value; ring0[f] = wload<4>(W, (base0 + f * 256) * 4u, v4); });
                 }
-                geo_scale<MODE, HOIST, 4, 1, 4, L_GEO_AT1_A>(W, lane, la, r_at1, pix8, nn8, tw8, sc0, sc1, g8);
-                if constexpr (MODE == 1) ring0b = ring_start_b<HOIST, 4, 180, false, layer_offset_b(L_MLP0, HOIST)>(W, la);
+                geo_scale<MODE, LEVEL, 4, 1, 4, L_GEO_AT1_A>(W, lane, la, r_at1, pix8, nn8, tw8, sc0, sc1, g8);
+                if constexpr (MODE == 1) ring0b = ring_start_b<LEVEL, 4, 180, false, layer_offset_b(L_MLP0, LEVEL)>(W, la);
                 STAMP(4); // geo1
             }
 
@@ -873,10 +926,12 @@ __global__ __launch_bounds__(64 * WPB<MODE>, SPILL ? WAVES_PER_SIMD_SPILL : WAVE
                         // 179 the bias.  A bf16 step takes 8 consecutive pairs, so key point i is computed right before the first step
                         // that needs it (at most two key points are live at a time).
                         float feat[PE_KPT_PER_HALF][PE_FEATS];
-                        run_layer_b<HOIST, 4, 180, false, layer_offset_b(L_MLP0, HOIST)>(a0, ring0b, W, la,
+                        // (lean: the geo pairs hold the folded matrix and read the scale's hidden layer through its ReLU)
+                        run_layer_b<LEVEL, 4, 180, false, layer_offset_b(L_MLP0, LEVEL)>(a0, ring0b, W, la,
                             [&](auto tc) -> float {
                                 constexpr int t = decltype(tc)::value;
                                 if constexpr (t < 147) return feat[t / 7][t % 7];
+                                else if constexpr (LEAN && t < 179) return lazy_act<MODE, ACT_RELU>(g64[(t - 147) / 16][(t - 147) % 16]);
                                 else return chain(g64, std::integral_constant<int, t - 147>{}, std::integral_constant<int, 32>{});
                             },
                             [&](auto sc) {
@@ -890,29 +945,30 @@ __global__ __launch_bounds__(64 * WPB<MODE>, SPILL ? WAVES_PER_SIMD_SPILL : WAVE
                     }
                 }
                 STAMP(5); // mlp0 (PE + geo64)
-                auto r1 = ring_start_m<MODE, HOIST, 4, 65, L_MLP1>(W, la);
+                auto r1 = ring_start_m<MODE, LEVEL, 4, T_MLP1, L_MLP1>(W, la);
                 if constexpr (MODE == 0) softplus<4>(a0);
                 f32x16 a1[4];
-                zero<4>(a1);
-                run_layer_m<MODE, HOIST, 4, 65, L_MLP1>(a1, r1, W, la, [&](auto tc) -> float { return chain_sp(a0, tc, std::integral_constant<int, 64>{}); });
-                auto r2 = ring_start_m<MODE, HOIST, 4, 69, L_MLP2>(W, la);
+                if constexpr (LEAN) load_bias<L_MLP1, 4>(h, a1);
+                else zero<4>(a1);
+                run_layer_m<MODE, LEVEL, 4, T_MLP1, L_MLP1>(a1, r1, W, la, [&](auto tc) -> float { return chain_sp(a0, tc, std::integral_constant<int, 64>{}); });
+                auto r2 = ring_start_m<MODE, LEVEL, 4, 69, L_MLP2>(W, la);
                 if constexpr (MODE == 0) softplus<4>(a1);
                 zero<4>(a0);
-                run_layer_m<MODE, HOIST, 4, 69, L_MLP2>(a0, r2, W, la, [&](auto tc) -> float {
+                run_layer_m<MODE, LEVEL, 4, 69, L_MLP2>(a0, r2, W, la, [&](auto tc) -> float {
                     constexpr int t = decltype(tc)::value;
                     if constexpr (t < 64) return lazy_act<MODE, ACT_SOFTPLUS>(a1[t / 16][t % 16]);
-                    else if constexpr (t < 68) return g8[0][t - 64];
+                    else if constexpr (t < 68) return LEAN ? lazy_act<MODE, ACT_RELU>(g8[0][t - 64]) : g8[0][t - 64];
                     else return one_h0;
                 });
-                auto r3 = ring_start_m<MODE, HOIST, 2, 61, L_MLP3>(W, la);
+                auto r3 = ring_start_m<MODE, LEVEL, 2, 61, L_MLP3>(W, la);
                 if constexpr (MODE == 0) softplus<4>(a0);
                 zero<2>(xv);
-                run_layer_m<MODE, HOIST, 2, 61, L_MLP3>(xv, r3, W, la, [&](auto tc) -> float { return chain_sp(a0, tc, std::integral_constant<int, 60>{}); });
+                run_layer_m<MODE, LEVEL, 2, 61, L_MLP3>(xv, r3, W, la, [&](auto tc) -> float { return chain_sp(a0, tc, std::integral_constant<int, 60>{}); });
             }
             STAMP(6); // softplus x3 + mlp1..3
             if constexpr (MODE == 0) tex_gathers(); // ~2 layers before the texture branch needs them
             // ---- PoolModule mean/var over V = 1 views (src/utils.py:744-779, 854-880) --------------------------
-            auto rh0 = ring_start_m<MODE, HOIST, 2, 65, L_HEAD0>(W, la);
+            auto rh0 = ring_start_m<MODE, LEVEL, 2, T_HEAD0, L_HEAD0>(W, la);
             if constexpr (MODE == 0)
                 static_for<32>([&](auto rc) { constexpr int r = decltype(rc)::value; spill_aux<AUX_XV + r>(la, xv[r / 16][r % 16]); });
     #pragma unroll
@@ -927,18 +983,22 @@ __global__ __launch_bounds__(64 * WPB<MODE>, SPILL ? WAVES_PER_SIMD_SPILL : WAVE
             // ---- mlp_geo.layers2: 128 -> 64 -> 64 -> 2 (src/utils.py:709-719) ----------------------------------
             {
                 f32x16 m0[2], m1[2];
-                zero<2>(m0);
-                run_layer_m<MODE, HOIST, 2, 65, L_HEAD0>(m0, rh0, W, la, [&](auto tc) -> float { return chain(pool, tc, std::integral_constant<int, 64>{}); });
-                auto rh1 = ring_start_m<MODE, HOIST, 2, 33, L_HEAD1>(W, la);
+                if constexpr (LEAN) load_bias<L_HEAD0, 2>(h, m0);
+                else zero<2>(m0);
+                run_layer_m<MODE, LEVEL, 2, T_HEAD0, L_HEAD0>(m0, rh0, W, la, [&](auto tc) -> float { return chain(pool, tc, std::integral_constant<int, 64>{}); });
+                static_assert(LDS_FIRST == L_HEAD2 + 1 || LDS_FIRST == L_HEAD0 + 1, "the ring is closed behind its last streamed layer");
+                if constexpr (MODE == 1 && LDS_FIRST == L_HEAD0 + 1) ring_close<LEVEL>(W, la);
+                auto rh1 = ring_start_m<MODE, LEVEL, 2, T_HEAD1, L_HEAD1>(W, la);
                 if constexpr (MODE == 0) softplus<2>(m0);
-                zero<2>(m1);
-                run_layer_m<MODE, HOIST, 2, 33, L_HEAD1>(m1, rh1, W, la, [&](auto tc) -> float { return chain_sp(m0, tc, std::integral_constant<int, 32>{}); });
-                auto rh2 = ring_start_m<MODE, HOIST, 1, 33, L_HEAD2>(W, la);
+                if constexpr (LEAN) load_bias<L_HEAD1, 2>(h, m1);
+                else zero<2>(m1);
+                run_layer_m<MODE, LEVEL, 2, T_HEAD1, L_HEAD1>(m1, rh1, W, la, [&](auto tc) -> float { return chain_sp(m0, tc, std::integral_constant<int, 32>{}); });
+                auto rh2 = ring_start_m<MODE, LEVEL, 1, T_HEAD2, L_HEAD2>(W, la);
                 if constexpr (MODE == 0) softplus<2>(m1);
-                zero<1>(head);
-                run_layer_m<MODE, HOIST, 1, 33, L_HEAD2>(head, rh2, W, la, [&](auto tc) -> float { return chain_sp(m1, tc, std::integral_constant<int, 32>{}); });
-                static_assert(LDS_FIRST == L_HEAD2 + 1, "the ring is closed behind its last streamed layer");
-                if constexpr (MODE == 1) ring_close<HOIST>(W, la);
+                if constexpr (LEAN) load_bias<L_HEAD2, 1>(h, head);
+                else zero<1>(head);
+                run_layer_m<MODE, LEVEL, 1, T_HEAD2, L_HEAD2>(head, rh2, W, la, [&](auto tc) -> float { return chain_sp(m1, tc, std::integral_constant<int, 32>{}); });
+                if constexpr (MODE == 1 && LDS_FIRST == L_HEAD2 + 1) ring_close<LEVEL>(W, la);
             }
         } else {
             if constexpr (MODE == 0) tex_gathers();
@@ -953,14 +1013,15 @@ __global__ __launch_bounds__(64 * WPB<MODE>, SPILL ? WAVES_PER_SIMD_SPILL : WAVE
         typename RingSel<MODE, 3>::type r_ta;
         if (MODE == 1 && !any_valid) {
             // all-invalid group: the pooled latent is exactly zero, the layer returns its bias -- the block's constant (same chain, same bits)
-            r_ta = ring_start_m<MODE, HOIST, 3, T_TEX_AT, L_TEX_AT_A>(W, la);
+            r_ta = ring_start_m<MODE, LEVEL, 3, T_TEX_AT, L_TEX_AT_A>(W, la);
             if constexpr (MODE == 1)
                 static_for<16>([&](auto rc) { constexpr int r = decltype(rc)::value; lat[0][r] = __uint_as_float(reinterpret_cast<const lds_u32_t*>((size_t)LDS_LAT0)[h * 16 + r]); });
         } else {
-            auto r_ibr = ring_start_m<MODE, HOIST, 1, 65, L_IBR>(W, la);
-            r_ta = ring_start_m<MODE, HOIST, 3, T_TEX_AT, L_TEX_AT_A>(W, la);
-            zero<1>(lat);
-            run_layer_m<MODE, HOIST, 1, 65, L_IBR>(lat, r_ibr, W, la, [&](auto tc) -> float { return chain(pool, tc, std::integral_constant<int, 64>{}); });
+            auto r_ibr = ring_start_m<MODE, LEVEL, 1, T_IBR, L_IBR>(W, la);
+            r_ta = ring_start_m<MODE, LEVEL, 3, T_TEX_AT, L_TEX_AT_A>(W, la);
+            if constexpr (LEAN) load_bias<L_IBR, 1>(h, lat);
+            else zero<1>(lat);
+            run_layer_m<MODE, LEVEL, 1, T_IBR, L_IBR>(lat, r_ibr, W, la, [&](auto tc) -> float { return chain(pool, tc, std::integral_constant<int, 64>{}); });
         }
         STAMP(8); // ibr
         // ---- TexVisFusion per-sample part (src/networks.py:281-293) -----------------------------------------
@@ -968,9 +1029,9 @@ __global__ __launch_bounds__(64 * WPB<MODE>, SPILL ? WAVES_PER_SIMD_SPILL : WAVE
         {
             float q[6];
             q[0] = h ? qt[3] : qi[0]; q[1] = h ? qt[4] : qi[1]; q[2] = h ? qt[5] : qi[2];
-            q[3] = h ? qt[6] : qt[0]; q[4] = h ? qt[7] : qt[1]; q[5] = h ? 0.0f : qt[2];
+            q[3] = h ? qt[6] : qt[0]; q[4] = h ? qt[7] : qt[1]; q[5] = h ? (LEAN ? vis_tw : 0.0f) : qt[2]; // (lean: k-pair (qt[2] | vis_twin))
             const float t0 = h ? vis_nn : q_vis; // k-pair (qvis | vis_nn)
-            const float t1 = h ? 0.0f : vis_tw;  // k-pair (vis_twin | -)
+            [[maybe_unused]] const float t1 = h ? 0.0f : vis_tw;  // k-pair (vis_twin | -) (not in the lean stream)
             f32x16 latg = lat[0];
             auto tex_in = [&](auto tc) -> float {
                 constexpr int t = decltype(tc)::value;
@@ -978,7 +1039,7 @@ __global__ __launch_bounds__(64 * WPB<MODE>, SPILL ? WAVES_PER_SIMD_SPILL : WAVE
                 else if constexpr (t < 35) return q[t - 29];
                 else if constexpr (t < 47) return latg[t - 35];
                 else if constexpr (t == 47) return t0;
-                else return t1;
+                else { static_assert(!LEAN || t < 48, "the lean stream has no (vis_twin | -) pair"); return t1; }
             };
             auto from_ta = [&](auto& ta_) { return [&](auto tc) -> float { constexpr int t = decltype(tc)::value; return lazy_act<MODE, ACT_RELU>(ta_[t / 16][t % 16]); }; };
             // hoisted kernel: the ungated first layer starts from P[i], the two vertex rows' share of it, and runs [query6 | latent12 | 2 visibility pairs]
@@ -988,18 +1049,18 @@ __global__ __launch_bounds__(64 * WPB<MODE>, SPILL ? WAVES_PER_SIMD_SPILL : WAVE
                 else if constexpr (t < 6) return q[t];
                 else if constexpr (t < 18) return latg[t - 6];
                 else if constexpr (t == 18) return t0;
-                else return t1;
+                else { static_assert(!LEAN || t < 19, "the lean stream has no (vis_twin | -) pair"); return t1; }
             };
             f32x16 ta[3];
             if constexpr (HOIST) load_acc<3>(P.vp + VP_P, (unsigned)(nn_idx * (int)VP_P_ROW + 48 * h), ta);
             else zero<3>(ta);
-            run_layer_m<MODE, HOIST, 3, T_TEX_AT, L_TEX_AT_A>(ta, r_ta, W, la, tex_at_in);
-            auto r_tg = ring_start_m<MODE, HOIST, 1, 48, L_TEX_AT_B>(W, la);
+            run_layer_m<MODE, LEVEL, 3, T_TEX_AT, L_TEX_AT_A>(ta, r_ta, W, la, tex_at_in);
+            auto r_tg = ring_start_m<MODE, LEVEL, 1, 48, L_TEX_AT_B>(W, la);
             if constexpr (MODE == 0) relu<3>(ta);
             f32x16 tg[1];
             zero<1>(tg);
-            run_layer_m<MODE, HOIST, 1, 48, L_TEX_AT_B>(tg, r_tg, W, la, from_ta(ta));
-            auto r_tb = ring_start_m<MODE, HOIST, 3, 49, L_TEX_A>(W, la);
+            run_layer_m<MODE, LEVEL, 1, 48, L_TEX_AT_B>(tg, r_tg, W, la, from_ta(ta));
+            auto r_tb = ring_start_m<MODE, LEVEL, 3, T_TEX, L_TEX_A>(W, la);
             // six gates: rows 0..3 -> h = 0 lanes regs 0..3, rows 4,5 -> h = 1 lanes regs 0,1
             float m0 = sigmoid_f(tg[0][0]), m1 = sigmoid_f(tg[0][1]), m2 = sigmoid_f(tg[0][2]), m3 = sigmoid_f(tg[0][3]);
             float o0 = __shfl_xor(m0, 32), o1 = __shfl_xor(m1, 32), o2 = __shfl_xor(m2, 32);
@@ -1016,15 +1077,16 @@ __global__ __launch_bounds__(64 * WPB<MODE>, SPILL ? WAVES_PER_SIMD_SPILL : WAVE
 #pragma unroll
             for (int t = 11; t < 29; ++t) row[t] *= ggf;
 #pragma unroll
-            for (int t = 0; t < 6; ++t) q[t] *= gq;
+            for (int t = 0; t < (LEAN ? 5 : 6); ++t) q[t] *= gq;
+            if constexpr (LEAN) q[5] = h ? q[5] : q[5] * gq; // the h = 1 half of the merged pair is vis_twin: not gated
 #pragma unroll
             for (int r = 0; r < 12; ++r) latg[r] = lat[0][r] * glat;
             zero<3>(ta);
-            run_layer_m<MODE, HOIST, 3, 49, L_TEX_A>(ta, r_tb, W, la, tex_in);
-            auto r_rgb = ring_start_m<MODE, HOIST, 1, 48, L_TEX_B>(W, la);
+            run_layer_m<MODE, LEVEL, 3, T_TEX, L_TEX_A>(ta, r_tb, W, la, tex_in);
+            auto r_rgb = ring_start_m<MODE, LEVEL, 1, 48, L_TEX_B>(W, la);
             if constexpr (MODE == 0) relu<3>(ta);
             zero<1>(rgb);
-            run_layer_m<MODE, HOIST, 1, 48, L_TEX_B>(rgb, r_rgb, W, la, from_ta(ta));
+            run_layer_m<MODE, LEVEL, 1, 48, L_TEX_B>(rgb, r_rgb, W, la, from_ta(ta));
         }
         STAMP(9); // tex
         // ---- eval_func (src/model.py:1140-1160): rows 0,1 of the head / 0..2 of the colour live in the h = 0 lanes ----
@@ -1082,9 +1144,9 @@ QueryParams query_params(const VanerfFrame& f, const float* stream_w, size_t str
 // cycles to the MFMA time), so the second wave does not hide VALU work behind MFMAs; what it hides is load latency and the in-order issue gaps
 // of its partner --, split-bf16 ONE 8-wave block (it owns the CU's LDS), spill build one 4-wave block (it takes the whole register file).
 struct QueryLaunch { void (*kernel)(QueryParams); int wpb, blocks_per_cu; unsigned lds_bytes; };
-template <int MODE, bool SPILL = false, bool HOIST = false> QueryLaunch query_launch()
+template <int MODE, bool SPILL = false, int LEVEL = 0> QueryLaunch query_launch()
 {
-    return {query_kernel<MODE, SPILL, HOIST>, WPB<MODE>, (SPILL ? WAVES_PER_SIMD_SPILL : WAVES_PER_SIMD) * 4 / WPB<MODE>, MODE == 1 ? DYN_LDS_BYTES<HOIST> : 0u};
+    return {query_kernel<MODE, SPILL, LEVEL>, WPB<MODE>, (SPILL ? WAVES_PER_SIMD_SPILL : WAVES_PER_SIMD) * 4 / WPB<MODE>, MODE == 1 ? DYN_LDS_BYTES<LEVEL> : 0u};
 }
 
 // persistent grid: one block per WPB groups, at most what the device holds at once (the blocks claim their groups from the queue word)
@@ -1107,10 +1169,19 @@ void launch_query(const QueryLaunch& L, long long blocks, QueryParams& P, void* 
     HIP_CHECK(hipGetLastError());
 }
 
+// VANERF_LEAN_STREAM (read at every launch, for tests and A/B runs): 0 = a bf16x3 handle with a table of vertex products runs the hoisted kernel
+// instead of the lean one.  Unset or anything else: the lean kernel.
+bool lean_stream_enabled()
+{
+    const char* e = std::getenv("VANERF_LEAN_STREAM");
+    return !(e && e[0] == '0' && !e[1]);
+}
+
 } // namespace
 
 // vertex_products: the frame's table from vanerf_vertex_products (built with the same handle, after its last update), or NULL.  With the
-// table a bf16x3 handle runs the hoisted kernel on its hoisted stream; without it every handle runs the un-hoisted kernel of its mode.
+// table a bf16x3 handle runs the lean kernel on its lean stream (the hoisted kernel on the hoisted stream under VANERF_LEAN_STREAM=0); without
+// it every handle runs the un-hoisted kernel of its mode.
 extern "C" int vanerf_query_samples(const VanerfWeights* w, const VanerfFrame* frame, const float* pts, const float* query_sdf,
                                     const uint8_t* query_vis, const int32_t* knn_idx, const float* noise, const int32_t* order, int raw, int64_t n,
                                     float* out, uint8_t* valid, void* queue_word, const float* vertex_products, void* stream)
@@ -1128,9 +1199,12 @@ extern "C" int vanerf_query_samples(const VanerfWeights* w, const VanerfFrame* f
         const bool hoist = vertex_products != nullptr;
         if (hoist && (w->mode != 1 || !w->n_floats_h)) throw_error("vanerf_query_samples: a table of vertex products needs a bf16x3 weight handle");
         if (hoist && (reinterpret_cast<uintptr_t>(vertex_products) & 15u)) throw_error("vanerf_query_samples: the table must be 16-byte aligned");
-        QueryParams P = query_params(f, hoist ? w->dev + w->n_floats : w->dev, hoist ? w->n_floats_h : w->n_floats, pts, query_sdf, query_vis, knn_idx, raw, n, out);
+        const bool lean = hoist && w->n_floats_l && lean_stream_enabled();
+        const float* stream_w = lean ? w->dev + w->n_floats + w->n_floats_h : hoist ? w->dev + w->n_floats : w->dev;
+        const size_t stream_floats = lean ? w->n_floats_l + BIAS_TABLE_FLOATS : hoist ? w->n_floats_h : w->n_floats;
+        QueryParams P = query_params(f, stream_w, stream_floats, pts, query_sdf, query_vis, knn_idx, raw, n, out);
         P.noise = noise; P.order = order; P.valid = valid; P.short_groups = w->stats; P.vp = vertex_products;
-        const QueryLaunch L = w->mode == 1 && hoist ? query_launch<1, false, true>() : w->mode == 1 ? query_launch<1>() : query_launch<0>();
+        const QueryLaunch L = lean ? query_launch<1, false, 2>() : w->mode == 1 && hoist ? query_launch<1, false, 1>() : w->mode == 1 ? query_launch<1>() : query_launch<0>();
         launch_query(L, query_blocks(L, n), P, queue_word, stream);
     });
 }

@@ -5,6 +5,8 @@
 // parts).  The placement tables depend on layer_spec.h only, are built once per process and serve both the host packer
 // (vanerf_weights_pack: one hipMemcpy per pack) and the device packer (weights_update.hip: vanerf_weights_update re-packs a handle in place
 // from parameters that live on the device, two launches per stream, no synchronisation -- the training step's path).
+// Stage 1 also forms the two FOLDED matrices of the lean bf16x3 stream (layer_spec.h) behind the layers' own weights in `eff`, so that their
+// placement is a gather like every other.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -66,7 +68,14 @@ constexpr unsigned eff_offset(int l)
 }
 static_assert(eff_offset(NUM_LAYERS) < (1u << 24), "ids must be exact in fp32");
 
-Mat id_matrix(int l)
+constexpr unsigned EFF_FOLD0 = eff_offset(NUM_LAYERS), EFF_FOLD1 = EFF_FOLD0 + FOLD0_ROWS * FOLD0_COLS, EFF_TOTAL = EFF_FOLD0 + FOLD_FLOATS;
+static_assert(EFF_TOTAL < (1u << 24), "ids must be exact in fp32");
+static_assert(FOLD0_ROWS == (unsigned)kShape[L_MLP0].nout && FOLD0_COLS == (unsigned)kShape[L_GEO_ATED0_B].nout && kShape[L_MLP0].kin == 294 + (int)FOLD0_COLS &&
+              FOLD1_ROWS == (unsigned)kShape[L_MLP2].nout && FOLD1_COLS == (unsigned)kShape[L_GEO_ATED1_B].nout && kShape[L_MLP2].kin == 128 + (int)FOLD1_COLS,
+              "the folded matrices replace the geo columns of mlp0 / mlp2");
+
+// level 2 (the lean stream): the geo columns of L_MLP0 / L_MLP2 hold the folded matrices F0 / F1 (their k index is the channel of `mid`)
+Mat id_matrix(int l, int level = 0)
 {
     const Shape sh = kShape[l];
     if (sh.nout != kNOUT[l]) throw_error("internal: layer %d has %d outputs, spec says %d", l, sh.nout, kNOUT[l]);
@@ -76,6 +85,12 @@ Mat id_matrix(int l)
     if (sh.bias) {
         m.b.resize(sh.nout);
         for (int o = 0; o < sh.nout; ++o) m.b[o] = (float)(base + m.w.size() + o);
+    }
+    if (level == 2 && (l == L_MLP0 || l == L_MLP2)) {
+        const int c0 = l == L_MLP0 ? 294 : 128, nc = (int)(l == L_MLP0 ? FOLD0_COLS : FOLD1_COLS);
+        const unsigned fold = (l == L_MLP0 ? EFF_FOLD0 : EFF_FOLD1) + 1u;
+        for (int o = 0; o < sh.nout; ++o)
+            for (int k = 0; k < nc; ++k) m.w[(size_t)o * sh.kin + c0 + k] = (float)(fold + (unsigned)(o * nc + k));
     }
     return m;
 }
@@ -103,12 +118,12 @@ void emit(std::vector<float>& out, int layer, const Mat& m, const Pairs& pairs)
 
 // bf16x3 stream of one layer (layer_spec.h): element j of the 8-element fragment of lane (r, h) at step s is k-pair 8s + j.
 // Placement only: per 32-bit word of the stream two ids (the elements in its low and high half) and which bf16 part of them it holds.
-void emit_b_ids(std::vector<WordB>& out, int layer, const Mat& m, const Pairs& pairs, bool hoist)
+void emit_b_ids(std::vector<WordB>& out, int layer, const Mat& m, const Pairs& pairs, int level)
 {
-    const int nb = kNB[layer], T = kT_b(layer, hoist), S = steps_b(layer, hoist);
+    const int nb = kNB[layer], T = kT_b(layer, level), S = steps_b(layer, level);
     if ((int)pairs.size() != T) throw_error("internal: layer %d has %d k-pairs, spec says %d", layer, (int)pairs.size(), T);
     size_t base = out.size();
-    out.resize(base + layer_dwords_b(layer, hoist), WordB{0, 0, 0});
+    out.resize(base + layer_dwords_b(layer, level), WordB{0, 0, 0});
     WordB* dst = out.data() + base;
     for (int s = 0; s < S; ++s)
         for (int ob = 0; ob < nb; ++ob)
@@ -143,18 +158,19 @@ Pairs geo_input_pairs(int c, bool hoist = false)
 }
 
 // TexVisFusion input (src/networks.py:284-286): [q11 | nn11 | tw11 | nn_gf18 | tw_gf18 | latent24 | qvis | vis_nn | vis_tw]
-// (hoisted stream: without the two vertex rows, i.e. [query 6 | latent 12 | 2 visibility pairs])
-Pairs tex_input_pairs(bool hoist = false)
+// (hoisted stream: without the two vertex rows, i.e. [query 6 | latent 12 | 2 visibility pairs]; merged: vis_tw rides in the empty half of the
+// query feature's last pair, (q[5] | vis_tw), and the last pair is gone)
+Pairs tex_input_pairs(bool hoist = false, bool merged = false)
 {
     Pairs p;
     if (!hoist) {
         for (int t = 0; t < 11; ++t) p.emplace_back(11 + t, 22 + t);  // h0: nearest vertex row, h1: twin vertex row
         for (int t = 0; t < 18; ++t) p.emplace_back(33 + t, 51 + t);
     }
-    for (int u = 0; u < 6; ++u) p.emplace_back(u, u < 5 ? 6 + u : ZERO); // query feature: h0 q[0..5], h1 q[6..10]
+    for (int u = 0; u < 6; ++u) p.emplace_back(u, u < 5 ? 6 + u : merged ? 95 : ZERO); // query feature: h0 q[0..5], h1 q[6..10]
     chain(p, 1, 12, 69, 24);                                        // latent24 straight from the ibr accumulator
     p.emplace_back(93, 94);
-    p.emplace_back(95, ZERO);
+    if (!merged) p.emplace_back(95, ZERO);
     return p;
 }
 
@@ -163,15 +179,18 @@ Pairs tex_input_pairs(bool hoist = false)
 namespace {
 
 // k-pairs (input channel of lane half 0 / 1 per k-step) of every layer: structure only, no weights
-Pairs layer_pairs(int l, bool hoist = false)
+// (level: 0 the plain streams, 1 the hoisted bf16x3 stream, 2 the lean one -- layer_spec.h)
+Pairs layer_pairs(int l, int level = 0)
 {
     Pairs p;
+    const bool hoist = level >= 1, lean = level == 2;
+    auto bias_pair = [&](Pairs& q) { if (!(lean && lean_no_bias_pair(l))) ::bias_pair(q); };
     switch (l) {
     case L_GEO_AT0_A: case L_GEO_ATED0_A: return geo_input_pairs(64, hoist);
     case L_GEO_AT1_A: case L_GEO_ATED1_A: return geo_input_pairs(8);
     case L_GEO_AT0_B: case L_GEO_AT1_B: chain(p, 1, 6, 0, 10); return p;
-    case L_GEO_ATED0_B: chain(p, 2, 16, 0, 64); return p;
-    case L_GEO_ATED1_B: chain(p, 1, 4, 0, 8); return p;
+    case L_GEO_ATED0_B: if (!lean) chain(p, 2, 16, 0, 64); return p; // (lean: folded into mlp0 / mlp2)
+    case L_GEO_ATED1_B: if (!lean) chain(p, 1, 4, 0, 8); return p;
     case L_MLP0:
         for (int i = 0; i < PE_KPT_PER_HALF; ++i)
             for (int f = 0; f < PE_FEATS; ++f) p.emplace_back(f * 42 + i, f * 42 + PE_KPT_PER_HALF + i);
@@ -183,8 +202,8 @@ Pairs layer_pairs(int l, bool hoist = false)
     case L_MLP3: chain(p, 4, 12, 0, 120); bias_pair(p); return p;
     case L_HEAD0: case L_IBR: chain(p, 2, 16, 0, 64); chain(p, 2, 16, 64, 64); bias_pair(p); return p; // [mean | var]
     case L_HEAD1: case L_HEAD2: chain(p, 2, 16, 0, 64); bias_pair(p); return p;
-    case L_TEX_AT_A: return tex_input_pairs(hoist);
-    case L_TEX_A: return tex_input_pairs();
+    case L_TEX_AT_A: return tex_input_pairs(hoist, lean);
+    case L_TEX_A: return tex_input_pairs(false, lean);
     case L_TEX_AT_B: case L_TEX_B: chain(p, 3, 16, 0, 96); return p;
     }
     throw_error("internal: no layer %d", l);
@@ -227,7 +246,7 @@ void fold_host(const VanerfWeightTable& w, std::vector<float>& eff)
 {
     vanerf::LayerSrc src[NUM_LAYERS];
     sources(w, src);
-    eff.assign(eff_offset(NUM_LAYERS), 0.0f);
+    eff.assign(EFF_TOTAL, 0.0f);
     for (int l = 0; l < NUM_LAYERS; ++l) {
         const vanerf::LayerSrc& s = src[l];
         float* e = eff.data() + s.eff;
@@ -244,6 +263,21 @@ void fold_host(const VanerfWeightTable& w, std::vector<float>& eff)
             if (s.b) e[(size_t)s.nout * s.kin + o] = s.b[o];
         }
     }
+    // the folded matrices of the lean stream: F[o][c] = sum_k A[o][a0 + k] B[k][c], one fmaf chain per element in ascending k (fold_products_kernel
+    // of weights_update.hip runs the same chain: the same bits)
+    auto fold = [&](int la, int a0, int lb, unsigned dst) {
+        const int kin_a = kShape[la].kin, n = kShape[lb].nout, nc = kShape[lb].kin;
+        const float* a = eff.data() + eff_offset(la);
+        const float* b = eff.data() + eff_offset(lb);
+        for (int o = 0; o < kShape[la].nout; ++o)
+            for (int c = 0; c < nc; ++c) {
+                float acc = 0.0f;
+                for (int k = 0; k < n; ++k) acc = std::fmaf(a[(size_t)o * kin_a + a0 + k], b[(size_t)k * nc + c], acc);
+                eff[dst + (size_t)o * nc + c] = acc;
+            }
+    };
+    fold(L_MLP0, 294, L_GEO_ATED0_B, EFF_FOLD0);
+    fold(L_MLP2, 128, L_GEO_ATED1_B, EFF_FOLD1);
 }
 
 // Backward stream of one layer (layer_spec.h): dX = W^T dY as the same MFMA chain with the roles swapped.  K dimension: the layer's output
@@ -310,7 +344,7 @@ const PackTables& pack_tables()
     static const PackTables tables = [] {
         PackTables t;
         std::vector<float> fwd, bwd;
-        std::vector<WordB> fwd_b, fwd_bh;
+        std::vector<WordB> fwd_b, fwd_bh, fwd_bl;
         for (int l = 0; l < NUM_LAYERS; ++l) {
             t.offs.off[l] = (unsigned)fwd.size();
             if (fwd.size() != layer_offset(l)) throw_error("internal: layer %d starts at %zu, layer_spec.h says %u", l, fwd.size(), layer_offset(l));
@@ -318,9 +352,19 @@ const PackTables& pack_tables()
             const Mat m = id_matrix(l);
             const Pairs p = layer_pairs(l);
             emit(fwd, l, m, p);
-            emit_b_ids(fwd_b, l, m, p, false);
-            if (fwd_bh.size() != layer_offset_b(l, true)) throw_error("internal: layer %d (hoisted bf16x3) starts at %zu, layer_spec.h says %u", l, fwd_bh.size(), layer_offset_b(l, true));
-            emit_b_ids(fwd_bh, l, m, layer_pairs(l, true), true);
+            emit_b_ids(fwd_b, l, m, p, 0);
+            if (fwd_bh.size() != layer_offset_b(l, 1)) throw_error("internal: layer %d (hoisted bf16x3) starts at %zu, layer_spec.h says %u", l, fwd_bh.size(), layer_offset_b(l, 1));
+            emit_b_ids(fwd_bh, l, m, layer_pairs(l, 1), 1);
+            if (fwd_bl.size() != layer_offset_b(l, 2)) throw_error("internal: layer %d (lean bf16x3) starts at %zu, layer_spec.h says %u", l, fwd_bl.size(), layer_offset_b(l, 2));
+            emit_b_ids(fwd_bl, l, id_matrix(l, 2), layer_pairs(l, 2), 2);
+            if (t.bias.size() != bias_table_offset(l)) throw_error("internal: layer %d (bias table) starts at %zu, layer_spec.h says %u", l, t.bias.size(), bias_table_offset(l));
+            if (lean_no_bias_pair(l)) // [lane half][block][register] -> the bias of that D register's output row
+                for (int h = 0; h < 2; ++h)
+                    for (int ob = 0; ob < kNB[l]; ++ob)
+                        for (int r = 0; r < 16; ++r) {
+                            const int o = 32 * ob + row0(r) + 4 * h;
+                            t.bias.push_back(o < m.nout ? (int)m.b[o] : 0);
+                        }
             emit_bwd(bwd, l, m, p);
         }
         // slack behind the last layer (prefetch rings never read past a layer's own steps, this is belt and braces)
@@ -328,17 +372,19 @@ const PackTables& pack_tables()
         bwd.resize(bwd.size() + 2 * 64 * 4, 0.0f);
         fwd_b.resize(fwd_b.size() + 2 * 64 * 4, WordB{0, 0, 0});
         fwd_bh.resize(fwd_bh.size() + 2 * 64 * 4, WordB{0, 0, 0});
+        fwd_bl.resize(fwd_bl.size() + STREAM_SLACK_DW, WordB{0, 0, 0});
+        if (t.bias.size() != BIAS_TABLE_FLOATS) throw_error("internal: bias table of %zu floats, layer_spec.h says %u", t.bias.size(), BIAS_TABLE_FLOATS);
         t.fwd.assign(fwd.begin(), fwd.end());
         t.bwd.assign(bwd.begin(), bwd.end());
-        for (auto [src, dst] : {std::pair{&fwd_b, &t.fwd_b}, std::pair{&fwd_bh, &t.fwd_bh}}) {
+        for (auto [src, dst] : {std::pair{&fwd_b, &t.fwd_b}, std::pair{&fwd_bh, &t.fwd_bh}, std::pair{&fwd_bl, &t.fwd_bl}}) {
             dst->resize(2 * src->size());
             for (size_t i = 0; i < src->size(); ++i) {
                 (*dst)[2 * i] = (*src)[i].id0 | ((*src)[i].part << 30);
                 (*dst)[2 * i + 1] = (*src)[i].id1;
             }
         }
-        t.n_eff = eff_offset(NUM_LAYERS);
-        for (const std::vector<int>* v : {&t.fwd, &t.bwd, &t.fwd_b, &t.fwd_bh})
+        t.n_eff = EFF_TOTAL;
+        for (const std::vector<int>* v : {&t.fwd, &t.bwd, &t.fwd_b, &t.fwd_bh, &t.fwd_bl, &t.bias})
             for (int id : *v)
                 if ((id & 0x3fffffff) > (int)t.n_eff) throw_error("internal: placement id %d beyond the %u effective weights", id, t.n_eff);
         return t;
@@ -349,9 +395,10 @@ const PackTables& pack_tables()
 void layer_sources(const VanerfWeightTable& w, LayerSrc out[NUM_LAYERS]) { sources(w, out); }
 
 unsigned eff_layer_offset(int l) { return eff_offset(l); }
+unsigned eff_fold_offset() { return EFF_FOLD0; }
 
 void pack_weights_host(const VanerfWeightTable& w, std::vector<float>& out, LayerOffsets& offs, int mode, std::vector<float>* bwd, std::vector<float>* hoisted,
-                       std::vector<float>* eff_out)
+                       std::vector<float>* eff_out, std::vector<float>* lean, std::vector<float>* bias)
 {
     const PackTables& t = pack_tables();
     std::vector<float> eff;
@@ -368,6 +415,11 @@ void pack_weights_host(const VanerfWeightTable& w, std::vector<float>& out, Laye
         }
     };
     if (hoisted) place_b(t.fwd_bh, *hoisted);
+    if (lean) place_b(t.fwd_bl, *lean);
+    if (bias) {
+        bias->resize(t.bias.size());
+        for (size_t i = 0; i < bias->size(); ++i) (*bias)[i] = value(t.bias[i]);
+    }
     if (mode) {
         place_b(t.fwd_b, out);
     } else {
