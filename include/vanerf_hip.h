@@ -115,16 +115,22 @@ int vanerf_weights_update(VanerfWeights* w, const VanerfWeightTable* dev, const 
 int vanerf_weights_short_groups(const VanerfWeights* w, uint64_t* count);
 /* Host-only view of the packed fragment stream (no GPU touched): out[cap] or NULL to query the size; offsets[20]. */
 int vanerf_weights_pack_host(const VanerfWeightTable* w, float* out, int64_t cap, int64_t* n_out, unsigned* offsets);
-/* Host-only view of any stream a handle can carry: which = 0 the fp32 forward stream, 1 the bf16x3 forward stream (32-bit words of two bf16
- * each, copied raw), 2 the transposed fp32 stream of the fused backward pass, 3 the hoisted bf16x3 stream a bf16x3 handle carries behind
- * stream 1 (three first layers packed with their per-sample k-pairs only), 4 the lean bf16x3 stream behind that (what vanerf_query_samples
- * runs on when it is given vertex_products: the hoisted stream with geo_vis_fusion.fconv_ated.2 / fconv_ated1.2 multiplied into
- * mlp_geo.layers1's layers 0 / 2, no bias k-pair in five layers, one k-pair less in TexVisFusion's input), 5 the lean stream's fp32 bias table
- * (five layers' biases in accumulator-register order), 6 its two folded matrices in fp32 ([128][64], then [120][8]).  out[cap] or NULL: the size. */
+/* The streams a handle can carry: the `which` of the two calls below.  An fp32 handle carries FP32 and BACKWARD, a bf16x3 handle the others. */
+enum {
+    VANERF_STREAM_FP32 = 0,       /* the fp32 forward stream */
+    VANERF_STREAM_BF16X3 = 1,     /* the bf16x3 forward stream (32-bit words of two bf16 each, copied raw) */
+    VANERF_STREAM_BACKWARD = 2,   /* the transposed fp32 stream of the fused backward pass */
+    VANERF_STREAM_HOISTED = 3,    /* the hoisted bf16x3 stream behind stream 1 (three first layers packed with their per-sample k-pairs only) */
+    VANERF_STREAM_LEAN = 4,       /* the lean bf16x3 stream behind that (what vanerf_query_samples runs on when it is given vertex_products: the
+                                   * hoisted stream with geo_vis_fusion.fconv_ated.2 / fconv_ated1.2 multiplied into mlp_geo.layers1's layers 0 / 2,
+                                   * no bias k-pair in five layers, one k-pair less in TexVisFusion's input) */
+    VANERF_STREAM_LEAN_BIAS = 5,  /* the lean stream's fp32 bias table (five layers' biases in accumulator-register order) */
+    VANERF_STREAM_LEAN_FOLDED = 6 /* its two folded matrices in fp32 ([128][64], then [120][8]) */
+};
+/* Host-only view of any stream a handle can carry.  out[cap] or NULL: the size. */
 int vanerf_weights_stream_host(const VanerfWeightTable* w, int which, float* out, int64_t cap, int64_t* n_out);
 /* The streams a handle holds on the device, copied back to host memory (blocking; for tests of vanerf_weights_update): which = 0 the forward
- * stream of the handle's mode, 2 the backward stream (fp32 handles only), 3 / 4 / 5 / 6 the hoisted bf16x3 stream, the lean bf16x3 stream, its
- * bias table and its folded matrices (bf16x3 handles only).                                                                                      */
+ * stream of the handle's mode (never 1), any other a stream the handle carries.                                                               */
 int vanerf_weights_download(const VanerfWeights* w, int which, float* out, int64_t cap, int64_t* n_out);
 
 /* a1-a4  Pixel grid, ray generation, bbox clipping, coarse depths (src/model.py:1191-1238, 1496-1570), described by a VanerfPassDesc (below).

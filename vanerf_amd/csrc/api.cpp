@@ -17,6 +17,28 @@ extern "C" int vanerf_abi_version(void) { return VANERF_ABI_VERSION; }
 
 extern "C" const char* vanerf_last_error(void) { return g_last_error.c_str(); }
 
+namespace {
+// frees everything a handle holds and the handle; the first error, if any
+hipError_t release(VanerfWeights* h)
+{
+    hipError_t first = hipSuccess;
+    for (void* p : {(void*)h->block[BLOCK_MAIN], (void*)h->block[BLOCK_BACKWARD], (void*)h->block[BLOCK_EFF], (void*)h->stats, (void*)h->dev_beta}) {
+        const hipError_t e = p ? hipFree(p) : hipSuccess;
+        if (first == hipSuccess) first = e;
+    }
+    delete h;
+    return first;
+}
+
+void copy_out(const char* who, const std::vector<float>& src, float* out, int64_t cap, int64_t* n_out)
+{
+    *n_out = (int64_t)src.size();
+    if (!out) return;
+    if (cap < (int64_t)src.size()) throw_error("%s: buffer too small", who);
+    std::memcpy(out, src.data(), src.size() * sizeof(float)); // raw copy: the bf16x3 words are not numbers
+}
+} // namespace
+
 extern "C" int vanerf_weights_pack(const VanerfWeightTable* w, int mode, VanerfWeights** out)
 {
     return guarded([&] {
@@ -26,41 +48,45 @@ extern "C" int vanerf_weights_pack(const VanerfWeightTable* w, int mode, VanerfW
         constexpr size_t n_ptrs = offsetof(VanerfWeightTable, sigmoid_beta) / sizeof(const float*);
         for (size_t i = 0; i < n_ptrs; ++i)
             if (!ptrs[i]) throw_error("vanerf_weights_pack: weight pointer #%d is null", (int)i);
-        std::vector<float> host, host_bwd, host_h, eff, host_l, bias;
-        LayerOffsets offs{};
-        pack_weights_host(*w, host, offs, mode, mode == 0 ? &host_bwd : nullptr, mode == 1 ? &host_h : nullptr, mode == 1 ? &eff : nullptr,
-                          mode == 1 ? &host_l : nullptr, mode == 1 ? &bias : nullptr);
-        host_l.insert(host_l.end(), bias.begin(), bias.end()); // the bias table rides behind the lean stream
+        // every block's host image: the streams the mode carries back to back in the table's order (BLOCK_EFF: eff itself)
+        const std::vector<float> eff = fold_host(*w);
+        std::vector<float> host[NUM_BLOCKS];
+        size_t at[NUM_STREAMS] = {};
+        for (int s = 0; s < NUM_STREAMS; ++s) {
+            if (!carries(mode, s)) continue;
+            std::vector<float>& image = host[kStreams[s].block];
+            if (kStreams[s].kind == EFF_SLICE) {
+                image = eff;
+                at[s] = eff_slice_offset();
+            } else {
+                const std::vector<float> v = stream_host(eff, s);
+                at[s] = image.size();
+                image.insert(image.end(), v.begin(), v.end());
+            }
+        }
         auto* h = new VanerfWeights();
-        h->n_floats_bwd = host_bwd.size();
-        h->n_floats = host.size();
-        h->n_floats_h = host_h.size();
-        h->n_floats_l = host_l.size() - bias.size();
-        h->offs = offs;
+        h->offs = layer_offsets(mode);
         h->mode = mode;
         h->beta = w->sigmoid_beta < 2e-3f ? 2e-3f : w->sigmoid_beta; // sdf_activation clamp (src/model.py:880)
-        hipError_t e = hipGetDevice(&h->device);
-        if (e == hipSuccess) e = hipMalloc(&h->dev, (host.size() + host_h.size() + host_l.size()) * sizeof(float));
-        if (e == hipSuccess) e = hipMemcpy(h->dev, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice);
-        if (e == hipSuccess && !host_h.empty()) e = hipMemcpy(h->dev + host.size(), host_h.data(), host_h.size() * sizeof(float), hipMemcpyHostToDevice);
-        if (e == hipSuccess && !host_l.empty())
-            e = hipMemcpy(h->dev + host.size() + host_h.size(), host_l.data(), host_l.size() * sizeof(float), hipMemcpyHostToDevice);
-        if (e == hipSuccess && !eff.empty()) e = hipMalloc(&h->dev_eff, eff.size() * sizeof(float));
-        if (e == hipSuccess && !eff.empty()) e = hipMemcpy(h->dev_eff, eff.data(), eff.size() * sizeof(float), hipMemcpyHostToDevice);
-        if (e == hipSuccess && !host_bwd.empty()) e = hipMalloc(&h->dev_bwd, host_bwd.size() * sizeof(float));
-        if (e == hipSuccess && !host_bwd.empty()) e = hipMemcpy(h->dev_bwd, host_bwd.data(), host_bwd.size() * sizeof(float), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMalloc(&h->stats, sizeof(unsigned long long));
-        if (e == hipSuccess) e = hipMemset(h->stats, 0, sizeof(unsigned long long));
-        if (e == hipSuccess) e = hipMalloc(&h->dev_beta, sizeof(float));
-        if (e == hipSuccess) e = hipMemcpy(h->dev_beta, &h->beta, sizeof(float), hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            if (h->dev) (void)hipFree(h->dev);
-            if (h->dev_bwd) (void)hipFree(h->dev_bwd);
-            if (h->stats) (void)hipFree(h->stats);
-            if (h->dev_beta) (void)hipFree(h->dev_beta);
-            if (h->dev_eff) (void)hipFree(h->dev_eff);
-            delete h;
-            hip_check(e, "vanerf_weights_pack: device upload");
+        try {
+            HIP_CHECK(hipGetDevice(&h->device));
+            for (int b = 0; b < NUM_BLOCKS; ++b) { // one allocation and one copy per block
+                if (host[b].empty()) continue;
+                HIP_CHECK(hipMalloc(&h->block[b], host[b].size() * sizeof(float)));
+                HIP_CHECK(hipMemcpy(h->block[b], host[b].data(), host[b].size() * sizeof(float), hipMemcpyHostToDevice));
+            }
+            for (int s = 0; s < NUM_STREAMS; ++s) {
+                if (!carries(mode, s)) continue;
+                h->stream[s] = h->block[kStreams[s].block] + at[s];
+                h->words[s] = pack_tables().words(s);
+            }
+            HIP_CHECK(hipMalloc(&h->stats, sizeof(unsigned long long)));
+            HIP_CHECK(hipMemset(h->stats, 0, sizeof(unsigned long long)));
+            HIP_CHECK(hipMalloc(&h->dev_beta, sizeof(float)));
+            HIP_CHECK(hipMemcpy(h->dev_beta, &h->beta, sizeof(float), hipMemcpyHostToDevice));
+        } catch (...) {
+            (void)release(h);
+            throw;
         }
         *out = h;
     });
@@ -69,77 +95,46 @@ extern "C" int vanerf_weights_pack(const VanerfWeightTable* w, int mode, VanerfW
 extern "C" int vanerf_weights_free(VanerfWeights* w)
 {
     return guarded([&] {
-        if (!w) return;
-        if (w->dev) HIP_CHECK(hipFree(w->dev));
-        if (w->dev_bwd) HIP_CHECK(hipFree(w->dev_bwd));
-        if (w->stats) HIP_CHECK(hipFree(w->stats));
-        if (w->dev_beta) HIP_CHECK(hipFree(w->dev_beta));
-        if (w->dev_eff) HIP_CHECK(hipFree(w->dev_eff));
-        delete w;
+        if (w) hip_check(release(w), "vanerf_weights_free");
     });
 }
 
-// Host-only view of the packed stream, used by the CPU tests of the packer (no GPU needed).
+// Host-only view of the fp32 forward stream, used by the CPU tests of the packer (no GPU needed).
 extern "C" int vanerf_weights_pack_host(const VanerfWeightTable* w, float* out, int64_t cap, int64_t* n_out, unsigned* offsets)
 {
     return guarded([&] {
         if (!w || !n_out) throw_error("vanerf_weights_pack_host: null argument");
-        std::vector<float> host;
-        LayerOffsets offs{};
-        pack_weights_host(*w, host, offs);
-        *n_out = (int64_t)host.size();
-        if (offsets) std::copy_n(offs.off, (size_t)NUM_LAYERS, offsets);
-        if (out) {
-            if (cap < (int64_t)host.size()) throw_error("vanerf_weights_pack_host: buffer too small");
-            std::copy(host.begin(), host.end(), out);
-        }
+        if (offsets) std::copy_n(layer_offsets(0).off, (size_t)NUM_LAYERS, offsets);
+        copy_out("vanerf_weights_pack_host", stream_host(fold_host(*w), STREAM_FP32), out, cap, n_out);
     });
 }
 
-// Host-only view of any of the streams a handle can carry: which = 0 the fp32 forward stream, 1 the bf16x3 forward stream (32-bit words
-// of two bf16 each, returned as raw floats), 2 the transposed fp32 stream of the fused backward pass, 3 the hoisted bf16x3 stream, 4 the lean
-// bf16x3 stream, 5 the lean stream's fp32 bias table, 6 the two folded matrices of the lean stream in fp32, F0 [128][64] then F1 [120][8]
-// (layer_spec.h).
+// Host-only view of any of the streams a handle can carry (streams.h; the bf16x3 words returned as raw floats).
 extern "C" int vanerf_weights_stream_host(const VanerfWeightTable* w, int which, float* out, int64_t cap, int64_t* n_out)
 {
     return guarded([&] {
         if (!w || !n_out) throw_error("vanerf_weights_stream_host: null argument");
-        if (which < 0 || which > 6)
+        if (which < 0 || which >= NUM_STREAMS)
             throw_error("vanerf_weights_stream_host: which = %d (0 fp32, 1 bf16x3, 2 backward, 3 hoisted bf16x3, 4 lean bf16x3, 5 its bias table, 6 its folded matrices)", which);
-        std::vector<float> host, bwd, hoisted, lean, bias, eff;
-        LayerOffsets offs{};
-        pack_weights_host(*w, host, offs, which == 1 ? 1 : 0, which == 2 ? &bwd : nullptr, which == 3 ? &hoisted : nullptr, which == 6 ? &eff : nullptr,
-                          which == 4 ? &lean : nullptr, which == 5 ? &bias : nullptr);
-        if (which == 6) eff.erase(eff.begin(), eff.begin() + eff_fold_offset());
-        const std::vector<float>& src = which == 2 ? bwd : which == 3 ? hoisted : which == 4 ? lean : which == 5 ? bias : which == 6 ? eff : host;
-        *n_out = (int64_t)src.size();
-        if (out) {
-            if (cap < (int64_t)src.size()) throw_error("vanerf_weights_stream_host: buffer too small");
-            std::memcpy(out, src.data(), src.size() * sizeof(float)); // raw copy: the bf16x3 words are not numbers
-        }
+        copy_out("vanerf_weights_stream_host", stream_host(fold_host(*w), which), out, cap, n_out);
     });
 }
 
 // The streams a handle holds on the device, copied back (blocking; tests of vanerf_weights_update): which = 0 the forward stream of the handle's
-// mode, 2 the backward stream (fp32 handles), 3 / 4 / 5 / 6 the hoisted stream, the lean stream, its bias table and its folded matrices
-// (bf16x3 handles).
+// mode, otherwise a stream of streams.h.
 extern "C" int vanerf_weights_download(const VanerfWeights* w, int which, float* out, int64_t cap, int64_t* n_out)
 {
     return guarded([&] {
         if (!w || !n_out) throw_error("vanerf_weights_download: null argument");
-        if (which != 0 && (which < 2 || which > 6))
+        if (which != 0 && (which < 2 || which >= NUM_STREAMS))
             throw_error("vanerf_weights_download: which = %d (0 forward, 2 backward, 3 hoisted bf16x3, 4 lean bf16x3, 5 its bias table, 6 its folded matrices)", which);
-        const float* lean = w->n_floats_l ? w->dev + w->n_floats + w->n_floats_h : nullptr;
-        const float* src = which == 2 ? w->dev_bwd : which == 3 ? (w->n_floats_h ? w->dev + w->n_floats : nullptr) : which == 4 ? lean
-                           : which == 5 ? (lean ? lean + w->n_floats_l : nullptr) : which == 6 ? (lean && w->dev_eff ? w->dev_eff + eff_fold_offset() : nullptr) : w->dev;
-        const size_t n = which == 2 ? w->n_floats_bwd : which == 3 ? w->n_floats_h : which == 4 ? w->n_floats_l : which == 5 ? (size_t)BIAS_TABLE_FLOATS
-                         : which == 6 ? (size_t)FOLD_FLOATS : w->n_floats;
-        if (!src) throw_error("vanerf_weights_download: the handle carries no such stream");
-        *n_out = (int64_t)n;
+        if (which == STREAM_FP32) which = forward_stream(w->mode); // 0 asks for the forward stream of whichever mode
+        if (!w->stream[which]) throw_error("vanerf_weights_download: the handle carries no such stream");
+        *n_out = (int64_t)w->words[which];
         if (out) {
-            if (cap < (int64_t)n) throw_error("vanerf_weights_download: buffer too small");
+            if (cap < *n_out) throw_error("vanerf_weights_download: buffer too small");
             HIP_CHECK(hipDeviceSynchronize());
-            HIP_CHECK(hipMemcpy(out, src, n * sizeof(float), hipMemcpyDeviceToHost));
+            HIP_CHECK(hipMemcpy(out, w->stream[which], w->words[which] * sizeof(float), hipMemcpyDeviceToHost));
         }
     });
 }

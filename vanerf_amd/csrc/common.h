@@ -11,6 +11,8 @@
 
 #include "../../include/vanerf_hip.h"
 #include "layer_spec.h"
+#include "pack_math.h"
+#include "streams.h"
 
 namespace vanerf {
 
@@ -63,14 +65,9 @@ int guarded(F&& fn) noexcept
     }
 }
 
-// hoisted / lean: the second and third bf16x3 stream, bias: the lean level's fp32 bias table (layer_spec.h), eff_out: the effective weights
-// themselves (stage 1 below)
-void pack_weights_host(const VanerfWeightTable& w, std::vector<float>& out, LayerOffsets& offs, int mode = 0, std::vector<float>* bwd = nullptr,
-                       std::vector<float>* hoisted = nullptr, std::vector<float>* eff_out = nullptr, std::vector<float>* lean = nullptr,
-                       std::vector<float>* bias = nullptr);
+// The packer's two stages (weights_pack.cpp).  Stage 1: where a layer's parameters are and where its effective weights go in the flat array
+// `eff` (every layer's [out][in] matrix with weight-norm folded, then its bias; the folded matrices of the lean stream behind the last layer).
 unsigned eff_layer_offset(int l); // where layer l's [nout][kin] matrix starts in eff
-unsigned eff_fold_offset();       // where the folded matrices F0, F1 of the lean stream start in eff (behind the last layer)
-// The packer's two stages (weights_pack.cpp): where a layer's parameters are and where its effective weights go in the flat array `eff` ...
 struct LayerSrc {
     const float* w; // [nout][kin] (weight-normed layers: weight_v)
     const float* g; // weight_g or null
@@ -79,15 +76,19 @@ struct LayerSrc {
     unsigned eff;   // offset of the layer in eff: [nout][kin], then the bias
 };
 void layer_sources(const VanerfWeightTable& w, LayerSrc out[NUM_LAYERS]);
-// ... and the placement of eff in the streams: out[i] = id ? eff[id - 1] : 0.  fwd / bwd: the fp32 forward stream and the transposed stream of
-// the fused backward; fwd_b: the bf16x3 stream, two ints per 32-bit word (low half's id | part << 30, high half's id; part 0 = high bf16 part).
+void fold_products(FoldProduct out[2]);                   // the two folded matrices, F0 then F1, back to back at eff_slice_offset()
+std::vector<float> fold_host(const VanerfWeightTable& w); // eff from host pointers
+// Stage 2: the placement of eff in the streams (streams.h), weight independent and built once per process.
 struct PackTables {
-    std::vector<int> fwd, bwd, fwd_b, fwd_bh; // fwd_bh: the hoisted bf16x3 stream (layer_spec.h)
-    std::vector<int> fwd_bl, bias;            // fwd_bl: the lean bf16x3 stream, as fwd_b; bias: its fp32 bias table, one id per float, as fwd
-    LayerOffsets offs{};
+    std::vector<int> place[NUM_STREAMS]; // the gathers' ids (empty: EFF_SLICE)
+    LayerOffsets offs{};                 // of the fp32 forward stream
     unsigned n_eff = 0;
+    size_t words(int s) const { return kStreams[s].kind == EFF_SLICE ? FOLD_FLOATS : place[s].size() / (kStreams[s].kind == GATHER_BF16X3 ? 2 : 1); }
 };
 const PackTables& pack_tables();
+unsigned eff_slice_offset();                                           // where the EFF_SLICE stream starts in eff
+std::vector<float> stream_host(const std::vector<float>& eff, int which); // any stream of streams.h from eff (bf16x3 words as raw floats)
+LayerOffsets layer_offsets(int mode);                                  // of the forward stream of a handle of `mode`
 int layer_slots(int layer, int* k_of_slot, int cap);
 
 // A pass marches n_views * nx * ny * S samples in one launch; the validity partition (vanerf_query_order) indexes them with 32 bits, so
@@ -98,18 +99,13 @@ void check_camera_source(const char* who, const VanerfPassDesc& d); // render_ke
 } // namespace vanerf
 
 struct VanerfWeights {
-    float* dev = nullptr;   // packed fragment streams; bf16x3 handles: [the stream | the hoisted stream | the lean stream | its bias table] (layer_spec.h)
-    size_t n_floats_h = 0;  // 32-bit words of the hoisted stream, which starts at dev + n_floats (bf16x3 handles only)
-    size_t n_floats_l = 0;  // 32-bit words of the lean stream, which starts at dev + n_floats + n_floats_h; BIAS_TABLE_FLOATS of bias table follow it
-    float* dev_bwd = nullptr; // fp32 handles only: the transposed streams of the fused backward pass (query_backward.hip)
-    size_t n_floats_bwd = 0;
-    size_t n_floats = 0;
+    float* block[vanerf::NUM_BLOCKS] = {};   // the device allocations (streams.h); fp32 handles get BLOCK_EFF at their first vanerf_weights_update
+    float* stream[vanerf::NUM_STREAMS] = {}; // where each stream starts in its block (null: the handle does not carry it) ...
+    size_t words[vanerf::NUM_STREAMS] = {};  // ... and its 32-bit words; both set once, at the pack
     vanerf::LayerOffsets offs{};
     int mode = 0;
     float beta = 0.1f;      // sigmoid_beta as packed from the host (clamped); stale once vanerf_weights_update took it from the device ...
     float* dev_beta = nullptr; // ... so the passes' composites read this device copy (one float, clamped)
-    float* dev_eff = nullptr;  // the effective weights, stage 1 of the packer: what vanerf_vertex_products multiplies (bf16x3 handles: uploaded at
-                               // the pack) and what vanerf_weights_update folds into (fp32 handles: allocated at the first update)
     int device = 0;
     unsigned long long* stats = nullptr; // [0]: running count of 32-sample groups that took query_kernel's all-invalid short path
 };

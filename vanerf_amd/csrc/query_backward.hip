@@ -363,12 +363,12 @@ extern "C" int vanerf_query_backward(const VanerfWeights* w, const float* d, con
 {
     return guarded([&] {
         if (n <= 0) throw_error("vanerf_query_backward: n = %lld", (long long)n);
-        if (!w || !w->dev_bwd || w->mode != 0) throw_error("vanerf_query_backward: needs an fp32 weight handle (vanerf_weights_pack mode 0)");
+        if (!w || !w->stream[STREAM_BACKWARD]) throw_error("vanerf_query_backward: needs an fp32 weight handle (vanerf_weights_pack mode 0)");
         if (!d || !raw || !valid || !xs || !aux || !ys || !ig) throw_error("vanerf_query_backward: null argument");
         if (npad < n || npad % 32 != 0) throw_error("vanerf_query_backward: npad = %lld must be a multiple of 32 and >= n = %lld", (long long)npad, (long long)n);
         if ((long long)X_ROWS * 4 * npad >= (long long)NO_COL) throw_error("vanerf_query_backward: a block of %lld samples spills more than 4 GB", (long long)npad);
         BwdParams P;
-        P.wb = w->dev_bwd; P.wbytes = (unsigned)(w->n_floats_bwd * sizeof(float)); P.d = d; P.d2 = d2; P.noise = noise; P.noise2 = noise2; P.raw = raw; P.valid = valid; P.n = n; P.npad = npad;
+        P.wb = w->stream[STREAM_BACKWARD]; P.wbytes = (unsigned)(w->words[STREAM_BACKWARD] * sizeof(float)); P.d = d; P.d2 = d2; P.noise = noise; P.noise2 = noise2; P.raw = raw; P.valid = valid; P.n = n; P.npad = npad;
         P.xs = xs; P.aux = aux; P.ys = ys; P.ig = ig;
         int dev = 0, cus = 256;
         HIP_CHECK(hipGetDevice(&dev));

@@ -1128,11 +1128,12 @@ void check_frame_pointers(const char* who, const VanerfFrame& f)
 }
 
 // The parameters every launch has; what only some have (noise, order, valid, stamps, short_groups, vp, the spills) starts out absent.
-QueryParams query_params(const VanerfFrame& f, const float* stream_w, size_t stream_floats, const float* pts, const float* query_sdf,
+// The kernel runs on stream `s` of the handle; the lean kernel reads the bias table, which sits directly behind its stream, through the same buffer.
+QueryParams query_params(const VanerfFrame& f, const VanerfWeights& w, Stream s, const float* pts, const float* query_sdf,
                          const uint8_t* query_vis, const int32_t* knn_idx, int raw, int64_t n, float* out)
 {
     QueryParams P = {};
-    P.f = f; P.w = stream_w; P.wbytes = (unsigned)(stream_floats * sizeof(float));
+    P.f = f; P.w = w.stream[s]; P.wbytes = (unsigned)((w.words[s] + (s == STREAM_LEAN ? w.words[STREAM_LEAN_BIAS] : 0)) * sizeof(float));
     P.pts = pts; P.qsdf = query_sdf; P.qvis = query_vis; P.knn_in = knn_idx; P.raw = raw; P.n = n; P.out = out;
     const int ws[4] = {f.wi, f.wt, f.w0, f.w1}, hs[4] = {f.hi, f.ht, f.h0, f.h1};
     for (int i = 0; i < 4; ++i) { P.wm1[i] = (float)(ws[i] - 1); P.hm1[i] = (float)(hs[i] - 1); }
@@ -1189,7 +1190,7 @@ extern "C" int vanerf_query_samples(const VanerfWeights* w, const VanerfFrame* f
     return guarded([&] {
         if (n < 0) throw_error("vanerf_query_samples: n = %lld < 0", (long long)n);
         if (n == 0) return; // an empty batch is valid (and has null data pointers)
-        if (!w || !w->dev || !frame || !pts || !query_sdf || !query_vis || !knn_idx || !out) throw_error("vanerf_query_samples: null argument");
+        if (!w || !w->block[BLOCK_MAIN] || !frame || !pts || !query_sdf || !query_vis || !knn_idx || !out) throw_error("vanerf_query_samples: null argument");
         check_queue_word("vanerf_query_samples", queue_word);
         if ((n + 31) / 32 >= 0xffffff00LL) throw_error("vanerf_query_samples: n = %lld too large for one launch", (long long)n);
         const VanerfFrame& f = *frame;
@@ -1197,14 +1198,12 @@ extern "C" int vanerf_query_samples(const VanerfWeights* w, const VanerfFrame* f
         if (f.h0 < 1 || f.w0 < 1 || f.h1 < 1 || f.w1 < 1 || f.ht < 1 || f.wt < 1 || f.hi < 1 || f.wi < 1)
             throw_error("vanerf_query_samples: feature-map sizes must be positive");
         const bool hoist = vertex_products != nullptr;
-        if (hoist && (w->mode != 1 || !w->n_floats_h)) throw_error("vanerf_query_samples: a table of vertex products needs a bf16x3 weight handle");
+        if (hoist && !w->stream[STREAM_HOISTED]) throw_error("vanerf_query_samples: a table of vertex products needs a bf16x3 weight handle");
         if (hoist && (reinterpret_cast<uintptr_t>(vertex_products) & 15u)) throw_error("vanerf_query_samples: the table must be 16-byte aligned");
-        const bool lean = hoist && w->n_floats_l && lean_stream_enabled();
-        const float* stream_w = lean ? w->dev + w->n_floats + w->n_floats_h : hoist ? w->dev + w->n_floats : w->dev;
-        const size_t stream_floats = lean ? w->n_floats_l + BIAS_TABLE_FLOATS : hoist ? w->n_floats_h : w->n_floats;
-        QueryParams P = query_params(f, stream_w, stream_floats, pts, query_sdf, query_vis, knn_idx, raw, n, out);
+        const Stream s = !hoist ? forward_stream(w->mode) : w->stream[STREAM_LEAN] && lean_stream_enabled() ? STREAM_LEAN : STREAM_HOISTED;
+        QueryParams P = query_params(f, *w, s, pts, query_sdf, query_vis, knn_idx, raw, n, out);
         P.noise = noise; P.order = order; P.valid = valid; P.short_groups = w->stats; P.vp = vertex_products;
-        const QueryLaunch L = lean ? query_launch<1, false, 2>() : w->mode == 1 && hoist ? query_launch<1, false, 1>() : w->mode == 1 ? query_launch<1>() : query_launch<0>();
+        const QueryLaunch L = s == STREAM_LEAN ? query_launch<1, false, 2>() : s == STREAM_HOISTED ? query_launch<1, false, 1>() : s == STREAM_BF16X3 ? query_launch<1>() : query_launch<0>();
         launch_query(L, query_blocks(L, n), P, queue_word, stream);
     });
 }
@@ -1217,7 +1216,7 @@ extern "C" int vanerf_query_forward_spill(const VanerfWeights* w, const VanerfFr
 {
     return guarded([&] {
         if (n <= 0) throw_error("vanerf_query_forward_spill: n = %lld", (long long)n);
-        if (!w || !w->dev || w->mode != 0) throw_error("vanerf_query_forward_spill: needs an fp32 weight handle (vanerf_weights_pack mode 0)");
+        if (!w || !w->stream[STREAM_FP32]) throw_error("vanerf_query_forward_spill: needs an fp32 weight handle (vanerf_weights_pack mode 0)");
         if (!frame || !pts || !query_sdf || !query_vis || !knn_idx || !out_raw || !xs || !aux) throw_error("vanerf_query_forward_spill: null argument");
         check_queue_word("vanerf_query_forward_spill", queue_word);
         if (npad < n || npad % 32 != 0) throw_error("vanerf_query_forward_spill: npad = %lld must be a multiple of 32 and >= n = %lld", (long long)npad, (long long)n);
@@ -1226,7 +1225,7 @@ extern "C" int vanerf_query_forward_spill(const VanerfWeights* w, const VanerfFr
                         (long long)npad, (long long)SPILL_OFF / (4 * X_ROWS) / 32 * 32);
         const VanerfFrame& f = *frame;
         check_frame_pointers("vanerf_query_forward_spill", f);
-        QueryParams P = query_params(f, w->dev, w->n_floats, pts, query_sdf, query_vis, knn_idx, 1, n, out_raw);
+        QueryParams P = query_params(f, *w, STREAM_FP32, pts, query_sdf, query_vis, knn_idx, 1, n, out_raw);
         P.valid = valid; P.xs = xs; P.aux = aux; P.npad = npad;
         const QueryLaunch L = query_launch<0, true>();
         launch_query(L, query_blocks(L, n), P, queue_word, stream);
@@ -1331,7 +1330,7 @@ extern "C" int vanerf_debug_query_stamps(const VanerfWeights* w, const VanerfFra
                                          const uint8_t* query_vis, const int32_t* knn_idx, int64_t n, float* out, unsigned long long* stamps, int* n_waves, void* queue_word, void* stream)
 {
     return guarded([&] {
-        QueryParams P = query_params(*frame, w->dev, w->n_floats, pts, query_sdf, query_vis, knn_idx, 0, n, out);
+        QueryParams P = query_params(*frame, *w, forward_stream(w->mode), pts, query_sdf, query_vis, knn_idx, 0, n, out);
         P.stamps = stamps;
         const QueryLaunch L = w->mode == 1 ? query_launch<1>() : query_launch<0>();
         const long long blocks = query_blocks(L, n);

@@ -71,13 +71,14 @@ extern "C" int vanerf_vertex_products(const VanerfWeights* w, const VanerfFrame*
     const int rc = guarded([&] {
         if (!table) { size = (int)VP_FLOATS; return; }
         if (!w || !frame) throw_error("vanerf_vertex_products: null argument");
-        if (w->mode != 1 || !w->dev_eff) throw_error("vanerf_vertex_products: needs a bf16x3 weight handle (vanerf_weights_pack mode 1)");
+        const float* eff = w->block[BLOCK_EFF]; // the effective weights themselves: a bf16x3 handle holds them from the pack on
+        if (w->mode != 1 || !eff) throw_error("vanerf_vertex_products: needs a bf16x3 weight handle (vanerf_weights_pack mode 1)");
         if (!frame->vfeat0 || !frame->vfeat_tex) throw_error("vanerf_vertex_products: frame has a null pointer");
         if (cap_floats < (int64_t)VP_FLOATS) throw_error("vanerf_vertex_products: room for %lld floats, %u needed", (long long)cap_floats, VP_FLOATS);
         if (reinterpret_cast<uintptr_t>(table) & 15u) throw_error("vanerf_vertex_products: the table must be 16-byte aligned");
         const unsigned n = VP_NV * VP_PER_VERTEX;
-        hipLaunchKernelGGL(vertex_products_kernel, dim3((n + 255u) / 256u), dim3(256), 0, (hipStream_t)stream, w->dev_eff + eff_layer_offset(L_GEO_AT0_A),
-                           w->dev_eff + eff_layer_offset(L_GEO_ATED0_A), w->dev_eff + eff_layer_offset(L_TEX_AT_A), frame->vfeat0, frame->vfeat_tex, table);
+        hipLaunchKernelGGL(vertex_products_kernel, dim3((n + 255u) / 256u), dim3(256), 0, (hipStream_t)stream, eff + eff_layer_offset(L_GEO_AT0_A),
+                           eff + eff_layer_offset(L_GEO_ATED0_A), eff + eff_layer_offset(L_TEX_AT_A), frame->vfeat0, frame->vfeat_tex, table);
         HIP_CHECK(hipGetLastError());
     });
     return rc != VANERF_OK ? rc : size;

@@ -9,8 +9,8 @@
 // placement is a gather like every other.
 #include <hip/hip_runtime.h>
 
-#include <cmath>
-#include <cstring>
+#include <algorithm>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -239,47 +239,6 @@ void sources(const VanerfWeightTable& w, vanerf::LayerSrc out[NUM_LAYERS])
     set(L_TEX_B, w.tex_w2, nullptr, nullptr);
 }
 
-// stage 1 on the host: eff from host pointers.  torch.nn.utils.weight_norm, dim=0: W[o][:] = g[o] * v[o][:] / ||v[o][:]||_2
-// (src/utils.py:674-675); torch: v * (g / norm(v)), its norm accumulates in fp32 (vectorised); double here, error << 1 ulp of W.
-// weights_update.hip's fold_kernel does the same arithmetic in the same order on the device.
-void fold_host(const VanerfWeightTable& w, std::vector<float>& eff)
-{
-    vanerf::LayerSrc src[NUM_LAYERS];
-    sources(w, src);
-    eff.assign(EFF_TOTAL, 0.0f);
-    for (int l = 0; l < NUM_LAYERS; ++l) {
-        const vanerf::LayerSrc& s = src[l];
-        float* e = eff.data() + s.eff;
-        for (int o = 0; o < s.nout; ++o) {
-            const float* v = s.w + (size_t)o * s.kin;
-            if (s.g) {
-                double sum = 0.0;
-                for (int k = 0; k < s.kin; ++k) sum += (double)v[k] * (double)v[k];
-                const float scale = s.g[o] / (float)std::sqrt(sum);
-                for (int k = 0; k < s.kin; ++k) e[(size_t)o * s.kin + k] = v[k] * scale;
-            } else {
-                for (int k = 0; k < s.kin; ++k) e[(size_t)o * s.kin + k] = v[k];
-            }
-            if (s.b) e[(size_t)s.nout * s.kin + o] = s.b[o];
-        }
-    }
-    // the folded matrices of the lean stream: F[o][c] = sum_k A[o][a0 + k] B[k][c], one fmaf chain per element in ascending k (fold_products_kernel
-    // of weights_update.hip runs the same chain: the same bits)
-    auto fold = [&](int la, int a0, int lb, unsigned dst) {
-        const int kin_a = kShape[la].kin, n = kShape[lb].nout, nc = kShape[lb].kin;
-        const float* a = eff.data() + eff_offset(la);
-        const float* b = eff.data() + eff_offset(lb);
-        for (int o = 0; o < kShape[la].nout; ++o)
-            for (int c = 0; c < nc; ++c) {
-                float acc = 0.0f;
-                for (int k = 0; k < n; ++k) acc = std::fmaf(a[(size_t)o * kin_a + a0 + k], b[(size_t)k * nc + c], acc);
-                eff[dst + (size_t)o * nc + c] = acc;
-            }
-    };
-    fold(L_MLP0, 294, L_GEO_ATED0_B, EFF_FOLD0);
-    fold(L_MLP2, 128, L_GEO_ATED1_B, EFF_FOLD1);
-}
-
 // Backward stream of one layer (layer_spec.h): dX = W^T dY as the same MFMA chain with the roles swapped.  K dimension: the layer's output
 // rows in D-register order (k-pair t'' = block t''/16, register t''%16: rows 32 ob + row0(r) and + 4); output rows: the layer's input
 // SLOTS -- slot row 32 ib + jj of the result is k-pair t = 16 (kBLO + ib) + reg', lane half h' with jj = row0(reg') + 4 h', i.e. exactly
@@ -318,74 +277,90 @@ void emit_bwd(std::vector<float>& out, int layer, const Mat& m, const Pairs& pai
 
 namespace vanerf {
 
-inline unsigned short bf16_rne(float f)
+void fold_products(FoldProduct out[2])
 {
-    unsigned u;
-    std::memcpy(&u, &f, 4);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return 0x7fc0; // NaN stays NaN (the rounding add would carry a full payload over into -0.0); torch's constant
-    return (unsigned short)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-}
-inline float bf16_to_f32(unsigned short b)
-{
-    unsigned u = (unsigned)b << 16;
-    float f;
-    std::memcpy(&f, &u, 4);
-    return f;
-}
-inline unsigned short bf16_part(float v, int part)
-{
-    const unsigned short hi = bf16_rne(v);
-    return part ? bf16_rne(v - bf16_to_f32(hi)) : hi;
+    auto set = [](int la, int a0, int lb, unsigned dst) {
+        return FoldProduct{eff_offset(la), eff_offset(lb), dst, kShape[la].kin, a0, kShape[lb].nout, kShape[lb].kin, kShape[la].nout};
+    };
+    out[0] = set(L_MLP0, 294, L_GEO_ATED0_B, EFF_FOLD0);
+    out[1] = set(L_MLP2, 128, L_GEO_ATED1_B, EFF_FOLD1);
 }
 
-// The placement tables: weight independent, built once per process.
+std::vector<float> fold_host(const VanerfWeightTable& w)
+{
+    LayerSrc src[NUM_LAYERS];
+    sources(w, src);
+    std::vector<float> eff(EFF_TOTAL, 0.0f);
+    for (const LayerSrc& s : src)
+        for (int o = 0; o < s.nout; ++o) {
+            const float* v = s.w + (size_t)o * s.kin;
+            float* e = eff.data() + s.eff + (size_t)o * s.kin;
+            if (s.g) {
+                const float scale = weight_norm_scale(v, s.kin, s.g[o]);
+                for (int k = 0; k < s.kin; ++k) e[k] = v[k] * scale;
+            } else
+                std::copy_n(v, s.kin, e);
+            if (s.b) eff[s.eff + (size_t)s.nout * s.kin + o] = s.b[o];
+        }
+    FoldProduct fold[2];
+    fold_products(fold);
+    for (const FoldProduct& p : fold)
+        for (unsigned i = 0; i < (unsigned)(p.nout * p.nc); ++i) eff[p.dst + i] = folded_element(eff.data(), p, i);
+    return eff;
+}
+
+// One placement builder per gathered stream: the ids of layer l, appended.  level: of the bf16x3 streams (layer_spec.h).
+namespace {
+void place_f32(std::vector<float>& out, int l)
+{
+    if (out.size() != layer_offset(l)) throw_error("internal: layer %d starts at %zu, layer_spec.h says %u", l, out.size(), layer_offset(l));
+    emit(out, l, id_matrix(l), layer_pairs(l));
+}
+void place_backward(std::vector<float>& out, int l) { emit_bwd(out, l, id_matrix(l), layer_pairs(l)); }
+template <int LEVEL> void place_bf16x3(std::vector<WordB>& out, int l)
+{
+    if (out.size() != layer_offset_b(l, LEVEL)) throw_error("internal: layer %d (bf16x3 level %d) starts at %zu, layer_spec.h says %u", l, LEVEL, out.size(), layer_offset_b(l, LEVEL));
+    emit_b_ids(out, l, id_matrix(l, LEVEL), layer_pairs(l, LEVEL), LEVEL);
+}
+void place_bias(std::vector<float>& out, int l) // [lane half][block][register] -> the bias of that D register's output row
+{
+    if (out.size() != bias_table_offset(l)) throw_error("internal: layer %d (bias table) starts at %zu, layer_spec.h says %u", l, out.size(), bias_table_offset(l));
+    const Mat m = id_matrix(l);
+    for (int i = 0; lean_no_bias_pair(l) && i < 2 * kNB[l] * 16; ++i) {
+        const int o = 32 * ((i / 16) % kNB[l]) + row0(i % 16) + 4 * (i / (16 * kNB[l]));
+        out.push_back(o < m.nout ? m.b[o] : 0.0f);
+    }
+}
+// every layer through `place`, then `slack` zero ids behind the last layer (prefetch rings never read past a layer's own steps, this is belt
+// and braces); a bf16x3 word becomes its two ints
+template <class T> std::vector<int> placement(void (*place)(std::vector<T>&, int), size_t slack)
+{
+    std::vector<T> ids;
+    for (int l = 0; l < NUM_LAYERS; ++l) place(ids, l);
+    ids.resize(ids.size() + slack, T{});
+    std::vector<int> out;
+    for (const T& v : ids)
+        if constexpr (std::is_same_v<T, WordB>) out.insert(out.end(), {v.id0 | (v.part << 30), v.id1});
+        else out.push_back((int)v);
+    return out;
+}
+} // namespace
+
 const PackTables& pack_tables()
 {
     static const PackTables tables = [] {
         PackTables t;
-        std::vector<float> fwd, bwd;
-        std::vector<WordB> fwd_b, fwd_bh, fwd_bl;
-        for (int l = 0; l < NUM_LAYERS; ++l) {
-            t.offs.off[l] = (unsigned)fwd.size();
-            if (fwd.size() != layer_offset(l)) throw_error("internal: layer %d starts at %zu, layer_spec.h says %u", l, fwd.size(), layer_offset(l));
-            if (fwd_b.size() != layer_offset_b(l)) throw_error("internal: layer %d (bf16x3) starts at %zu, layer_spec.h says %u", l, fwd_b.size(), layer_offset_b(l));
-            const Mat m = id_matrix(l);
-            const Pairs p = layer_pairs(l);
-            emit(fwd, l, m, p);
-            emit_b_ids(fwd_b, l, m, p, 0);
-            if (fwd_bh.size() != layer_offset_b(l, 1)) throw_error("internal: layer %d (hoisted bf16x3) starts at %zu, layer_spec.h says %u", l, fwd_bh.size(), layer_offset_b(l, 1));
-            emit_b_ids(fwd_bh, l, m, layer_pairs(l, 1), 1);
-            if (fwd_bl.size() != layer_offset_b(l, 2)) throw_error("internal: layer %d (lean bf16x3) starts at %zu, layer_spec.h says %u", l, fwd_bl.size(), layer_offset_b(l, 2));
-            emit_b_ids(fwd_bl, l, id_matrix(l, 2), layer_pairs(l, 2), 2);
-            if (t.bias.size() != bias_table_offset(l)) throw_error("internal: layer %d (bias table) starts at %zu, layer_spec.h says %u", l, t.bias.size(), bias_table_offset(l));
-            if (lean_no_bias_pair(l)) // [lane half][block][register] -> the bias of that D register's output row
-                for (int h = 0; h < 2; ++h)
-                    for (int ob = 0; ob < kNB[l]; ++ob)
-                        for (int r = 0; r < 16; ++r) {
-                            const int o = 32 * ob + row0(r) + 4 * h;
-                            t.bias.push_back(o < m.nout ? (int)m.b[o] : 0);
-                        }
-            emit_bwd(bwd, l, m, p);
-        }
-        // slack behind the last layer (prefetch rings never read past a layer's own steps, this is belt and braces)
-        fwd.resize(fwd.size() + 2 * 64 * 4, 0.0f);
-        bwd.resize(bwd.size() + 2 * 64 * 4, 0.0f);
-        fwd_b.resize(fwd_b.size() + 2 * 64 * 4, WordB{0, 0, 0});
-        fwd_bh.resize(fwd_bh.size() + 2 * 64 * 4, WordB{0, 0, 0});
-        fwd_bl.resize(fwd_bl.size() + STREAM_SLACK_DW, WordB{0, 0, 0});
-        if (t.bias.size() != BIAS_TABLE_FLOATS) throw_error("internal: bias table of %zu floats, layer_spec.h says %u", t.bias.size(), BIAS_TABLE_FLOATS);
-        t.fwd.assign(fwd.begin(), fwd.end());
-        t.bwd.assign(bwd.begin(), bwd.end());
-        for (auto [src, dst] : {std::pair{&fwd_b, &t.fwd_b}, std::pair{&fwd_bh, &t.fwd_bh}, std::pair{&fwd_bl, &t.fwd_bl}}) {
-            dst->resize(2 * src->size());
-            for (size_t i = 0; i < src->size(); ++i) {
-                (*dst)[2 * i] = (*src)[i].id0 | ((*src)[i].part << 30);
-                (*dst)[2 * i + 1] = (*src)[i].id1;
-            }
-        }
+        t.place[STREAM_FP32] = placement(place_f32, 2 * 64 * 4);
+        t.place[STREAM_BF16X3] = placement(place_bf16x3<0>, 2 * 64 * 4);
+        t.place[STREAM_BACKWARD] = placement(place_backward, 2 * 64 * 4);
+        t.place[STREAM_HOISTED] = placement(place_bf16x3<1>, 2 * 64 * 4);
+        t.place[STREAM_LEAN] = placement(place_bf16x3<2>, STREAM_SLACK_DW);
+        t.place[STREAM_LEAN_BIAS] = placement(place_bias, 0);
+        for (int l = 0; l < NUM_LAYERS; ++l) t.offs.off[l] = layer_offset(l);
+        if (t.words(STREAM_LEAN_BIAS) != BIAS_TABLE_FLOATS) throw_error("internal: bias table of %zu floats, layer_spec.h says %u", t.words(STREAM_LEAN_BIAS), BIAS_TABLE_FLOATS);
         t.n_eff = EFF_TOTAL;
-        for (const std::vector<int>* v : {&t.fwd, &t.bwd, &t.fwd_b, &t.fwd_bh, &t.fwd_bl, &t.bias})
-            for (int id : *v)
+        for (const std::vector<int>& v : t.place)
+            for (int id : v)
                 if ((id & 0x3fffffff) > (int)t.n_eff) throw_error("internal: placement id %d beyond the %u effective weights", id, t.n_eff);
         return t;
     }();
@@ -395,42 +370,27 @@ const PackTables& pack_tables()
 void layer_sources(const VanerfWeightTable& w, LayerSrc out[NUM_LAYERS]) { sources(w, out); }
 
 unsigned eff_layer_offset(int l) { return eff_offset(l); }
-unsigned eff_fold_offset() { return EFF_FOLD0; }
+unsigned eff_slice_offset() { return EFF_FOLD0; }
 
-void pack_weights_host(const VanerfWeightTable& w, std::vector<float>& out, LayerOffsets& offs, int mode, std::vector<float>* bwd, std::vector<float>* hoisted,
-                       std::vector<float>* eff_out, std::vector<float>* lean, std::vector<float>* bias)
+LayerOffsets layer_offsets(int mode)
+{
+    LayerOffsets offs{};
+    for (int l = 0; l < NUM_LAYERS; ++l) offs.off[l] = mode ? layer_offset_b(l) : layer_offset(l);
+    return offs;
+}
+
+std::vector<float> stream_host(const std::vector<float>& eff, int which)
 {
     const PackTables& t = pack_tables();
-    std::vector<float> eff;
-    fold_host(w, eff);
-    auto value = [&](int id) { return id ? eff[(size_t)id - 1] : 0.0f; };
-    for (int l = 0; l < NUM_LAYERS; ++l) offs.off[l] = mode ? layer_offset_b(l) : t.offs.off[l];
-    auto place_b = [&](const std::vector<int>& tab, std::vector<float>& o) {
-        const size_t n = tab.size() / 2;
-        o.resize(n);
-        unsigned* dst = reinterpret_cast<unsigned*>(o.data());
-        for (size_t i = 0; i < n; ++i) {
-            const int a = tab[2 * i], part = (a >> 30) & 1;
-            dst[i] = (unsigned)bf16_part(value(a & 0x3fffffff), part) | ((unsigned)bf16_part(value(tab[2 * i + 1]), part) << 16);
-        }
-    };
-    if (hoisted) place_b(t.fwd_bh, *hoisted);
-    if (lean) place_b(t.fwd_bl, *lean);
-    if (bias) {
-        bias->resize(t.bias.size());
-        for (size_t i = 0; i < bias->size(); ++i) (*bias)[i] = value(t.bias[i]);
+    const std::vector<int>& tab = t.place[which];
+    std::vector<float> out(t.words(which));
+    unsigned* words = reinterpret_cast<unsigned*>(out.data()); // raw: the bf16x3 words are not numbers
+    for (size_t i = 0; i < out.size(); ++i) switch (kStreams[which].kind) {
+        case GATHER_F32: out[i] = placed_f32(eff.data(), tab[i]); break;
+        case GATHER_BF16X3: words[i] = placed_bf16x3(eff.data(), tab[2 * i], tab[2 * i + 1]); break;
+        case EFF_SLICE: out[i] = eff[eff_slice_offset() + i]; break;
     }
-    if (mode) {
-        place_b(t.fwd_b, out);
-    } else {
-        out.resize(t.fwd.size());
-        for (size_t i = 0; i < out.size(); ++i) out[i] = value(t.fwd[i]);
-    }
-    if (bwd) {
-        bwd->resize(t.bwd.size());
-        for (size_t i = 0; i < bwd->size(); ++i) (*bwd)[i] = value(t.bwd[i]);
-    }
-    if (eff_out) *eff_out = std::move(eff);
+    return out;
 }
 
 // slot -> input channel of layer l (2 T entries, slot 2 t + h): >= 0 channel of the reference's [out][in] matrix, -1 unused, -2 bias

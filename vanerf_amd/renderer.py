@@ -162,42 +162,47 @@ class PackedWeights:
     __del__ = close
 
 
-def stream_host(sd, which):
-    """Host-only packed stream `which` (0 fp32 forward, 1 bf16x3 forward, 2 backward, 3 hoisted bf16x3, 4 lean bf16x3) as raw int32 words (tests)."""
-    tab, keep = weight_table(sd)
+# The streams a handle can carry, by the `which` of vanerf_weights_stream_host / vanerf_weights_download (VANERF_STREAM_* of include/vanerf_hip.h).
+# An fp32 handle carries "fp32" and "backward", a bf16x3 handle the others.
+STREAMS = {"fp32": 0, "bf16x3": 1, "backward": 2, "hoisted": 3, "lean": 4, "lean_bias": 5, "lean_folded": 6}
+
+
+def _read_stream(call, first, which):
+    which = STREAMS.get(which, which)
     n = c_int64()
-    check(lib.vanerf_weights_stream_host(byref(tab), which, None, 0, byref(n)))
+    check(call(first, which, None, 0, byref(n)))
     out = torch.empty(n.value, dtype=torch.float32)
-    check(lib.vanerf_weights_stream_host(byref(tab), which, c_void_p(out.data_ptr()), n.value, byref(n)))
+    check(call(first, which, c_void_p(out.data_ptr()), n.value, byref(n)))
     return out.view(torch.int32)
+
+
+def stream_host(sd, which):
+    """Host-only packed stream `which` (a name or a number of STREAMS) as raw int32 words (tests)."""
+    tab, keep = weight_table(sd)
+    return _read_stream(lib.vanerf_weights_stream_host, byref(tab), which)
 
 
 def stream_device(weights, which):
-    """The stream a handle holds on the device (0 forward of its mode, 2 backward, 3 hoisted bf16x3, 4 lean bf16x3), copied back, as raw int32 words
-    (tests; blocking)."""
-    n = c_int64()
-    check(lib.vanerf_weights_download(weights.handle, which, None, 0, byref(n)))
-    out = torch.empty(n.value, dtype=torch.float32)
-    check(lib.vanerf_weights_download(weights.handle, which, c_void_p(out.data_ptr()), n.value, byref(n)))
-    return out.view(torch.int32)
+    """The stream `which` of STREAMS that a handle holds on the device (0: the forward stream of its mode, never 1), copied back, as raw int32
+    words (tests; blocking)."""
+    return _read_stream(lib.vanerf_weights_download, weights.handle, which)
 
 
-LEAN_BIAS_TABLE, LEAN_FOLDED = 5, 6  # `which` of the lean stream's fp32 bias table and of its folded matrices (include/vanerf_hip.h)
+def _stream_of(weights_or_sd, which):
+    get = stream_device if isinstance(weights_or_sd, PackedWeights) else stream_host
+    return get(weights_or_sd, which).view(torch.float32)
 
 
 def bias_table(weights_or_sd):
     """The fp32 bias table of the lean bf16x3 stream (layer_spec.h): five layers' biases in D-register order, [lane half][block][register] each.
     Of a bf16x3 handle: what it holds on the device (blocking); of a state dict: the host packer's (tests)."""
-    if isinstance(weights_or_sd, PackedWeights):
-        return stream_device(weights_or_sd, LEAN_BIAS_TABLE).view(torch.float32)
-    return stream_host(weights_or_sd, LEAN_BIAS_TABLE).view(torch.float32)
+    return _stream_of(weights_or_sd, "lean_bias")
 
 
 def folded_matrices(weights_or_sd):
     """The two folded matrices of the lean bf16x3 stream in fp32 (layer_spec.h): (F0 (128, 64) = W_mlp0[:, 294:358] W_ated0_b, F1 (120, 8) =
     W_mlp2[:, 128:136] W_ated1_b), of a bf16x3 handle (blocking) or, from the host packer, of a state dict (tests)."""
-    get = stream_device if isinstance(weights_or_sd, PackedWeights) else stream_host
-    f = get(weights_or_sd, LEAN_FOLDED).view(torch.float32)
+    f = _stream_of(weights_or_sd, "lean_folded")
     return f[:128 * 64].view(128, 64), f[128 * 64:].view(120, 8)
 
 
