@@ -19,7 +19,7 @@ an edge and unsound at a vertex: a point that shares y and z with a vertex (the 
 fan ties) got 0, 1 or 2 crossings from the fan whatever its geometry.  Of 4 000 such points per mesh, decided ones only, the C oracle (and
 the kernels, bit-equal to it) had the wrong sign on 28 (fingered hand), 32-33 (two hands, by placement), 10 (fine hand), 83 (torus) and 0 (shells);
 three points of the torus' axis line are among them.  A tie is now decided as if the point were displaced by (eps^2, eps) in (y,z), the same
-for every edge (oracle/mesh_oracle.c:edge_side, csrc/mesh_kernels.hip:edges_agree): 0 wrong on all of them.
+for every edge (oracle/mesh_oracle.c:edge_side, csrc/mesh_device.h:edges_agree): 0 wrong on all of them.
 A point at distance exactly 0 keeps the index rule: its sign means nothing under either, and the earlier tests and fixtures, whose only exact
 ties are points placed on vertices, recorded that one -- every result computed before this file existed is unchanged, bit for bit.
 

@@ -1,4 +1,4 @@
-"""Times mesh_query_accel_kernel alone on the samples of the benchmark view: the coarse samples, or with --fine the importance samples (z_new of a
+"""Times mesh_query_accel_kernel (csrc/mesh_accel_query.hip) alone on the samples of the benchmark view: the coarse samples, or with --fine the importance samples (z_new of a
 whole pass).  --order: also the tile-order kernel alone (vanerf_mesh_tile_order) and the query with its table.  --phases: the phase counters of a
 -DVANERF_MESH_PHASES build, by index and (with --order) by the table."""
 import os

@@ -1,7 +1,7 @@
-"""mesh_query_accel_kernel on small launches (a few rows of the benchmark view): the time of a launch that gives every wave at most one or two
+"""mesh_query_accel_kernel (csrc/mesh_accel_query.hip) on small launches (a few rows of the benchmark view): the time of a launch that gives every wave at most one or two
 items is the latency of a single item plus the cold start of the kernel (instruction fetch, table staging) -- what bounds an N-GPU rank's share."""
 import os, sys, torch
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from vanerf_amd import renderer as R, synth
 sd = synth.make_full_weights(0)
 frame = synth.make_frame(seed=11, tar_h=512, tar_w=334, orbit_deg=15.0)

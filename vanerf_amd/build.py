@@ -7,7 +7,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "lib", "libvanerf_hip.so")
-SOURCES = ["api.cpp", "weights_pack.cpp", "pass.cpp", "query_kernel.hip", "render_kernels.hip", "mesh_kernels.hip", "train_kernels.hip", "query_backward.hip", "weights_update.hip", "weight_products.hip", "vis_render.hip", "image_metrics.hip", "mask_at_box.hip", "vertex_products.hip", "surface.hip", "surface_lines.hip", "volume_render.hip", "volume_surface.hip"]
+SOURCES = ["api.cpp", "weights_pack.cpp", "pass.cpp", "query_kernel.hip", "render_kernels.hip", "mesh_kernels.hip", "mesh_accel_query.hip", "mesh_accel_build.hip", "train_kernels.hip", "query_backward.hip", "weights_update.hip", "weight_products.hip", "vis_render.hip", "image_metrics.hip", "mask_at_box.hip", "vertex_products.hip", "surface.hip", "surface_lines.hip", "volume_render.hip", "volume_surface.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
          "-Wall", "-Wextra", "-Wno-unused-parameter"]
 # per-file flags.  query_kernel.hip: MFMA results are allocated in VGPRs (the chained layers read every accumulator element once with VALU
@@ -20,7 +20,11 @@ FILE_FLAGS = {"query_kernel.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-slp
               # No SLP vectoriser here either: a v_pk_mul_f32 / v_pk_add_f32 takes the issue slots of two scalar ops on gfx950
               # (tools/probe_pk_f32.hip), so its packs save no issue time in this VALU-bound kernel and their operand pairs cost registers
               # (128 -> 111 VGPRs without it; 1.96 -> 1.79 ms on the benchmark view).
-              "mesh_kernels.hip": ["-mllvm", "-sink-insts-to-avoid-spills", "-fno-slp-vectorize"]}
+              "mesh_accel_query.hip": ["-mllvm", "-sink-insts-to-avoid-spills", "-fno-slp-vectorize"],
+              # the kernels of these two were built with the same pair while they shared a file with mesh_query_accel_kernel, and need neither flag;
+              # they keep them because their code differs without (raster, knn1, bounds_sort, tables, cell_scan, cell_record: a few instructions each)
+              "mesh_kernels.hip": ["-mllvm", "-sink-insts-to-avoid-spills", "-fno-slp-vectorize"],
+              "mesh_accel_build.hip": ["-mllvm", "-sink-insts-to-avoid-spills", "-fno-slp-vectorize"]}
 
 
 def _stale():
