@@ -634,6 +634,40 @@ int vanerf_volume_surface(const float* voxels, const float origin[3], const floa
                           const float* rays_d, const float* cam_pos, const float* z, const uint8_t* hit, int R, int rays_per_view, int row_rays, int S,
                           float* depth, float* normal, float* color, uint8_t* found, void* stream);
 
+/* The baked volume rendered in ANOTHER POSE of the same mesh.  The volume is a field in the source pose's space; the
+ * mesh has the same faces in every pose; so a sample of a ray through the posed hand is carried back into source space by the affine map of
+ * its closest face and looked up there.  A preview under the usual surface-aligned deformation model: it does not claim what the networks would
+ * render from a photograph of the new pose.
+ *
+ *     vanerf_pose_transforms: verts_src[nv][3], verts_pose[nv][3], faces[nf][3] -> T[nf][12], one record per face: A (3 x 3, row-major) then
+ *         t, the map q = A p + t from POSED space to SOURCE space.  For face (i0, i1, i2) and a mesh X: a = x1 - x0, b = x2 - x0, c = a x b,
+ *         n = c / |c|, M_X = [a b n] as columns; the rows of M_X^-1 are (b x n) / det, (n x a) / det and n with det = a . (b x n).
+ *         A = M_src M_pose^-1, t = x0_src - A x0_pose.  n is a UNIT vector: distance along the face normal is preserved, so skin thickness does
+ *         not scale with the triangle's area.  Computed in fp64 from the fp32 vertices (every product and sum rounded separately, sums from the
+ *         left) and rounded once to fp32.  A face whose |c|^2 is not above 1e-30 in either mesh, or any of whose 12 fp32 values is not finite,
+ *         gets A = I, t = centroid_src - centroid_pose (centroid = ((x0 + x1) + x2) / 3 in fp64); a face with a vertex index outside
+ *         [0, nv) gets A = I, t = 0.  nv, nf >= 1; T 16-byte aligned.  One thread per face, one launch.
+ *     vanerf_volume_render_posed: vanerf_volume_render's grid, rays, sigmoid_beta, layouts and outputs, plus T[nf][12] (16-byte aligned), and
+ *         per sample face[R][S] and sdf[R][S]: what vanerf_mesh_query_accel returns for the POSED mesh at the points of vanerf_sample_points on
+ *         the same rays.  The kernel makes no discrete geometric decision of its own.  Per ray:
+ *         - hit == 0: colour, depth and alpha are 0 and nothing else happens;
+ *         - sample i is EMPTY iff face < 0, face >= nf, sdf is not finite or sdf > reach (reach: any float but NaN; +inf disables the test,
+ *           -inf empties every sample).  An empty sample has c = 0: it contributes nothing and leaves the transmittance as it is;
+ *         - otherwise p = o + d z_i per axis (vanerf_sample_points' expression) is carried to q = A p + t with its face's record, in fp32:
+ *           qx = ((A00 px + A01 py) + A02 pz) + tx and likewise for y and z, every product and sum rounded separately; (f, r, g, b) is
+ *           vanerf_volume_render's trilinear interpolation at q, with its clamp to the grid (border padding: given (face, sdf) the outputs
+ *           are a continuous function of the float inputs; `reach` bounds how far a border voxel can smear) and its (1 - w) a + w b blends;
+ *         - the composite is vanerf_volume_render's unchanged, dist = 1e10f for the ray's last sample whether or not that sample is empty.
+ *         One wave per ray, the samples over the lanes in rounds of 64, the waves of a block on a 2 x 2 pixel tile of one view; a round all of
+ *         whose samples are empty issues no gather (the same bits either way).  Any S >= 1; nf >= 1; V <= 65535; R == 0 is a no-op.  One launch.
+ * All pointers but origin and spacing are DEVICE pointers.  All work goes to `stream`; no allocation, no host synchronisation, no atomics, no
+ * device-side state; every output element is written on every call: the same bits every call.  Arguments are checked before any launch.  */
+int vanerf_pose_transforms(const float* verts_src, const float* verts_pose, int nv, const int32_t* faces, int nf, float* T, void* stream);
+int vanerf_volume_render_posed(const float* voxels, const float origin[3], const float spacing[3], int nx, int ny, int nz, const VanerfWeights* w,
+                               float beta, const float* rays_d, const float* cam_pos, const float* z, const uint8_t* hit, int R, int rays_per_view,
+                               int row_rays, int S, const float* T, int nf, const int32_t* face, const float* sdf, float reach, float* color,
+                               float* depth, float* alpha, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

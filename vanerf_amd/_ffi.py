@@ -137,6 +137,9 @@ _SIGS = {
                                      c_int, _FP, _FP, _FP, c_void_p]),
     "vanerf_volume_surface": (c_int, [_FP, POINTER(c_float), POINTER(c_float), c_int, c_int, c_int, c_float, c_int, _FP, _FP, _FP, _FP, c_int, c_int, c_int,
                                       c_int, _FP, _FP, _FP, _FP, c_void_p]),
+    "vanerf_pose_transforms": (c_int, [_FP, _FP, c_int, _FP, c_int, _FP, c_void_p]),
+    "vanerf_volume_render_posed": (c_int, [_FP, POINTER(c_float), POINTER(c_float), c_int, c_int, c_int, c_void_p, c_float, _FP, _FP, _FP, _FP, c_int, c_int,
+                                           c_int, c_int, _FP, c_int, _FP, _FP, c_float, _FP, _FP, _FP, c_void_p]),
 }
 EXPORTS = tuple(_SIGS)
 

@@ -648,6 +648,15 @@ class VANeRF(nn.Module):
         from . import baked
         return baked.render_baked_surface_views(baked.bake_volume(self, tr_batch, resolution=resolution), cam_tars, **kwargs)
 
+    @torch.no_grad()
+    def render_posed_views(self, tr_batch, verts_pose, cam_tars, resolution=128, volume=None, **kwargs):
+        """The hand of tr_batch in ANOTHER pose of its mesh, verts_pose (nv, 3), from the target cameras: the frame baked
+        at `resolution` (bake_volume, unless volume= hands one in) and vanerf_amd.posed.render_posed_views (kwargs: its samples, reach, bounds,
+        accel) on it.  A preview under a surface-aligned deformation model: the networks are not evaluated on the new pose."""
+        from . import baked, posed
+        vol = baked.bake_volume(self, tr_batch, resolution=resolution) if volume is None else volume
+        return posed.render_posed_views(vol, posed._frame_faces(tr_batch, vol.voxels.device), verts_pose, cam_tars, **kwargs)
+
     def attach_autograd(self, out, img_in, feat_geo, feat_tex, targets, sp_data, fg_mask):
         """Replaces the differentiable entries of `out` (a batch_render_pifu_nerf result computed with _autograd=True) by tensors that
         carry the HIP values and, in backward, the gradients of the networks evaluated at the same samples (same points, same importance
