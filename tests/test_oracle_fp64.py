@@ -7,6 +7,7 @@ import pytest
 import torch
 
 from oracle import vanerf_oracle as orc
+from tests.oracle_criterion import cast  # noqa: F401  (re-exported: tests/test_oracle_posed.py and the per-sample tests import it from here)
 from vanerf_amd import synth
 from vanerf_amd.hip_backward import LAYER_PARAMS
 
@@ -15,17 +16,6 @@ IG_NAMES = tuple(IG_WIDTHS)
 # layers followed by a ReLU (the others: softplus, sigmoid gates or nothing)
 RELU_LAYERS = ("geo_vis_fusion.fconv_at.0.weight", "geo_vis_fusion.fconv_ated.0.weight", "geo_vis_fusion.fconv_at1.0.weight",
                "geo_vis_fusion.fconv_ated1.0.weight", "tex_vis_fusion.fconv_at.0.weight", "tex_vis_fusion.fconv.0.weight")
-
-
-def cast(obj, dtype):
-    """Every floating tensor of a (nested) dict / list in `dtype`; integer and bool tensors and numbers unchanged."""
-    if isinstance(obj, torch.Tensor):
-        return obj.to(dtype) if obj.is_floating_point() else obj
-    if isinstance(obj, dict):
-        return {k: cast(v, dtype) for k, v in obj.items()}
-    if isinstance(obj, (list, tuple)):
-        return type(obj)(cast(v, dtype) for v in obj)
-    return obj
 
 
 def param_keys(spec):

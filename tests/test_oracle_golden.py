@@ -1,12 +1,20 @@
 """The CPU oracle (oracle/vanerf_oracle.py) against golden vectors captured from the reference's own code
 (oracle/gen_golden.py, run in the build container; fixtures in tests/golden/).  Floats: <= 1e-6 abs
-(same torch ops, same order); integers and booleans: bit-exact."""
+(same torch ops, same order); integers and booleans: bit-exact.
+
+"Same ops, same order" makes the fp32 bits equal only on the CPU whose torch kernels wrote the golden.  Every float comparison therefore
+also stands under the host-independent criterion of tests/oracle_criterion.py: the golden within max(bar, 3 H + u) of the oracle in fp64,
+H this host's own fp32 error.  test_spatial_encoder and test_tex_vertex_features have that criterion alone (the reference's own fp32 result
+is farther from the exact value than their bars: no host but the writer's could pass); every other comparison keeps its direct test and has
+a `*_under_the_criterion` companion.  Not restated: pts_fine of test_whole_pass (the points come out of searchsorted and sort, which
+stay fp32), test_ray_bbox, test_importance_sample and test_render_full_stitch."""
 import numpy as np
 import pytest
 import torch
 
 from oracle import vanerf_oracle as orc
 from tests.conftest import assert_close_frac
+from tests.oracle_criterion import both, hold, hold_pass, remarch64
 from vanerf_amd import synth
 
 TOL = 1e-6
@@ -20,14 +28,28 @@ def close(a, b, tol=TOL):
 
 
 def test_spatial_encoder(golden):
+    """Both comparisons under the criterion (tests/oracle_criterion.py), floor 1e-6.  Against the golden directly the first one failed on every
+    host but the writer's: the reference's own fp32 result is 1.4e-6 from the exact value.  Measured on the CPU machine and on an MI355X host
+    (torch 2.10, AVX512 kernels on both: the figures of this file agree between the two to every digit given):
+
+      tensor             | |o32 - golden| | D        | H        | D/H  | bar
+      spatial_encode     | 1.486e-6       | 1.402e-6 | 1.830e-6 | 0.77 | 5.55e-6
+      position_embedding | 0              | 7.82e-7  | 7.82e-7  | 1.00 | 2.47e-6"""
     g = golden("spatial")
-    close(orc.spatial_encode(g["v"], g["kpt3d"], g["extrin"]), g["y"])
-    close(orc.position_embedding(g["pe_x"], 3), g["pe_y"])
+    hold("spatial_encode", g["y"], *both(orc.spatial_encode, g["v"], g["kpt3d"], g["extrin"]), TOL)
+    hold("position_embedding", g["pe_y"], *both(lambda x: orc.position_embedding(x, 3), g["pe_x"]), TOL)
 
 
 def test_feat_sample(golden):
     g = golden("feat_sample")
     close(orc.feat_sample(g["feat"], g["uv"]), g["out"])
+
+
+def test_feat_sample_under_the_criterion(golden):
+    """test_feat_sample under the criterion, floor 1e-6.  CPU machine and MI355X host alike: |o32 - golden| 0, D 5.41e-7, H 5.41e-7, D/H 1.00,
+    bar 1.86e-6."""
+    g = golden("feat_sample")
+    hold("feat_sample", g["out"], *both(orc.feat_sample, g["feat"], g["uv"]), TOL)
 
 
 def test_ray_bbox(golden):
@@ -50,6 +72,31 @@ def test_rgba2out(golden, name, beta):
     assert abs(g["beta_after_" + name].item() - max(beta, 2e-3)) < 1e-8  # reference clamps the parameter in place
     for a, k in ((color, "color"), (depth, "depth"), (alpha, "alpha"), (contrib, "contrib"), (sdf, "sdf")):
         close(a, g[f"{k}_{name}"])
+
+
+@pytest.mark.parametrize("name,beta", [("b0p1", 0.1), ("b2em3", 1e-3)])
+def test_rgba2out_under_the_criterion(golden, name, beta):
+    """test_rgba2out under the criterion, floor 1e-6: the floor decides all twelve bars (3 H + u stays below 4e-7).  CPU machine and MI355X
+    host alike, D / H / D/H for beta 0.1 and beta 1e-3 (clamped to 2e-3):
+
+      tensor        | beta 0.1                  | beta 1e-3
+      sigma x beta  | 7.80e-8 / 7.80e-8 / 1.00  | 7.48e-8 / 7.48e-8 / 1.00
+      color         | 3.71e-8 / 6.33e-8 / 0.59  | 8.91e-8 / 8.91e-8 / 1.00
+      depth         | 8.36e-8 / 1.05e-7 / 0.80  | 7.38e-8 / 7.38e-8 / 1.00
+      alpha         | 5.96e-8 / 5.96e-8 / 1.00  | 5.96e-8 / 5.96e-8 / 1.00
+      contrib       | 6.30e-8 / 6.30e-8 / 1.00  | 7.30e-8 / 7.30e-8 / 1.00
+      sdf           | 6.13e-8 / 6.70e-8 / 0.91  | 8.09e-8 / 8.09e-8 / 1.00
+
+    Not seen by this fixture, nor by any other golden: `+ 1e-8` dropped from the two divides (the outputs of every golden move by at most 1.1e-8,
+    a sixth of an fp32 ulp of a depth) and 1e10 -> 1e9 in the last `dist` (no output moves by a bit)."""
+    g = golden("rgba2out")
+    sd = {"sigmoid_beta": torch.tensor([beta])}
+    scale = max(beta, 2e-3)  # sigma reaches 1/beta = 500: compared relative to that scale, as in test_rgba2out
+    hold(f"rgba2out[{name}]:sigma", g["sigma_" + name] * scale,
+         *both(lambda sd, rgba, vs: orc.sdf_activation(sd, -(rgba[..., 0] + vs.squeeze(-1))) * scale, sd, g["rgba"], g["vert_sdf"]), TOL)
+    o32, o64 = both(orc.rgba2out, sd, g["rgba"], g["z"], g["vert_sdf"])
+    for i, k in enumerate(("color", "depth", "alpha", "contrib", "sdf")):
+        hold(f"rgba2out[{name}]:{k}", g[f"{k}_{name}"], o32[i], o64[i], TOL)
 
 
 def test_importance_sample(golden):
@@ -100,6 +147,46 @@ def test_query_blocks(golden, hot_weights):
     assert torch.equal(g["ibr_rgb"].reshape(N, 3), g["rgb_feat"][0, :, :3])
 
 
+def test_query_blocks_under_the_criterion(golden, hot_weights):
+    """The blocks of test_query_blocks under the criterion, each on the golden's own intermediate inputs cast up; floor 1e-6 (0 for the IBR
+    head, an exact identity at one view).  CPU machine and MI355X host alike:
+
+      block      | |o32 - golden| | D        | H        | D/H  | bar
+      y          | 5.96e-8        | 1.208e-7 | 1.208e-7 | 1.00 | 1.00e-6
+      geo_fused0 | 6.56e-7        | 5.487e-6 | 5.546e-6 | 0.99 | 1.68e-5
+      geo_fused1 | 3.58e-7        | 1.415e-5 | 1.427e-5 | 0.99 | 4.29e-5
+      mlp_out    | 3.58e-7        | 2.25e-7  | 2.40e-7  | 0.94 | 1.00e-6
+      x_view     | 4.84e-8        | 5.67e-8  | 5.50e-8  | 1.03 | 1.00e-6
+      latent     | 4.84e-8        | 5.71e-8  | 6.07e-8  | 0.94 | 1.00e-6
+      rgb_feat   | 2.98e-7        | 3.55e-7  | 3.08e-7  | 1.15 | 1.04e-6
+      ibr_rgb    | 0              | 0        | 0        | -    | 5.96e-8"""
+    g = golden("query")
+    sd = dict(hot_weights)
+    frame = _frame3()
+    cam, vert3d, fgeo = frame["cam_in"], frame["targets"]["vert_world"], frame["feat_geo"]
+    pts, N = g["pts"], g["pts"].shape[1]
+    vv = g["vert_vis"].type(torch.int)
+    hold("blocks:y", g["y"], *both(orc.spatial_encode, pts, frame["sp_data"]["kpt3d"], frame["sp_data"]["extrin"]), TOL)
+
+    def fusion(sd, cam, fgeo, vert3d, pts, q_sdf):
+        xy = orc.project(pts, cam)[0]
+        fs = [orc.feat_sample(f, xy).view(1, 1, N, -1) for f in fgeo]
+        return orc.geo_vis_fusion(sd, orc.project_verts(vert3d, cam), fgeo, fs, vert3d, pts, vv, g["q_vis"], q_sdf.unsqueeze(-1))
+
+    f32, f64 = both(fusion, sd, cam, fgeo, vert3d, pts, g["q_sdf"])
+    hold("blocks:geo_fused0", g["geo_fused0"], f32[0], f64[0], TOL)
+    hold("blocks:geo_fused1", g["geo_fused1"], f32[1], f64[1], TOL)
+    m32, m64 = both(lambda sd, y, f, w: orc.mlp_geo(sd, y.view(1, 1, N, -1), f, g["out_mask"], w),
+                    sd, g["y"], [g["geo_fused0"], g["geo_fused1"]], g["pix_weight"])
+    assert torch.equal(m64[1], g["mlp_valid"])
+    for i, k in ((0, "mlp_out"), (2, "x_view"), (3, "latent")):
+        hold("blocks:" + k, g[k], m32[i], m64[i], TOL)
+    hold("blocks:rgb_feat", g["rgb_feat"], *both(lambda sd, vf, ft, vert3d, pts, img_xy, l24: orc.tex_vis_fusion(
+        sd, vf, ft, vert3d, pts, vv, g["q_vis"], img_xy, l24), sd, g["vert_feat29"], g["ft_xy"], vert3d, pts, g["img_xy"], g["latent24"]), TOL)
+    hold("blocks:ibr_rgb", g["ibr_rgb"].reshape(N, 3), *both(lambda sd, rf, rd: orc.ibr_head(
+        sd, rf.view(N, 1, 1, -1), rd.reshape(N, 1, 1, 4), g["out_mask"].view(N, 1, 1, 1)).reshape(N, 3), sd, g["rgb_feat"], g["ray_diff"]), 0.0)
+
+
 def _texframe_weights(golden):
     """Reference init (src/model.py:669-698): torch.manual_seed(125) before every module, normal_(0, 0.02);
     LayerNorm keeps ones/zeros.  Rebuilt here instead of committing 16 MB, verified by checksums."""
@@ -122,11 +209,24 @@ def _texframe_weights(golden):
 
 
 def test_tex_vertex_features(golden):
+    """The per-vertex feature under the criterion, floor 2e-6, separately for its 11 gathered columns (bilinear taps of the image and the
+    128 x 128 texture map) and its 18 conv-stack columns (two 3 x 3 conv + LayerNorm stacks, pooled, two conv1d + LayerNorm).
+    Against the golden directly it failed on every host but the writer's: the reference's own fp32 result is 6.1e-5 from the exact value.
+    CPU machine and MI355X host alike:
+
+      columns    | |o32 - golden| | D        | H        | D/H  | bar
+      gathered   | 0              | 1.351e-5 | 1.351e-5 | 1.00 | 4.06e-5
+      conv_stack | 7.15e-6        | 6.127e-5 | 6.109e-5 | 1.00 | 1.84e-4
+
+    LayerNorm eps 1e-5 for 1e-6 in the oracle: D 0.33 on the conv-stack columns."""
     g = golden("query")
     sd = _texframe_weights(golden)
     frame = _frame3()
-    vert_xy = orc.project_verts(frame["targets"]["vert_world"], frame["cam_in"])
-    close(orc.tex_vertex_features(sd, vert_xy, frame["feat_tex"], frame["img_in"]), g["vert_feat29"], 2e-6)
+    o32, o64 = both(lambda sd, verts, cam, ft, img: orc.tex_vertex_features(sd, orc.project_verts(verts, cam), ft, img),
+                    sd, frame["targets"]["vert_world"], frame["cam_in"], frame["feat_tex"], frame["img_in"])
+    assert o32.shape[-1] == 29
+    for what, cols in (("gathered", slice(0, 11)), ("conv_stack", slice(11, 29))):  # [img 3 | tex 8] bilinear taps; [gf 18] convs + LayerNorms
+        hold("tex_vertex_features:" + what, g["vert_feat29"][..., cols], o32[..., cols], o64[..., cols], 2e-6)
 
 
 def test_query_whole(golden, hot_weights):
@@ -144,9 +244,43 @@ def test_query_whole(golden, hot_weights):
     close(out, g["out"], 2e-6)
 
 
+def test_query_whole_under_the_criterion(golden, hot_weights):
+    """test_query_whole under the criterion, floors 1e-6 and (out) 2e-6.  CPU machine and MI355X host alike:
+
+      tensor     | |o32 - golden| | D        | H        | D/H  | bar
+      out_mask   | 0              | 0        | 0        | -    | 1.00e-6
+      pix_weight | 0              | 5.72e-8  | 5.72e-8  | 1.00 | 1.00e-6
+      latent24   | 5.96e-8        | 1.133e-6 | 1.148e-6 | 0.99 | 3.47e-6
+      ray_diff   | 0              | 2.80e-7  | 2.80e-7  | 1.00 | 1.00e-6
+      out        | 4.84e-7        | 4.987e-6 | 4.868e-6 | 1.02 | 1.47e-5"""
+    g = golden("query")
+    sd = dict(hot_weights)
+    sd.update(_texframe_weights(golden))
+    frame = _frame3()
+
+    def whole(sd, frame, pts, q_sdf, view, fg_mask):
+        want = {}
+        out, valid = orc.query(sd, pts, frame["cam_in"], frame["targets"], frame["feat_geo"], frame["feat_tex"], g["vert_vis"], g["q_vis"],
+                               q_sdf, frame["sp_data"], frame["img_in"], view, fg_mask, want=want)
+        assert torch.equal(valid, g["valid"])
+        return dict(out_mask=want["out_mask"], pix_weight=want["pix_weight"], latent24=want["latent24"], ray_diff=want["ray_diff"].reshape(-1, 4), out=out)
+
+    o32, o64 = both(whole, sd, frame, g["pts"], g["q_sdf"], g["view"], g["fg_mask"])
+    assert o64["out"].dtype == torch.float64
+    for k in ("out_mask", "pix_weight", "latent24", "ray_diff", "out"):
+        hold("query:" + k, g[k].reshape(o32[k].shape), o32[k], o64[k], 2e-6 if k == "out" else TOL)
+
+
 def test_ibr_head_v2(golden, hot_weights):
     g = golden("ibr_head_v2")
     close(orc.ibr_head(dict(hot_weights), g["rgb_feats"], g["ray_diffs"], g["proj_mask"]), g["out"])
+
+
+def test_ibr_head_v2_under_the_criterion(golden, hot_weights):
+    """test_ibr_head_v2 under the criterion, floor 1e-6.  CPU machine and MI355X host alike: |o32 - golden| 4.47e-7, D 2.76e-7, H 5.74e-7,
+    D/H 0.48, bar 1.96e-6."""
+    g = golden("ibr_head_v2")
+    hold("ibr_head_v2", g["out"], *both(orc.ibr_head, dict(hot_weights), g["rgb_feats"], g["ray_diffs"], g["proj_mask"]), TOL)
 
 
 @pytest.mark.parametrize("tag,seed,hw,orbit,half", [("pass_8x8_s16", 3, 64, 8.0, False), ("pass_16x16_s24_bvv", 5, 64, 70.0, True),
@@ -170,6 +304,34 @@ def test_whole_pass(golden, hot_weights, tag, seed, hw, orbit, half):
     for k in ("tex_fg_fine", "depth_fine", "alpha_fine", "sdf"):  # behind the u = 1.0 tie of importance_sample (see above)
         assert_close_frac(out[k], g[k], 2e-6, 1e-3, k)
     assert out["depth_fine"].std() > 1e-3  # the view sees both hand and background
+
+
+@pytest.mark.parametrize("tag,seed,hw,orbit,half", [("pass_8x8_s16", 3, 64, 8.0, False), ("pass_16x16_s24_bvv", 5, 64, 70.0, True),
+                                                     ("pass_64x64_s64", 11, 256, 15.0, False)])
+def test_whole_pass_under_the_criterion(golden, hot_weights, tag, seed, hw, orbit, half):
+    """The three passes of test_whole_pass under the criterion: the fp32 pass, then its own samples re-marched in fp64 (remarch64); floor 2e-6,
+    coarse outputs with every element inside the bar, fine outputs under assert_close_frac's cap of 1e-3.  CPU machine and MI355X host
+    alike, D / H / D/H (elements above the bar where there are any):
+
+      output      | pass_8x8_s16             | pass_16x16_s24_bvv       | pass_64x64_s64
+      tex_fg      | 4.47e-6 / 4.42e-6 / 1.01 | 5.08e-6 / 5.02e-6 / 1.01 | 6.59e-6 / 6.44e-6 / 1.02
+      depth       | 1.82e-7 / 1.65e-7 / 1.10 | 3.02e-7 / 3.09e-7 / 0.98 | 8.00e-7 / 8.00e-7 / 1.00
+      alpha       | 5.96e-8 / 5.96e-8 / 1.00 | 5.96e-8 / 1.19e-7 / 0.50 | 1.19e-7 / 1.19e-7 / 1.00
+      tex_fg_fine | 4.47e-6 / 4.43e-6 / 1.01 | 5.06e-6 / 5.00e-6 / 1.01 | 7.43e-4 / 6.43e-6 / 116 (3 of 12288, 12 allowed)
+      depth_fine  | 1.61e-7 / 2.09e-7 / 0.77 | 7.11e-7 / 2.77e-7 / 2.57 | 6.84e-7 / 5.93e-7 / 1.15
+      alpha_fine  | 5.96e-8 / 1.19e-7 / 0.50 | 1.19e-7 / 1.19e-7 / 1.00 | 1.19e-7 / 1.19e-7 / 1.00
+      sdf         | 8.75e-7 / 8.30e-7 / 1.05 | 1.10e-6 / 9.63e-7 / 1.15 | 2.02e-4 / 3.26e-6 / 62 (1 of 4096, 4 allowed)
+
+    (pass_64x64_s64: one pixel of the reference's fine image sits behind a flipped importance sample, the case the cap is there for; the
+    oracle's fp32 image differs from the golden at the same pixel by the same 7.4e-4.)  The 64 x 64 x (64 + 64) pass stays: its fp64
+    re-march takes 5 s beside 7 s of fp32 pass on the CPU machine, 15 s together on the MI355X host."""
+    g = golden(tag)
+    sd = dict(hot_weights)
+    sd.update(_texframe_weights(golden))
+    frame = synth.make_frame(seed=seed, tar_h=hw, tar_w=hw, orbit_deg=orbit, half_mask=half)
+    S = int(g["S"])
+    out = orc.batch_render(sd, frame, int(g["level"]), g["stride_xy"].long()[None, None], S, S, want={})
+    hold_pass(tag, g, out, remarch64(sd, frame, out))
 
 
 def test_render_full_stitch(golden, hot_weights):
@@ -216,6 +378,30 @@ def test_training_pass_with_recorded_draws(golden, hot_weights):
     for k in ("tex_fg_fine", "depth_fine", "alpha_fine", "sdf"):
         close(out[k], g[k], 5e-6)
     assert (out["z"][..., 1:] > out["z"][..., :-1]).all() and out["z"].std() > 0  # stratified, still ascending
+
+
+def test_training_pass_with_recorded_draws_under_the_criterion(golden, hot_weights):
+    """test_training_pass_with_recorded_draws under the criterion: the fp64 re-march replays the same recorded draws; floors 2e-6 (coarse) and
+    5e-6 (fine), every element inside the bar.  CPU machine and MI355X host alike:
+
+      output      | |o32 - golden| | D       | H       | D/H  | bar
+      tex_fg      | 8.20e-8        | 1.10e-6 | 1.07e-6 | 1.03 | 3.24e-6
+      depth       | 2.38e-7        | 2.76e-7 | 2.91e-7 | 0.95 | 2.00e-6
+      alpha       | 1.19e-7        | 1.19e-7 | 5.96e-8 | 2.00 | 2.00e-6
+      tex_fg_fine | 2.38e-7        | 9.81e-7 | 9.57e-7 | 1.02 | 5.00e-6
+      depth_fine  | 2.38e-7        | 2.30e-7 | 2.79e-7 | 0.83 | 5.00e-6
+      alpha_fine  | 1.19e-7        | 1.19e-7 | 5.96e-8 | 2.00 | 5.00e-6
+      sdf         | 1.97e-7        | 8.52e-7 | 8.89e-7 | 0.96 | 5.00e-6"""
+    g = golden("pass_train_16x16_s16")
+    sd = dict(hot_weights)
+    sd.update(_texframe_weights(golden))
+    frame = _frame3()
+    S = int(g["S"])
+    grids, _ = orc.train_window(g["msk_in"][0], int(g["pick"].reshape(-1)[0]), 16, 16, 64, 64)
+    frame["out_hw"] = (16, 16)
+    draws = train_draws(g)
+    out = orc.batch_render(sd, frame, 5, None, S, S, grids=grids, draws=draws, want={})
+    hold_pass("pass_train_16x16_s16", g, out, remarch64(sd, frame, out, draws), 2e-6, 5e-6, None)  # (every element, as in the test above)
 
 
 def test_gt_gathers_of_an_eval_pass(golden, hot_weights):

@@ -9,8 +9,8 @@ rotation, a dropped translation or an x/y swap changes nothing.  The two poses o
   B    | -40,  20, -35          | 1100, 1100 | 140, 110
 
 (camera 1.05 from the mesh centre, looking at it, rolled about its optical axis).  Here: the oracle reproduces the reference's own query
-and whole pass on pose A (tests/golden/query_posed.npz, pass_16x16_s16_posed.npz, written by `python -m oracle.gen_golden --posed`) at the
-tolerances of tests/test_oracle_golden.py; its fp32 and fp64 evaluations agree on both poses; and the pose is visible in its outputs, so
+and whole pass on pose A (tests/golden/query_posed.npz, pass_16x16_s16_posed.npz, written by `python -m oracle.gen_golden --posed`) under the
+host-independent criterion of tests/oracle_criterion.py, floored at the tolerances of tests/test_oracle_golden.py; its fp32 and fp64 evaluations agree on both poses; and the pose is visible in its outputs, so
 that the GPU tests which take it as their reference cannot pass vacuously."""
 import math
 
@@ -18,10 +18,10 @@ import pytest
 import torch
 
 from oracle import vanerf_oracle as orc
-from tests.conftest import assert_close_frac
+from tests.oracle_criterion import both, hold, hold_pass, remarch64, ulp32
 from tests.test_hip_parity import _points_near_mesh as near_mesh_points  # (oracle/gen_golden.py draws query_posed.npz's points the same way)
 from tests.test_oracle_fp64 import cast, reference
-from tests.test_oracle_golden import _texframe_weights, close
+from tests.test_oracle_golden import _texframe_weights
 from vanerf_amd import synth
 
 POSES = (("A", 3), ("B", 5))  # pose name, frame seed (half of the source view masked in both)
@@ -117,33 +117,66 @@ def test_pose_source_camera_replaces_the_camera_and_nothing_else():
 
 
 def test_query_posed_vs_reference(golden, sd_full):
-    """VANeRF.query of the reference on pose A (tests/golden/query_posed.npz), at test_query_whole's tolerance."""
+    """VANeRF.query of the reference on pose A (tests/golden/query_posed.npz) under the criterion of tests/oracle_criterion.py, floor 2e-6
+    (test_query_whole's tolerance).  `extrin` is the golden's bit for bit.  KRT = K @ E is an fp32 matmul of the host: each entry must lie
+    of the golden's within 2 ulp of that entry's sum of absolute products |K||E| (observed: 7.6e-6 on an entry of 960, a quarter of that
+    bound), and the oracle is then fed the golden's KRT, so that it sees exactly the reference's inputs; points, q_sdf, q_vis, vert_vis and
+    validity stay bit-exact.  Against the golden directly `out` failed on every host but the writer's: the reference's own fp32 result is
+    1.1e-5 from the exact value.  CPU machine and MI355X host alike (torch 2.10, AVX512 kernels on both):
+
+      tensor | |o32 - golden| | D        | H        | D/H  | bar
+      out    | 1.812e-5       | 1.103e-5 | 2.036e-5 | 0.54 | 6.12e-5
+
+    `extrin`'s rotation transposed in the oracle's spatial encoder: D 0.13."""
     g = golden("query_posed")
     frame = posed_frame("A", 3)
-    assert torch.equal(frame["cam_in"]["KRT"], g["KRT"]) and torch.equal(frame["sp_data"]["extrin"], g["extrin"])
+    cam = frame["cam_in"]
+    assert torch.equal(frame["sp_data"]["extrin"], g["extrin"]) and torch.equal(cam["extrin"], g["extrin"])
+    sum_abs = cam["K"].double().abs() @ cam["extrin"].double().abs()  # |K||E|: an fp32 product in any order lands within a few ulp of it
+    krt_err = (cam["KRT"].double() - g["KRT"].double()).abs()
+    print(f"KRT: max |host - golden| {krt_err.max().item():.3e}, largest share of 2 ulp(|K||E|) {(krt_err / (2.0 * ulp32(sum_abs))).max().item():.2f}")
+    assert (krt_err <= 2.0 * ulp32(sum_abs)).all()
+    frame["cam_in"] = dict(cam, KRT=g["KRT"])  # from here on the oracle sees exactly the reference's inputs
     assert torch.equal(near_mesh_points(frame, N_POINTS, seed=2), g["pts"][0])
     q_sdf, q_vis, vert_vis = mesh_queries(frame, g["pts"][0])
     assert torch.equal(q_sdf, g["q_sdf"][0]) and torch.equal(q_vis, g["q_vis"][0, :, 0]) and torch.equal(vert_vis, g["vert_vis"][0, :, 0])
     view = torch.nn.functional.normalize(torch.ones_like(g["pts"]), dim=-1)
-    out, valid = orc.query(sd_full, g["pts"], frame["cam_in"], frame["targets"], frame["feat_geo"], frame["feat_tex"], g["vert_vis"],
-                           g["q_vis"], g["q_sdf"], frame["sp_data"], frame["img_in"], view, frame["src_foreground_mask"])
-    assert torch.equal(valid, g["valid"])
-    assert 0.05 < valid.float().mean() < 0.95
-    close(out, g["out"], 2e-6)
+
+    def whole(sd, frame, pts, q_sdf, view):
+        out, valid = orc.query(sd, pts, frame["cam_in"], frame["targets"], frame["feat_geo"], frame["feat_tex"], g["vert_vis"],
+                               g["q_vis"], q_sdf, frame["sp_data"], frame["img_in"], view, frame["src_foreground_mask"])
+        assert torch.equal(valid, g["valid"])
+        assert 0.05 < valid.float().mean() < 0.95
+        return out
+
+    o32, o64 = both(whole, sd_full, frame, g["pts"], g["q_sdf"], view)
+    assert o32.dtype == torch.float32 and o64.dtype == torch.float64
+    hold("query_posed:out", g["out"], o32, o64, 2e-6)
 
 
 def test_whole_pass_posed_vs_reference(golden, sd_full):
-    """VANeRF.batch_render_pifu_nerf of the reference on pose A, 16 x 16 rays, 16 + 16 samples, at test_whole_pass's tolerances."""
+    """VANeRF.batch_render_pifu_nerf of the reference on pose A, 16 x 16 rays, 16 + 16 samples, under the criterion: the fp32 pass, then its
+    own samples re-marched in fp64 (remarch64); floor 2e-6 (test_whole_pass's tolerance), coarse outputs with every element inside the bar,
+    fine outputs -- behind the u = 1.0 tie of importance_sample (tests/test_oracle_golden.py) -- under assert_close_frac's cap of 1e-3, of
+    which the reference needs none here.  CPU machine and MI355X host alike:
+
+      output      | |o32 - golden| | D       | H       | D/H  | bar
+      tex_fg      | 4.26e-6        | 4.52e-6 | 5.17e-6 | 0.87 | 1.56e-5
+      depth       | 7.15e-7        | 4.77e-7 | 3.71e-7 | 1.29 | 2.00e-6
+      alpha       | 5.96e-8        | 5.96e-8 | 5.96e-8 | 1.00 | 2.00e-6
+      tex_fg_fine | 4.35e-6        | 4.44e-6 | 5.10e-6 | 0.87 | 1.54e-5
+      depth_fine  | 7.15e-7        | 1.06e-6 | 3.94e-7 | 2.69 | 2.00e-6
+      alpha_fine  | 1.19e-7        | 1.19e-7 | 5.96e-8 | 2.00 | 2.00e-6
+      sdf         | 3.17e-6        | 2.38e-6 | 1.99e-6 | 1.19 | 5.98e-6
+
+    (depth_fine: D also holds the reference's own, slightly different fine depths; the floor covers it.)"""
     g = golden("pass_16x16_s16_posed")
     frame = posed_frame("A", 3)
     S = int(g["S"])
     assert (S, int(g["level"]), g["stride_xy"].tolist()) == (16, 3, [1, 2])
-    out = orc.batch_render(sd_full, frame, int(g["level"]), g["stride_xy"].long()[None, None], S, S)
+    out = orc.batch_render(sd_full, frame, int(g["level"]), g["stride_xy"].long()[None, None], S, S, want={})
     assert torch.equal(out["vert_vis"], g["vert_vis"])
-    for k in ("tex_fg", "depth", "alpha"):
-        close(out[k], g[k], 2e-6)
-    for k in ("tex_fg_fine", "depth_fine", "alpha_fine", "sdf"):  # behind the u = 1.0 tie of importance_sample (tests/test_oracle_golden.py)
-        assert_close_frac(out[k], g[k], 2e-6, 1e-3, k)
+    hold_pass("pass_16x16_s16_posed", g, out, remarch64(sd_full, frame, out), 2e-6, 2e-6, 1e-3)
     assert out["depth_fine"].std() > 1e-3 and 0.05 < out["coarse"]["vert_vis"].mean() < 0.95
 
 
