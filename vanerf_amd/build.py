@@ -7,7 +7,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "lib", "libvanerf_hip.so")
-SOURCES = ["api.cpp", "weights_pack.cpp", "pass.cpp", "query_kernel.hip", "render_kernels.hip", "mesh_kernels.hip", "mesh_accel_query.hip", "mesh_accel_build.hip", "train_kernels.hip", "query_backward.hip", "weights_update.hip", "weight_products.hip", "vis_render.hip", "image_metrics.hip", "mask_at_box.hip", "vertex_products.hip", "surface.hip", "surface_lines.hip", "volume_render.hip", "volume_surface.hip", "pose_warp.hip"]
+SOURCES = ["api.cpp", "weights_pack.cpp", "pass.cpp", "query_kernel.hip", "query_order.hip", "render_kernels.hip", "mesh_kernels.hip", "mesh_accel_query.hip", "mesh_accel_build.hip", "train_kernels.hip", "query_backward.hip", "weights_update.hip", "weight_products.hip", "vis_render.hip", "image_metrics.hip", "mask_at_box.hip", "vertex_products.hip", "surface.hip", "surface_lines.hip", "volume_render.hip", "volume_surface.hip", "pose_warp.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
          "-Wall", "-Wextra", "-Wno-unused-parameter"]
 # per-file flags.  query_kernel.hip: MFMA results are allocated in VGPRs (the chained layers read every accumulator element once with VALU
@@ -15,6 +15,11 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=o
 # stays off (it packs adjacent f32 multiplies / adds into v_pk_* instructions, which cost more beside MFMAs than the scalar pairs).
 FILE_FLAGS = {"query_kernel.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-slp-vectorize"],
               "query_backward.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-slp-vectorize"],
+              # the validity partition was built with the pair while it shared query_kernel.hip; it has no MFMA, but without -fno-slp-vectorize
+              # order_count_kernel packs the projection's multiplies and adds (249 -> 258 instructions, 21 -> 27 VGPRs; scan and scatter are
+              # the same either way), and its arithmetic stays what query_kernel's is.  With the flags all three are instruction for instruction
+              # what they were.
+              "query_order.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-slp-vectorize"],
               # mesh_query_accel_kernel sits exactly at 128 registers (four waves per SIMD): loop-invariant address arithmetic goes back into the
               # work loop instead of being parked in scratch (7 spilled VGPRs without the flag; scratch fails the build, _check_no_scratch).
               # No SLP vectoriser here either: a v_pk_mul_f32 / v_pk_add_f32 takes the issue slots of two scalar ops on gfx950

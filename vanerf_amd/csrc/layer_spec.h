@@ -1,5 +1,5 @@
 // layer_spec.h -- the one description of the per-sample network stack shared by the host-side
-// weight packer (weights_pack.cpp) and the device kernel (query_kernel.hip).
+// weight packer (weights_pack.cpp) and the device kernel (query_kernel.hip; its split-bf16 LDS map and ring: bf16x3_ring.h).
 //
 // Every dense layer y = W x (+ b) of the reference's per-sample networks
 //   GeoVisFusion   src/networks.py:43-106      MLPUNetFusion  src/utils.py:609-649, 781-880

@@ -1,5 +1,6 @@
 // mfma_chain.h -- the fp32 MFMA layer runner shared by query_kernel.hip (forward, fp32 mode) and query_backward.hip (training):
 // a chain of v_mfma_f32_32x32x2_f32 whose A fragments stream from L2 through a register ring (layer_spec.h describes the layout).
+// bf16x3_ring.h is its split-bf16 counterpart and sample_math.h takes f32x16 from here.
 #pragma once
 #include <utility>
 

@@ -1,5 +1,5 @@
 // query_backward.hip -- training: the fused backward pass of the per-sample networks, the reverse of
-// query_kernel.hip (reference: the autograd of VANeRF.query + query_color, src/model.py:748-957; networks src/networks.py:75-106, 281-293;
+// query_kernel.hip's stages (reference: the autograd of VANeRF.query + query_color, src/model.py:748-957; networks src/networks.py:75-106, 281-293;
 // src/utils.py:633-649, 709-719, 744-779, 822-880).
 //
 // Forward, D[out][sample] = W X keeps the sample on the lane and hands the accumulator registers of one layer to the next as its B

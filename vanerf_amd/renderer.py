@@ -931,7 +931,7 @@ def render_pass(weights, frame, cam_tar, bounds, x0, y0, step, nx, ny, sample_pe
 
     def eval_func(raw, valid, noise):
         """src/model.py:1140-1160 on the kernel's raw outputs [sdf_pred, rad, r, g, b] (vanerf_eval_func: the arithmetic of the kernel's own
-        epilogue, csrc/query_kernel.hip, so the same bits; one launch instead of eight element-wise ones)."""
+        epilogue, store_sample in csrc/query_kernel.hip, so the same bits; one launch instead of eight element-wise ones)."""
         n = raw.shape[0]
         out = torch.empty(n, 5, dtype=torch.float32, device=raw.device)
         check(lib.vanerf_eval_func(_ptr(raw, torch.float32), _ptr(valid, torch.uint8), None, None, None, _ptr(noise, torch.float32), 1, 0, n,
