@@ -16,10 +16,15 @@ ap.add_argument("--rows", type=int, default=512)
 ap.add_argument("--mode", type=int, default=0, help="0 = fp32 MFMA, 1 = split-bf16 x3")
 ap.add_argument("--order", type=int, default=1, help="1: work order from the validity partition (what render_pass does), 0: natural order")
 ap.add_argument("--vertex-products", type=int, default=1, help="mode 1: 1 = the lean kernel on the frame's table of per-vertex products (the default path; VANERF_LEAN_STREAM=0: the hoisted kernel), 0 = the un-hoisted kernel")
+ap.add_argument("--mask", choices=["frame", "zero", "one"], default="frame",
+                help="the source view's foreground mask: the frame's own, all zero (every sample invalid: the all-invalid short path alone), all one "
+                     "(valid wherever the sample projects into the source view)")
 args = ap.parse_args()
 sd = synth.make_full_weights(0)
 frame = synth.make_frame(seed=11, tar_h=512, tar_w=334, orbit_deg=15.0)
 fd = synth.to_device(frame, "cuda")
+if args.mask != "frame":
+    fd["src_foreground_mask"] = torch.full_like(fd["src_foreground_mask"], 0.0 if args.mask == "zero" else 1.0)
 sdd = {k: v.cuda() for k, v in sd.items() if k.startswith("tex_vis_fusion.")}
 fdat = R.FrameData(sdd, fd["img_in"], fd["feat_geo"], fd["feat_tex"], fd["src_foreground_mask"], fd["cam_in"], fd["targets"], fd["sp_data"])
 w = R.PackedWeights(sd, mode=args.mode)

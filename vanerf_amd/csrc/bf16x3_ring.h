@@ -61,6 +61,18 @@ static_assert(LDS_CTRL + 8u + 2u * 4u * RING_WAVES <= LDS_LAT0 && LDS_LAT0 + 128
 static_assert(DYN_LDS_BYTES<0> <= 160u * 1024u && DYN_LDS_BYTES<1> <= DYN_LDS_BYTES<0> && DYN_LDS_BYTES<2> <= 160u * 1024u,
               "key points + control words + ring + resident fragments (+ bias table) must fit the CU's 160 KB");
 static_assert(LDS_BIAS<2> % 16u == 0, "the bias table is read 16 bytes at a time");
+// The SHORT map, of the short-only kernel (query_short_kernel: all-invalid groups only, twelve waves on one copy).  It is the LEVEL map with
+// holes: every region the short path reads keeps the address it has in the full kernel's map, so the stages instantiate unchanged (same
+// functions, same LDS offsets, same bits), and what the short path never reads is never filled --
+//   [672, 768)  control words: unused           [768, 896)  the constant latent            [0, 672), [1024, 1024 + 32 KB)  key points, ring: not filled
+//   [SHORT_LDS_RES, + SHORT_RES_DW * 4)  resident fragments of L_IBR and the four TexVisFusion layers (lean: 16 + 78 KB; the head layers in
+//   front of them are not filled)                [LDS_BIAS, + 1280)  lean kernel: the bias table (L_IBR's row starts the constant latent)
+// The block's allocation stays DYN_LDS_BYTES<LEVEL>: one block per CU either way, the holes cost nothing.
+constexpr int SHORT_WAVES = 12; // waves of the short-only kernel's one block per CU: three per SIMD (168 registers; four would need 128)
+template <int LEVEL> constexpr unsigned SHORT_BASE_DW = layer_offset_b(L_IBR, LEVEL);
+template <int LEVEL> constexpr unsigned SHORT_RES_DW = layer_offset_b(NUM_LAYERS, LEVEL) - SHORT_BASE_DW<LEVEL>;
+template <int LEVEL> constexpr unsigned SHORT_LDS_RES = LDS_RES + (SHORT_BASE_DW<LEVEL> - RES_BASE_DW<LEVEL>) * 4u;
+static_assert(L_IBR >= LDS_FIRST<2> && SHORT_RES_DW<2> == (16u + 78u) * 256u, "the short path's layers are resident in the full map");
 extern __shared__ __attribute__((aligned(16))) u32x4 s_dyn[];
 typedef __attribute__((address_space(3))) u32x4 lds_u32x4_t;
 typedef __attribute__((address_space(3))) unsigned lds_u32_t;

@@ -13,7 +13,8 @@
 // from vanerf_mesh_query_accel.  query_kernel<1, false, 1> is the HOISTED split-bf16 kernel: three first layers start from the per-vertex
 // products of vertex_products.hip and run their per-sample k-steps only (layer_spec.h).  query_kernel<1, false, 2> is the LEAN kernel: the
 // hoisted one on the lean stream -- two linear layers folded into their consumers, five accumulators started from a bias table, one k-pair
-// less in the TexVisFusion input, the two last head layers resident (layer_spec.h).
+// less in the TexVisFusion input, the two last head layers resident (layer_spec.h).  With a validity partition it hands the all-invalid groups
+// behind the partition's boundary to query_short_kernel<2>, a second launch in a shape of its own (three waves per SIMD; same stages, same bits).
 //
 // The file: QueryParams, the fp32 lane with its spill plumbing, the mode dispatch of the layer runners (mfma_chain.h fp32, bf16x3_ring.h
 // split-bf16), the stages of a round in the order they run, the kernel -- its body is the round's protocol and the sequence of stages --,
@@ -177,15 +178,19 @@ template <int MODE, int NSTEPS, int NB, class TC> __device__ __forceinline__ flo
 // The six per-sample inputs of a group are fetched one group ahead (its index is known from the early claim): their HBM latency
 // is otherwise the first thing a group waits for.
 struct SampleIn { float px, py, pz, sdf; int knn; unsigned char vis; };
+__device__ __forceinline__ SampleIn fetch_at(const QueryParams& P, long long sc) // the inputs of sample sc
+{
+    SampleIn in;
+    in.px = P.pts[3 * sc]; in.py = P.pts[3 * sc + 1]; in.pz = P.pts[3 * sc + 2];
+    in.sdf = P.qsdf[sc]; in.knn = P.knn_in[sc]; in.vis = P.qvis[sc];
+    return in;
+}
 __device__ __forceinline__ SampleIn fetch_sample(const QueryParams& P, unsigned grp, int j)
 {
     const long long sr = (long long)grp * 32 + j;
     long long sc = sr < P.n ? sr : P.n - 1; // also covers a claim beyond the last group (never used)
     if (P.order) sc = P.order[sc];
-    SampleIn in;
-    in.px = P.pts[3 * sc]; in.py = P.pts[3 * sc + 1]; in.pz = P.pts[3 * sc + 2];
-    in.sdf = P.qsdf[sc]; in.knn = P.knn_in[sc]; in.vis = P.qvis[sc];
-    return in;
+    return fetch_at(P, sc);
 }
 
 // Block prologue of the split-bf16 kernel, once per launch (it is persistent).  The key points (the fp32 kernel reads them through the scalar cache) ...
@@ -194,14 +199,19 @@ __device__ __forceinline__ void key_points_to_lds(const VanerfFrame& F)
     if (threadIdx.x < 2 * PE_KPT_PER_HALF) s_dyn[LDS_KPT / 16 + threadIdx.x] = reinterpret_cast<const u32x4*>(F.kpt_cam)[threadIdx.x];
 }
 // ... one copy of the resident fragments per block (256 blocks x 126 KB from L2), the lean kernel's bias table and phase 0 of the ring
-template <int LEVEL> __device__ __forceinline__ void fill_lds(const QueryParams& P, WRsrc W, int lane, unsigned wv_u)
+// (BASE_DW, DW, LDS_AT: the part of the stream that stays and where -- the full map's, or the SHORT map's; THREADS: the block's)
+template <int LEVEL, unsigned BASE_DW, unsigned DW, unsigned LDS_AT, unsigned THREADS> __device__ __forceinline__ void resident_to_lds(const QueryParams& P)
 {
-    const u32x4* __restrict__ src = reinterpret_cast<const u32x4*>(P.w) + RES_BASE_DW<LEVEL> / 4;
-    for (unsigned i = threadIdx.x; i < RES_DW<LEVEL> / 4; i += 64 * RING_WAVES) s_dyn[LDS_RES / 16 + i] = src[i];
+    const u32x4* __restrict__ src = reinterpret_cast<const u32x4*>(P.w) + BASE_DW / 4;
+    for (unsigned i = threadIdx.x; i < DW / 4; i += THREADS) s_dyn[LDS_AT / 16 + i] = src[i];
     if constexpr (LEVEL == 2) { // the bias table stands behind the stream's slack (layer_spec.h); here it goes right behind the resident fragments
         const u32x4* __restrict__ bsrc = reinterpret_cast<const u32x4*>(P.w) + (layer_offset_b(NUM_LAYERS, LEVEL) + STREAM_SLACK_DW) / 4;
         if (threadIdx.x < BIAS_TABLE_FLOATS / 4) s_dyn[LDS_BIAS<LEVEL> / 16 + threadIdx.x] = bsrc[threadIdx.x];
     }
+}
+template <int LEVEL> __device__ __forceinline__ void fill_lds(const QueryParams& P, WRsrc W, int lane, unsigned wv_u)
+{
+    resident_to_lds<LEVEL, RES_BASE_DW<LEVEL>, RES_DW<LEVEL>, LDS_RES, 64 * RING_WAVES>(P);
     // phase 0 of the ring, once: every full round re-issues it for its successor (see phase_begin)
     const LAddr la0 = make_laddr(lane, wv_u);
     ring_dma<0>(W, la0);
@@ -665,10 +675,16 @@ __device__ __forceinline__ void store_sample(const QueryParams& P, bool live, in
 // zero (0 * x), the density head is masked out by eval_func and only the colour branch (fed by the bias of
 // ibr_compress) survives.  When ALL 32 samples of the wave are such samples, GeoVisFusion, mlp_geo.layers1 and the head
 // (82 % of the MFMAs) are skipped -- same bits, wave-uniform branch.  With real foreground masks most samples are.
-template <int MODE, bool SPILL = false, int LEVEL = 0>
+// The hand-over (HANDOVER: the launch has a validity partition and query_short_kernel stands behind it on the stream).  The partition puts the
+// all-invalid groups behind the others, so behind the first all-invalid round of ANY block every round is all-invalid.  A block that meets such
+// a round records its base in the second word of the launch's queue -- atomicMax of the complement: the word ends as ~(smallest base) and stays 0
+// when no block met one -- and leaves; all of its waves leave together (the decision is block-uniform), so the barriers stay matched.  Every
+// round in front of the smallest recorded base was claimed by a block that ran it in full; query_short_kernel runs every group from that base on.
+template <int MODE, bool SPILL = false, int LEVEL = 0, bool HANDOVER = false>
 __global__ __launch_bounds__(64 * WPB<MODE>, SPILL ? WAVES_PER_SIMD_SPILL : WAVES_PER_SIMD) void query_kernel(const QueryParams P)
 {
     static_assert(!SPILL || MODE == 0, "the training spill runs on the fp32 kernel");
+    static_assert(!HANDOVER || LEVEL == 2, "the short-only kernel exists at the lean level");
     static_assert(LEVEL >= 0 && LEVEL <= 2 && (LEVEL == 0 || MODE == 1), "only the split-bf16 kernel has a hoisted and a lean variant");
     constexpr bool HOIST = LEVEL >= 1;
     constexpr int WAVES_PER_BLOCK = WPB<MODE>;
@@ -739,6 +755,12 @@ __global__ __launch_bounds__(64 * WPB<MODE>, SPILL ? WAVES_PER_SIMD_SPILL : WAVE
 #pragma unroll
         for (int k = 0; k < WAVES_PER_BLOCK; ++k) anyv |= s_valid(par, k);
         const bool any_valid = SPILL || __builtin_amdgcn_readfirstlane((int)anyv) != 0; // (spill mode: every group writes every row)
+        if constexpr (HANDOVER) {
+            if (!any_valid) { // this round and every round behind it belong to query_short_kernel
+                if (threadIdx.x == 0) atomicMax(P.queue + 1, ~base_cur);
+                break;
+            }
+        }
         par ^= 1u;
         if (threadIdx.x == 0) pending = atomicAdd(P.queue, (unsigned)WAVES_PER_BLOCK);
         in_next = fetch_sample(P, base_next + wv, j);
@@ -823,6 +845,73 @@ __global__ __launch_bounds__(64 * WPB<MODE>, SPILL ? WAVES_PER_SIMD_SPILL : WAVE
 #endif
 }
 
+// The short-only kernel: the all-invalid groups a HANDOVER launch of query_kernel<1, false, LEVEL> left behind, from group ~queue[1] on.  It is
+// the round of query_kernel with any_valid == false as a constant -- the same stages with the same arguments in the same order, so the same bits
+// -- in a shape of its own: nothing of the full path is compiled in, so the stages fit 168 registers and TWELVE waves share the block's one
+// LDS copy (the SHORT map, bf16x3_ring.h) -- three waves per SIMD to hide the gathers and the dependent ds_read_b128s of a latency-bound path,
+// where the full kernel's shape has two, which run the same gathers at the same moment.  (Sixteen waves at 128 registers put 46 of them in
+// scratch: TexVisFusion's second layer holds 48 accumulators, 32 row values and its fragments at once.)  No ring, no phase barriers, no queue:
+// the range is known at launch and its groups cost the same, so they are dealt statically -- wave w of block b takes groups
+// start + 12 (b + k gridDim) + w.
+// Every group it executes is a short group (the counter bench.py prices FLOPs with): with the full kernel's count, the parent's number.
+template <int LEVEL>
+__global__ __launch_bounds__(64 * SHORT_WAVES) void query_short_kernel(const QueryParams P)
+{
+    static_assert(LEVEL == 2, "the lean level (the hoisted level's stages need 5 registers more than three waves per SIMD have: it keeps the in-kernel short path)");
+    const unsigned word = P.queue[1];
+    if (word == 0u) return; // no block of the full kernel met an all-invalid round
+    const long long ngroups = (P.n + 31) / 32;
+    const long long first = (long long)(~word) + (long long)SHORT_WAVES * blockIdx.x; // the block's first group
+    if (first >= ngroups) return; // no work: before the LDS fill
+    const VanerfFrame& F = P.f;
+    const WRsrc W = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(P.w), 0, P.wbytes, 0x00020000);
+    const unsigned wv_u = (unsigned)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    resident_to_lds<LEVEL, SHORT_BASE_DW<LEVEL>, SHORT_RES_DW<LEVEL>, SHORT_LDS_RES<LEVEL>, 64 * SHORT_WAVES>(P);
+    __syncthreads();
+    short_path_latent<LEVEL>(W, (int)(threadIdx.x & 63), wv_u);
+    __syncthreads();
+    unsigned short_groups = 0;
+    long long g = first + wv_u;
+    // the slot's sample (a hand-over launch has a partition): fetched one group ahead -- the index only, one register; the full kernel's six
+    // inputs ahead do not fit the register budget here, and the waves of a SIMD hide the one level of latency that is left
+    auto slot_sample = [&](long long grp, int j) -> int {
+        const long long sr = (grp < ngroups ? grp : ngroups - 1) * 32 + j;
+        return P.order[sr < P.n ? sr : P.n - 1];
+    };
+    int s_next = slot_sample(g, (int)(threadIdx.x & 31));
+    for (; g < ngroups; g += (long long)SHORT_WAVES * gridDim.x) {
+        const int lane = lane_id_fresh(), j = lane & 31, h = lane >> 5;
+        const float one_h0 = h ? 0.0f : 1.0f;
+        const LAddr la = make_laddr(lane, wv_u);
+        const bool live = g * 32 + j < P.n;
+        const int s = s_next; // (a lane beyond n: the last slot's sample, not stored)
+        const SampleIn in = fetch_at(P, s);
+        s_next = slot_sample(g + (long long)SHORT_WAVES * gridDim.x, j);
+        __builtin_amdgcn_sched_barrier(0x000F);
+        const float px = in.px, py = in.py, pz = in.pz;
+        const float q_vis = in.vis ? 1.0f : 0.0f;
+        const Projected pr = project_and_mask(F, P.wm1[0], P.hm1[0], px, py, pz);
+        const float x = pr.x, y = pr.y, mask = pr.mask;
+        const Bilin bi = bilin_setup(x, y, F.hi, F.wi, P.wm1[0], P.hm1[0]);
+        const int nn_idx = in.knn;
+        const int tw_idx = nn_idx >= VANERF_NV_HAND ? nn_idx - VANERF_NV_HAND : nn_idx + VANERF_NV_HAND;
+        const float vis_nn = ld_off<float>(F.vert_vis, 4u * nn_idx), vis_tw = ld_off<float>(F.vert_vis, 4u * tw_idx);
+        float row[32], qi[4], qt[8];
+        f32x16 pool[4], head[1];
+        zero<4>(pool);
+        zero<1>(head);
+        if (lane == 0) ++short_groups;
+        tex_gathers(P, x, y, bi, h, nn_idx, tw_idx, row, qi, qt);
+        f32x16 lat[1];
+        RingB<3> r_ta;
+        ibr_compress<1, LEVEL>(W, la, h, one_h0, false, pool, lat, r_ta);
+        f32x16 rgb[1];
+        tex_vis_fusion<1, LEVEL>(W, la, P.vp, h, nn_idx, q_vis, vis_nn, vis_tw, row, qi, qt, lat, r_ta, rgb);
+        store_sample(P, live, h, s, mask, head, rgb);
+    }
+    if (P.short_groups && lane_id_fresh() == 0 && short_groups) atomicAdd(P.short_groups, (unsigned long long)short_groups);
+}
+
 // ---- what the launch entries share: argument checks, the QueryParams of a launch, grid sizing, the launch itself ----
 void check_queue_word(const char* who, const void* queue_word)
 {
@@ -852,9 +941,9 @@ QueryParams query_params(const VanerfFrame& f, const VanerfWeights& w, Stream s,
 // cycles to the MFMA time), so the second wave does not hide VALU work behind MFMAs; what it hides is load latency and the in-order issue gaps
 // of its partner --, split-bf16 ONE 8-wave block (it owns the CU's LDS), spill build one 4-wave block (it takes the whole register file).
 struct QueryLaunch { void (*kernel)(QueryParams); int wpb, blocks_per_cu; unsigned lds_bytes; };
-template <int MODE, bool SPILL = false, int LEVEL = 0> QueryLaunch query_launch()
+template <int MODE, bool SPILL = false, int LEVEL = 0, bool HANDOVER = false> QueryLaunch query_launch()
 {
-    return {query_kernel<MODE, SPILL, LEVEL>, WPB<MODE>, (SPILL ? WAVES_PER_SIMD_SPILL : WAVES_PER_SIMD) * 4 / WPB<MODE>, MODE == 1 ? DYN_LDS_BYTES<LEVEL> : 0u};
+    return {query_kernel<MODE, SPILL, LEVEL, HANDOVER>, WPB<MODE>, (SPILL ? WAVES_PER_SIMD_SPILL : WAVES_PER_SIMD) * 4 / WPB<MODE>, MODE == 1 ? DYN_LDS_BYTES<LEVEL> : 0u};
 }
 
 // persistent grid: one block per WPB groups, at most what the device holds at once (the blocks claim their groups from the queue word)
@@ -867,14 +956,29 @@ long long query_blocks(const QueryLaunch& L, int64_t n)
     return std::min<long long>((ngroups + L.wpb - 1) / L.wpb, (long long)cus * L.blocks_per_cu);
 }
 
-void launch_query(const QueryLaunch& L, long long blocks, QueryParams& P, void* queue_word, void* stream)
+void launch_kernel(const QueryLaunch& L, long long blocks, const QueryParams& P, void* stream)
 {
-    P.queue = static_cast<unsigned*>(queue_word); // the caller's word: no launch shares a queue head with another (any number in flight, any streams)
-    HIP_CHECK(hipMemsetAsync(P.queue, 0, 8, (hipStream_t)stream));
     // the opt-in above 64 KB of dynamic LDS is per device: set on every call (cheap), as vanerf_mesh_query_accel does
     if (L.lds_bytes) HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(L.kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds_bytes));
     hipLaunchKernelGGL(L.kernel, dim3((unsigned)blocks), dim3(64 * L.wpb), L.lds_bytes, (hipStream_t)stream, P);
     HIP_CHECK(hipGetLastError());
+}
+
+// The launch's queue word is 8 bytes, zeroed here: the first 32-bit word is the work-queue head, the second the hand-over word of a HANDOVER
+// launch (no other kernel reads or writes it: without a hand-over it stays 0).
+void launch_query(const QueryLaunch& L, long long blocks, QueryParams& P, void* queue_word, void* stream)
+{
+    P.queue = static_cast<unsigned*>(queue_word); // the caller's word: no launch shares a queue head with another (any number in flight, any streams)
+    HIP_CHECK(hipMemsetAsync(P.queue, 0, 8, (hipStream_t)stream));
+    launch_kernel(L, blocks, P, stream);
+}
+
+// The short-only kernel behind a HANDOVER launch, same stream, same parameters: launched without knowing whether, or from where, there is work
+// for it (no host synchronisation) -- it reads the hand-over word; 0 ends it at once.  One 12-wave block per CU, at most one per 12 groups.
+template <int LEVEL> void launch_short(const QueryParams& P, void* stream)
+{
+    const QueryLaunch L = {query_short_kernel<LEVEL>, SHORT_WAVES, 1, DYN_LDS_BYTES<LEVEL>};
+    launch_kernel(L, query_blocks(L, P.n), P, stream);
 }
 
 // VANERF_LEAN_STREAM (read at every launch, for tests and A/B runs): 0 = a bf16x3 handle with a table of vertex products runs the hoisted kernel
@@ -882,6 +986,14 @@ void launch_query(const QueryLaunch& L, long long blocks, QueryParams& P, void* 
 bool lean_stream_enabled()
 {
     const char* e = std::getenv("VANERF_LEAN_STREAM");
+    return !(e && e[0] == '0' && !e[1]);
+}
+
+// VANERF_SHORT_KERNEL (read at every launch, for tests and A/B runs): 0 = a launch with a validity partition stays ONE launch, its all-invalid
+// groups on the short path inside the full kernel.  Unset or anything else: the hand-over to query_short_kernel.
+bool short_kernel_enabled()
+{
+    const char* e = std::getenv("VANERF_SHORT_KERNEL");
     return !(e && e[0] == '0' && !e[1]);
 }
 
@@ -910,8 +1022,14 @@ extern "C" int vanerf_query_samples(const VanerfWeights* w, const VanerfFrame* f
         const Stream s = !hoist ? forward_stream(w->mode) : w->stream[STREAM_LEAN] && lean_stream_enabled() ? STREAM_LEAN : STREAM_HOISTED;
         QueryParams P = query_params(f, *w, s, pts, query_sdf, query_vis, knn_idx, raw, n, out);
         P.noise = noise; P.order = order; P.valid = valid; P.short_groups = w->stats; P.vp = vertex_products;
-        const QueryLaunch L = s == STREAM_LEAN ? query_launch<1, false, 2>() : s == STREAM_HOISTED ? query_launch<1, false, 1>() : s == STREAM_BF16X3 ? query_launch<1>() : query_launch<0>();
+        // with a partition (`order`: vanerf_query_order's, the all-invalid groups last) the lean kernel hands those groups over
+        const bool handover = order && s == STREAM_LEAN && short_kernel_enabled();
+        const QueryLaunch L = s == STREAM_LEAN      ? (handover ? query_launch<1, false, 2, true>() : query_launch<1, false, 2>())
+                              : s == STREAM_HOISTED ? query_launch<1, false, 1>()
+                              : s == STREAM_BF16X3  ? query_launch<1>()
+                                                    : query_launch<0>();
         launch_query(L, query_blocks(L, n), P, queue_word, stream);
+        if (handover) launch_short<2>(P, stream);
     });
 }
 
