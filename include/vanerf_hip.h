@@ -257,7 +257,13 @@ int vanerf_knn1(const float* verts4, int nv, const float* pts, int64_t n, int32_
  *         gathered table rows and runs their per-sample k-steps only, reads the two folded layers' products from the packed weights and starts
  *         five more accumulators from the bias table (outputs within 2e-5 of the un-hoisted kernel's: summation order).  The environment
  *         variable VANERF_LEAN_STREAM=0, read at every launch, selects the hoisted kernel on the hoisted stream instead (the lean kernel's
- *         predecessor, for A/B runs).  NULL selects the un-hoisted kernel.                                                                    */
+ *         predecessor, for A/B runs).  NULL selects the un-hoisted kernel.
+ *         Where the frame's 64-channel geometry map has at most 1024 texels (h0 * w0; 32 x 32 for a 256 x 256 source) the table also holds the
+ *         per-texel products of that map and the launch runs the texel kernel on the handle's texel stream (the library's stream 8, with a
+ *         copy of the bias table, 9, behind it; 7 is no stream; neither has a name in the enum above): the lean kernel with the pixel
+ *         feature's share of geo_vis_fusion.fconv_at.0 / fconv_ated.0 sampled from the table instead of multiplied per sample (outputs
+ *         within 2e-5 of the lean kernel's: summation order).  A larger map runs the lean kernel.  VANERF_TEXEL_PRODUCTS=0, read at every
+ *         launch, selects the lean kernel as well (its bits are what they were).                                                            */
 int vanerf_query_samples(const VanerfWeights* w, const VanerfFrame* frame, const float* pts, const float* query_sdf,
                          const uint8_t* query_vis, const int32_t* knn_idx, const float* noise, const int32_t* order, int raw, int64_t n,
                          float* out, uint8_t* valid, void* queue_word /* as for vanerf_mesh_query_accel */, const float* vertex_products,
@@ -268,7 +274,10 @@ int vanerf_query_samples(const VanerfWeights* w, const VanerfFrame* frame, const
  * sample's 1-NN vertex; their products are a fixed vector per vertex: table = [A0 | N0 | T0 | P] (vanerf_amd/csrc/layer_spec.h), fp32, evaluated in
  * fp32 in a fixed order (two builds give the same bits).  table == NULL: returns the number of floats needed (> 0).  Otherwise one launch on
  * `stream` into table[cap_floats] (16-byte aligned; no allocation, no host synchronisation), returns 0; < 0: error.  The table belongs to
- * (handle contents, frame): rebuild it after vanerf_weights_update -- the library keeps no cache.                                          */
+ * (handle contents, frame): rebuild it after vanerf_weights_update -- the library keeps no cache.
+ * Behind P the table has room for the per-texel products of frame->geo0 with the pixel columns of the two geo layers, [GA | GM], 1024 texels
+ * of 16 + 64 floats (a second launch on `stream`; 1.5 MB + 320 KB in all -- size the table by the NULL call, never by a constant).  A frame
+ * with h0 * w0 > 1024 leaves that part unwritten, and vanerf_query_samples / vanerf_render_pass then run the lean kernel for it.          */
 int vanerf_vertex_products(const VanerfWeights* w, const VanerfFrame* frame, float* table, int64_t cap_floats, void* stream);
 
 /* Validity partition for vanerf_query_samples: order[N] = the samples whose projection hits the source view and its foreground mask

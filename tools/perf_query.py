@@ -15,7 +15,7 @@ ap.add_argument("--iters", type=int, default=5)
 ap.add_argument("--rows", type=int, default=512)
 ap.add_argument("--mode", type=int, default=0, help="0 = fp32 MFMA, 1 = split-bf16 x3")
 ap.add_argument("--order", type=int, default=1, help="1: work order from the validity partition (what render_pass does), 0: natural order")
-ap.add_argument("--vertex-products", type=int, default=1, help="mode 1: 1 = the lean kernel on the frame's table of per-vertex products (the default path; VANERF_LEAN_STREAM=0: the hoisted kernel), 0 = the un-hoisted kernel")
+ap.add_argument("--vertex-products", type=int, default=1, help="mode 1: 1 = the texel kernel on the frame's table of per-vertex and per-texel products (the default path; VANERF_TEXEL_PRODUCTS=0: the lean kernel, VANERF_LEAN_STREAM=0: the hoisted kernel), 0 = the un-hoisted kernel")
 ap.add_argument("--mask", choices=["frame", "zero", "one"], default="frame",
                 help="the source view's foreground mask: the frame's own, all zero (every sample invalid: the all-invalid short path alone), all one "
                      "(valid wherever the sample projects into the source view)")

@@ -1,6 +1,7 @@
-"""Two builds of the library compute the same bits in the per-sample kernels: vanerf_query_order, the five instantiations of query_kernel
-(fp32, bf16x3 without a table, lean, hoisted under VANERF_LEAN_STREAM=0 -- each without and with the work order -- and the training spill
-forward with its xs / aux buffers) on the half-masked 128 x 128 frame of tests/test_lean_stream.py at 16 samples per ray (262 144 samples:
+"""Two builds of the library compute the same bits in the per-sample kernels: vanerf_query_order, the instantiations of query_kernel
+(fp32, bf16x3 without a table, texel, lean under VANERF_TEXEL_PRODUCTS=0, hoisted under VANERF_LEAN_STREAM=0 -- each without and with the
+work order -- and the training spill forward with its xs / aux buffers; a library from before the texel level ignores its switch and runs the
+lean level in both cases: "texel" then differs, "lean" must not) on the half-masked 128 x 128 frame of tests/test_lean_stream.py at 16 samples per ray (262 144 samples:
 at least three rounds per block, with full -> full, full -> short and short -> full hand-overs).
 usage: query_bits.py LIB_A LIB_B     one fresh child process per library (VANERF_HIP_LIB), digests compared; exit status 1 on any difference"""
 import hashlib
@@ -36,17 +37,19 @@ def digests():
     res = {"n": pts.shape[0], "order": dig(order)}
     w0, w1 = R.PackedWeights(sd, mode="fp32"), R.PackedWeights(sd, mode="bf16x3")
     table = fdat.vertex_products(w1)
-    cases = [("fp32", w0, None, None), ("bf16x3", w1, None, None), ("lean", w1, table, None), ("hoisted", w1, table, "0")]
-    for name, w, vp, switch in cases:
-        os.environ.pop("VANERF_LEAN_STREAM", None)
-        if switch is not None:
-            os.environ["VANERF_LEAN_STREAM"] = switch
+    cases = [("fp32", w0, None, {}), ("bf16x3", w1, None, {}), ("texel", w1, table, {}), ("lean", w1, table, {"VANERF_TEXEL_PRODUCTS": "0"}),
+             ("hoisted", w1, table, {"VANERF_LEAN_STREAM": "0"})]
+    for name, w, vp, switches in cases:
+        for var in ("VANERF_LEAN_STREAM", "VANERF_TEXEL_PRODUCTS"):
+            os.environ.pop(var, None)
+        os.environ.update(switches)
         for o in (None, order):
             c0 = w.short_groups()
             out, valid = R.query_samples(w, fdat, pts, q_sdf, q_vis, knn, want_valid=True, order=o, vertex_products=vp)
             key = name + ("+order" if o is not None else "")
             res[key] = {"out": dig(out), "valid": dig(valid), "short_groups": int(w.short_groups() - c0), "finite": bool(torch.isfinite(out).all())}
-    os.environ.pop("VANERF_LEAN_STREAM", None)
+    for var in ("VANERF_LEAN_STREAM", "VANERF_TEXEL_PRODUCTS"):
+        os.environ.pop(var, None)
     n = 65536  # one block of the training step
     ws = HB.workspace(n, pts.device)
     for t in (ws.xs, ws.aux, ws.raw, ws.valid):

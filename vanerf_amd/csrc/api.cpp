@@ -114,8 +114,9 @@ extern "C" int vanerf_weights_stream_host(const VanerfWeightTable* w, int which,
 {
     return guarded([&] {
         if (!w || !n_out) throw_error("vanerf_weights_stream_host: null argument");
-        if (which < 0 || which >= NUM_STREAMS)
-            throw_error("vanerf_weights_stream_host: which = %d (0 fp32, 1 bf16x3, 2 backward, 3 hoisted bf16x3, 4 lean bf16x3, 5 its bias table, 6 its folded matrices)", which);
+        if (which < 0 || which >= NUM_STREAMS || which == STREAM_NONE)
+            throw_error("vanerf_weights_stream_host: which = %d (0 fp32, 1 bf16x3, 2 backward, 3 hoisted bf16x3, 4 lean bf16x3, 5 its bias table, 6 its folded matrices, "
+                        "8 texel bf16x3, 9 its copy of the bias table)", which);
         copy_out("vanerf_weights_stream_host", stream_host(fold_host(*w), which), out, cap, n_out);
     });
 }
@@ -126,8 +127,9 @@ extern "C" int vanerf_weights_download(const VanerfWeights* w, int which, float*
 {
     return guarded([&] {
         if (!w || !n_out) throw_error("vanerf_weights_download: null argument");
-        if (which != 0 && (which < 2 || which >= NUM_STREAMS))
-            throw_error("vanerf_weights_download: which = %d (0 forward, 2 backward, 3 hoisted bf16x3, 4 lean bf16x3, 5 its bias table, 6 its folded matrices)", which);
+        if (which != 0 && (which < 2 || which >= NUM_STREAMS || which == STREAM_NONE))
+            throw_error("vanerf_weights_download: which = %d (0 forward, 2 backward, 3 hoisted bf16x3, 4 lean bf16x3, 5 its bias table, 6 its folded matrices, "
+                        "8 texel bf16x3, 9 its copy of the bias table)", which);
         if (which == STREAM_FP32) which = forward_stream(w->mode); // 0 asks for the forward stream of whichever mode
         if (!w->stream[which]) throw_error("vanerf_weights_download: the handle carries no such stream");
         *n_out = (int64_t)w->words[which];

@@ -28,9 +28,9 @@ constexpr int RING_WAVES = 8; // the waves of the kernel's one block per CU, whi
 // Layers LDS_FIRST .. NUM_LAYERS-1 are copied once per block: ibr_compress and the four TexVisFusion layers (126 KB: what the all-invalid
 // groups need).  The layers in front of them are SHARED by the block's waves through an LDS ring of 32 KB (below).
 // The lean stream is short enough for L_HEAD1 and L_HEAD2 to stay as well (24 KB more): four ring phases and their barriers less per round.
-// (LEVEL: the stream of layer_spec.h the kernel walks, 0 plain, 1 hoisted, 2 lean -- layers differ in length, so every offset, the ring's phases
+// (LEVEL: the stream of layer_spec.h the kernel walks, 0 plain, 1 hoisted, 2 lean, 3 texel -- layers differ in length, so every offset, the ring's phases
 // and the resident size differ)
-template <int LEVEL> constexpr int LDS_FIRST = LEVEL == 2 ? L_HEAD1 : L_IBR;
+template <int LEVEL> constexpr int LDS_FIRST = lean_level(LEVEL) ? L_HEAD1 : L_IBR;
 template <int LEVEL> constexpr unsigned RES_BASE_DW = layer_offset_b(LDS_FIRST<LEVEL>, LEVEL);
 template <int LEVEL> constexpr unsigned RES_DW = layer_offset_b(NUM_LAYERS, LEVEL) - layer_offset_b(LDS_FIRST<LEVEL>, LEVEL);
 // (The key points live in LDS because 256 registers per wave hold nothing long-lived: one ds_read_b128 per key point and group.)
@@ -43,7 +43,7 @@ constexpr unsigned LDS_KPT = 0u, LDS_CTRL = 2u * PE_KPT_PER_HALF * 16u, LDS_LAT0
 // [768, 896): ibr_compress of an all-zero pooled latent (its bias through the same MFMA chain), [lane half][16 registers]: what every sample of an
 // all-invalid group gets from that layer -- computed once per block, read by the short path instead of 27 MFMAs per group
 template <int LEVEL> constexpr unsigned LDS_BIAS = LDS_RES + RES_DW<LEVEL> * 4u;
-template <int LEVEL> constexpr unsigned DYN_LDS_BYTES = LDS_BIAS<LEVEL> + (LEVEL == 2 ? BIAS_TABLE_FLOATS * 4u : 0u);
+template <int LEVEL> constexpr unsigned DYN_LDS_BYTES = LDS_BIAS<LEVEL> + (lean_level(LEVEL) ? BIAS_TABLE_FLOATS * 4u : 0u);
 // The streamed part of the fragment stream (layers 0 .. LDS_FIRST-1) as 1 KB pieces (one (k-step, output block, hi | lo) fragment each = one
 // LDS-DMA wave instruction), in the order the layers consume them; a PHASE is 16 consecutive pieces.
 template <int LEVEL> constexpr unsigned RING_PIECES = RES_BASE_DW<LEVEL> / 256u;
@@ -56,7 +56,9 @@ static_assert(RING_WAVES == 8 && 2u * RING_WAVES == RING_PHASE_PIECES, "the ring
 static_assert(RING_PHASES<0> * RING_PHASE_PIECES * 256u <= layer_offset_b(NUM_LAYERS), "the last phase's DMA must stay inside the stream");
 static_assert(RING_PHASES<1> * RING_PHASE_PIECES * 256u <= layer_offset_b(NUM_LAYERS, 1), "the last phase's DMA must stay inside the hoisted stream");
 static_assert(RING_PHASES<2> * RING_PHASE_PIECES * 256u <= layer_offset_b(NUM_LAYERS, 2), "the last phase's DMA must stay inside the lean stream");
-static_assert(RING_STREAM_PHASES<1> == 31u && RING_STREAM_PHASES<2> == 27u, "the streamed parts: 486 KB hoisted, 426 KB lean");
+static_assert(RING_PHASES<3> * RING_PHASE_PIECES * 256u <= layer_offset_b(NUM_LAYERS, 3), "the last phase's DMA must stay inside the texel stream");
+static_assert(RING_STREAM_PHASES<1> == 31u && RING_STREAM_PHASES<2> == 27u && RING_STREAM_PHASES<3> == 26u, "the streamed parts: 486 KB hoisted, 426 KB lean, 402 KB texel");
+static_assert(LDS_BIAS<3> == LDS_BIAS<2> && DYN_LDS_BYTES<3> == DYN_LDS_BYTES<2>, "the texel level's resident part and bias table are the lean level's");
 static_assert(LDS_CTRL + 8u + 2u * 4u * RING_WAVES <= LDS_LAT0 && LDS_LAT0 + 128u <= LDS_RING, "control words / constant latent overlap their neighbours");
 static_assert(DYN_LDS_BYTES<0> <= 160u * 1024u && DYN_LDS_BYTES<1> <= DYN_LDS_BYTES<0> && DYN_LDS_BYTES<2> <= 160u * 1024u,
               "key points + control words + ring + resident fragments (+ bias table) must fit the CU's 160 KB");

@@ -80,13 +80,19 @@ constexpr unsigned layer_offset(int l)
 //   - the TexVisFusion input holds (qt[2] | vis_tw) in ONE k-pair instead of (qt[2] | 0) and (vis_tw | 0): L_TEX_A has 48 pairs (6 steps),
 //     L_TEX_AT_A 19 (still 3 steps).
 constexpr bool lean_no_bias_pair(int l) { return l == L_MLP1 || l == L_HEAD0 || l == L_HEAD1 || l == L_HEAD2 || l == L_IBR; }
+//
+// A fourth, TEXEL stream (level 3) is the lean stream with L_GEO_AT0_A / L_GEO_ATED0_A cut to their two scalar k-pairs [(sdf, qvis) | (vis_nn,
+// vis_tw)]: the pixel feature is the bilinear sample of geo0, grid_sample is linear in the tap values and the gate a0 is a scalar, so
+// W[:, 0:64] bilin(geo0) = bilin(W[:, 0:64] geo0) -- the kernel samples the per-texel products (the table below) where it sampled the feature.
+constexpr bool lean_level(int level) { return level >= 2; }
 constexpr int kT_b(int l, int level)
 {
+    if (level == 3 && (l == L_GEO_AT0_A || l == L_GEO_ATED0_A)) return 2;
     if (level >= 1 && (l == L_GEO_AT0_A || l == L_GEO_ATED0_A)) return 32 + 2;
-    if (level >= 1 && l == L_TEX_AT_A) return 6 + 12 + (level == 2 ? 1 : 2);
-    if (level == 2 && (l == L_GEO_ATED0_B || l == L_GEO_ATED1_B)) return 0;
-    if (level == 2 && lean_no_bias_pair(l)) return kT[l] - 1;
-    if (level == 2 && l == L_TEX_A) return 48;
+    if (level >= 1 && l == L_TEX_AT_A) return 6 + 12 + (lean_level(level) ? 1 : 2);
+    if (lean_level(level) && (l == L_GEO_ATED0_B || l == L_GEO_ATED1_B)) return 0;
+    if (lean_level(level) && lean_no_bias_pair(l)) return kT[l] - 1;
+    if (lean_level(level) && l == L_TEX_A) return 48;
     return kT[l];
 }
 constexpr int steps_b(int l, int level = 0) { return (kT_b(l, level) + 7) / 8; }
@@ -123,7 +129,16 @@ constexpr unsigned FOLD_FLOATS = FOLD0_ROWS * FOLD0_COLS + FOLD1_ROWS * FOLD1_CO
 constexpr unsigned VP_NV = 1558u;
 constexpr unsigned VP_A0_ROW = 16u, VP_N0_ROW = 64u, VP_P_ROW = 96u;
 constexpr unsigned VP_A0 = 0u, VP_N0 = VP_A0 + VP_NV * VP_A0_ROW, VP_T0 = VP_N0 + VP_NV * VP_N0_ROW, VP_P = VP_T0 + VP_NV * VP_N0_ROW;
-constexpr unsigned VP_FLOATS = VP_P + VP_NV * VP_P_ROW;
+constexpr unsigned VP_VERTEX_FLOATS = VP_P + VP_NV * VP_P_ROW;
+// Behind them the per-texel products of the 64-channel geometry map (level 3), rows in the same D-register order, texel = y * w0 + x:
+//   GA[texel] = Wat[:, 0:64] geo0[texel]     [2][8]      like A0
+//   GM[texel] = Wated[:, 0:64] geo0[texel]   [2][2][16]  like N0 (scaled by the sample's gate a0)
+// The size query of vanerf_vertex_products has no frame, so the part has a fixed capacity: 32 x 32 texels (a 256 x 256 source).  A frame with
+// more texels leaves the part unwritten and runs the lean level (texel_products_fit: the build and the launch ask the same question).
+constexpr unsigned VP_TEXELS_MAX = 1024u;
+constexpr unsigned VP_GA = VP_VERTEX_FLOATS, VP_GM = VP_GA + VP_TEXELS_MAX * VP_A0_ROW;
+constexpr unsigned VP_FLOATS = VP_GM + VP_TEXELS_MAX * VP_N0_ROW;
+constexpr bool texel_products_fit(int h0, int w0) { return h0 > 0 && w0 > 0 && (long long)h0 * w0 <= (long long)VP_TEXELS_MAX; }
 
 // ---- training: spills of the fused backward pass (query_backward.hip) ---------------------------------------
 // The forward kernel in spill mode writes every layer's B operands X (the layer's inputs after the previous activation, slot (t, h) = k-pair t

@@ -204,7 +204,7 @@ template <int LEVEL, unsigned BASE_DW, unsigned DW, unsigned LDS_AT, unsigned TH
 {
     const u32x4* __restrict__ src = reinterpret_cast<const u32x4*>(P.w) + BASE_DW / 4;
     for (unsigned i = threadIdx.x; i < DW / 4; i += THREADS) s_dyn[LDS_AT / 16 + i] = src[i];
-    if constexpr (LEVEL == 2) { // the bias table stands behind the stream's slack (layer_spec.h); here it goes right behind the resident fragments
+    if constexpr (LEVEL >= 2) { // the bias table stands behind the stream's slack (layer_spec.h); here it goes right behind the resident fragments
         const u32x4* __restrict__ bsrc = reinterpret_cast<const u32x4*>(P.w) + (layer_offset_b(NUM_LAYERS, LEVEL) + STREAM_SLACK_DW) / 4;
         if (threadIdx.x < BIAS_TABLE_FLOATS / 4) s_dyn[LDS_BIAS<LEVEL> / 16 + threadIdx.x] = bsrc[threadIdx.x];
     }
@@ -226,7 +226,7 @@ template <int LEVEL> __device__ __forceinline__ void short_path_latent(WRsrc W, 
         const LAddr la0 = make_laddr(lane, wv_u);
         auto r0 = ring_start_m<1, LEVEL, 1, T_IBR, L_IBR>(W, la0);
         f32x16 lat0[1];
-        if constexpr (LEVEL == 2) load_bias<L_IBR, 1>(lane >> 5, lat0);
+        if constexpr (LEVEL >= 2) load_bias<L_IBR, 1>(lane >> 5, lat0);
         else zero<1>(lat0);
         const float one0 = (lane >> 5) ? 0.0f : 1.0f;
         run_layer_m<1, LEVEL, 1, T_IBR, L_IBR>(lat0, r0, W, la0, [&](auto tc) -> float { return decltype(tc)::value < 64 ? 0.0f : one0; });
@@ -237,15 +237,24 @@ template <int LEVEL> __device__ __forceinline__ void short_path_latent(WRsrc W, 
 
 // Inputs of GeoVisFusion scale 0: the lane half's 32 channels of the pixel and of the two vertex rows -- hoisted kernels: the rows' products with
 // the two first layers instead of the rows (nn = N0[i], tw = T0[i]: same registers) and a0s = A0[i]
-template <bool HOIST>
+// -- texel level: pix = the bilinear sample of GM (the feature's product with the second layer, same taps, same weights) and a0s = A0[i] + the
+// sample of GA
+template <bool HOIST, bool TEXEL = false>
 __device__ __forceinline__ void geo0_gathers(const QueryParams& P, float x, float y, int h, int nn_idx, int tw_idx, float (&pix)[32], float (&nn)[32],
                                              float (&tw)[32], float (&a0s)[8])
 {
     const VanerfFrame& F = P.f;
     const Bilin b0 = bilin_setup(x, y, F.h0, F.w0, P.wm1[2], P.hm1[2]);
-    gather<8>(F.geo0, b0, 64, 32 * h, pix);
+    if constexpr (TEXEL) gather<8>(P.vp + VP_GM, b0, (int)VP_N0_ROW, 32 * h, pix);
+    else gather<8>(F.geo0, b0, 64, 32 * h, pix);
     if constexpr (HOIST) {
         load_row<2>(P.vp + VP_A0, (unsigned)(nn_idx * (int)VP_A0_ROW + 8 * h), a0s);
+        if constexpr (TEXEL) {
+            float ga[8];
+            gather<2>(P.vp + VP_GA, b0, (int)VP_A0_ROW, 8 * h, ga);
+#pragma unroll
+            for (int r = 0; r < 8; ++r) a0s[r] += ga[r];
+        }
         load_row<8>(P.vp + VP_N0, (unsigned)(nn_idx * (int)VP_N0_ROW + 32 * h), nn);
         load_row<8>(P.vp + VP_T0, (unsigned)(nn_idx * (int)VP_N0_ROW + 32 * h), tw);
     } else {
@@ -310,7 +319,7 @@ __device__ __forceinline__ void geo_scale(WRsrc W, int lane, const typename Lane
     if constexpr (MODE == 0) { constexpr int A = HC == 32 ? AUX_G0 : AUX_G1; spill_aux<A>(la, a0); spill_aux<A + 1>(la, a1); spill_aux<A + 2>(la, a2); }
 #pragma unroll
     for (int t = 0; t < HC; ++t) { pix[t] *= a0; nn[t] *= a1; tw[t] *= a2; }
-    if constexpr (LEVEL == 2) {
+    if constexpr (LEVEL >= 2) {
         zero<NBO>(outacc);
         run_layer_m<MODE, LEVEL, NBO, TIN, l_at_a + 2>(outacc, r_mid, W, la, input);
     } else {
@@ -329,16 +338,19 @@ __device__ __forceinline__ void geo_scale(WRsrc W, int lane, const typename Lane
 // products: `at` starts from A0[i] (registers 0..7, the rest of the block is rows >= 10), `mid` from a1 N0[i] + a2 T0[i] -- the gates scale the
 // products instead of the rows, W (a x) = a (W x) -- and the MFMAs run the 34 per-sample k-pairs [pix32 | (sdf, qvis) | (vis_nn, vis_tw)] only.
 // Lean kernel: ends at `mid`, as geo_scale.
+// Texel level: `pix` holds the sampled product GM, `a0s` already includes the sampled GA (geo0_gathers); `mid` starts from
+// a0 GM + a1 N0 + a2 T0 and both layers run the one step of their two scalar k-pairs.
 template <int MODE, int LEVEL>
 __device__ __forceinline__ void geo_scale0_vp(WRsrc W, int lane, const typename LaneSel<MODE>::type& la, typename RingSel<MODE, 1>::type& ring_at,
                                               float (&pix)[32], const float (&a0s)[8], const float (&n0)[32], const float (&t0)[32], float s0, float s1,
                                               f32x16 (&outacc)[2])
 {
-    constexpr int TIN = 32 + 2;
+    constexpr int TIN = kT_b(L_GEO_AT0_A, LEVEL);
+    static_assert(TIN == (LEVEL == 3 ? 2 : 32 + 2), "[pix32 |] (sdf, qvis) | (vis_nn, vis_tw)");
     auto input = [&](auto tc) -> float {
         constexpr int t = decltype(tc)::value;
-        if constexpr (t < 32) return pix[t];
-        else if constexpr (t == 32) return s0;
+        if constexpr (t < TIN - 2) return pix[t];
+        else if constexpr (t == TIN - 2) return s0;
         else return s1;
     };
     f32x16 at[1];
@@ -354,7 +366,11 @@ __device__ __forceinline__ void geo_scale0_vp(WRsrc W, int lane, const typename 
     const float a0 = __shfl(sigmoid_f(gate[0][0]), lane & 31);
     const float a1 = __shfl(sigmoid_f(gate[0][1]), lane & 31);
     const float a2 = __shfl(sigmoid_f(gate[0][2]), lane & 31);
-    if constexpr (LEVEL == 2) {
+    if constexpr (LEVEL == 3) {
+#pragma unroll
+        for (int t = 0; t < 32; ++t) outacc[t / 16][t % 16] = fmaf(a0, pix[t], fmaf(a2, t0[t], a1 * n0[t]));
+        run_layer_m<MODE, LEVEL, 2, TIN, L_GEO_ATED0_A>(outacc, r_mid, W, la, input);
+    } else if constexpr (LEVEL == 2) {
 #pragma unroll
         for (int t = 0; t < 32; ++t) { pix[t] *= a0; outacc[t / 16][t % 16] = fmaf(a2, t0[t], a1 * n0[t]); }
         run_layer_m<MODE, LEVEL, 2, TIN, L_GEO_ATED0_A>(outacc, r_mid, W, la, input);
@@ -475,7 +491,7 @@ __device__ __forceinline__ void mlp0_b(const VanerfFrame& F, WRsrc W, const LAdd
         [&](auto tc) -> float {
             constexpr int t = decltype(tc)::value;
             if constexpr (t < 147) return feat[t / 7][t % 7];
-            else if constexpr (LEVEL == 2 && t < 179) return lazy_act<1, ACT_RELU>(g64[(t - 147) / 16][(t - 147) % 16]);
+            else if constexpr (LEVEL >= 2 && t < 179) return lazy_act<1, ACT_RELU>(g64[(t - 147) / 16][(t - 147) % 16]);
             else return chain<32>(g64, std::integral_constant<int, t - 147>{}, one_h0);
         },
         [&](auto sc) {
@@ -498,7 +514,7 @@ __device__ __forceinline__ void mlp123(WRsrc W, const typename LaneSel<MODE>::ty
     auto r1 = ring_start_m<MODE, LEVEL, 4, T_MLP1, L_MLP1>(W, la);
     if constexpr (MODE == 0) softplus<4>(a0);
     f32x16 a1[4];
-    if constexpr (LEVEL == 2) load_bias<L_MLP1, 4>(h, a1);
+    if constexpr (LEVEL >= 2) load_bias<L_MLP1, 4>(h, a1);
     else zero<4>(a1);
     run_layer_m<MODE, LEVEL, 4, T_MLP1, L_MLP1>(a1, r1, W, la, [&](auto tc) -> float { return chain_sp<MODE, 64>(a0, tc, one_h0); });
     auto r2 = ring_start_m<MODE, LEVEL, 4, 69, L_MLP2>(W, la);
@@ -507,7 +523,7 @@ __device__ __forceinline__ void mlp123(WRsrc W, const typename LaneSel<MODE>::ty
     run_layer_m<MODE, LEVEL, 4, 69, L_MLP2>(a0, r2, W, la, [&](auto tc) -> float {
         constexpr int t = decltype(tc)::value;
         if constexpr (t < 64) return lazy_act<MODE, ACT_SOFTPLUS>(a1[t / 16][t % 16]);
-        else if constexpr (t < 68) return LEVEL == 2 ? lazy_act<MODE, ACT_RELU>(g8[0][t - 64]) : g8[0][t - 64];
+        else if constexpr (t < 68) return LEVEL >= 2 ? lazy_act<MODE, ACT_RELU>(g8[0][t - 64]) : g8[0][t - 64];
         else return one_h0;
     });
     auto r3 = ring_start_m<MODE, LEVEL, 2, 61, L_MLP3>(W, la);
@@ -539,19 +555,19 @@ __device__ __forceinline__ void head_layers(WRsrc W, const typename LaneSel<MODE
 {
     constexpr int T_HEAD0 = kT_b(L_HEAD0, LEVEL), T_HEAD1 = kT_b(L_HEAD1, LEVEL), T_HEAD2 = kT_b(L_HEAD2, LEVEL);
     f32x16 m0[2], m1[2];
-    if constexpr (LEVEL == 2) load_bias<L_HEAD0, 2>(h, m0);
+    if constexpr (LEVEL >= 2) load_bias<L_HEAD0, 2>(h, m0);
     else zero<2>(m0);
     run_layer_m<MODE, LEVEL, 2, T_HEAD0, L_HEAD0>(m0, rh0, W, la, [&](auto tc) -> float { return chain<64>(pool, tc, one_h0); });
     static_assert(LDS_FIRST<LEVEL> == L_HEAD2 + 1 || LDS_FIRST<LEVEL> == L_HEAD0 + 1, "the ring is closed behind its last streamed layer");
     if constexpr (MODE == 1 && LDS_FIRST<LEVEL> == L_HEAD0 + 1) ring_close<LEVEL>(W, la);
     auto rh1 = ring_start_m<MODE, LEVEL, 2, T_HEAD1, L_HEAD1>(W, la);
     if constexpr (MODE == 0) softplus<2>(m0);
-    if constexpr (LEVEL == 2) load_bias<L_HEAD1, 2>(h, m1);
+    if constexpr (LEVEL >= 2) load_bias<L_HEAD1, 2>(h, m1);
     else zero<2>(m1);
     run_layer_m<MODE, LEVEL, 2, T_HEAD1, L_HEAD1>(m1, rh1, W, la, [&](auto tc) -> float { return chain_sp<MODE, 32>(m0, tc, one_h0); });
     auto rh2 = ring_start_m<MODE, LEVEL, 1, T_HEAD2, L_HEAD2>(W, la);
     if constexpr (MODE == 0) softplus<2>(m1);
-    if constexpr (LEVEL == 2) load_bias<L_HEAD2, 1>(h, head);
+    if constexpr (LEVEL >= 2) load_bias<L_HEAD2, 1>(h, head);
     else zero<1>(head);
     run_layer_m<MODE, LEVEL, 1, T_HEAD2, L_HEAD2>(head, rh2, W, la, [&](auto tc) -> float { return chain_sp<MODE, 32>(m1, tc, one_h0); });
     if constexpr (MODE == 1 && LDS_FIRST<LEVEL> == L_HEAD2 + 1) ring_close<LEVEL>(W, la);
@@ -571,7 +587,7 @@ __device__ __forceinline__ void ibr_compress(WRsrc W, const typename LaneSel<MOD
     } else {
         auto r_ibr = ring_start_m<MODE, LEVEL, 1, T_IBR, L_IBR>(W, la);
         r_ta = ring_start_m<MODE, LEVEL, 3, T_TEX_AT, L_TEX_AT_A>(W, la);
-        if constexpr (LEVEL == 2) load_bias<L_IBR, 1>(h, lat);
+        if constexpr (LEVEL >= 2) load_bias<L_IBR, 1>(h, lat);
         else zero<1>(lat);
         run_layer_m<MODE, LEVEL, 1, T_IBR, L_IBR>(lat, r_ibr, W, la, [&](auto tc) -> float { return chain<64>(pool, tc, one_h0); });
     }
@@ -584,7 +600,7 @@ __device__ __forceinline__ void tex_vis_fusion(WRsrc W, const typename LaneSel<M
                                                float vis_tw, float (&row)[32], const float (&qi)[4], const float (&qt)[8], const f32x16 (&lat)[1],
                                                typename RingSel<MODE, 3>::type& r_ta, f32x16 (&rgb)[1])
 {
-    constexpr bool HOIST = LEVEL >= 1, LEAN = LEVEL == 2;
+    constexpr bool HOIST = LEVEL >= 1, LEAN = LEVEL >= 2;
     constexpr int T_TEX_AT = kT_b(L_TEX_AT_A, LEVEL), T_TEX = kT_b(L_TEX_A, LEVEL);
     float q[6];
     q[0] = h ? qt[3] : qi[0]; q[1] = h ? qt[4] : qi[1]; q[2] = h ? qt[5] : qi[2];
@@ -684,8 +700,8 @@ template <int MODE, bool SPILL = false, int LEVEL = 0, bool HANDOVER = false>
 __global__ __launch_bounds__(64 * WPB<MODE>, SPILL ? WAVES_PER_SIMD_SPILL : WAVES_PER_SIMD) void query_kernel(const QueryParams P)
 {
     static_assert(!SPILL || MODE == 0, "the training spill runs on the fp32 kernel");
-    static_assert(!HANDOVER || LEVEL == 2, "the short-only kernel exists at the lean level");
-    static_assert(LEVEL >= 0 && LEVEL <= 2 && (LEVEL == 0 || MODE == 1), "only the split-bf16 kernel has a hoisted and a lean variant");
+    static_assert(!HANDOVER || LEVEL >= 2, "the short-only kernel exists at the lean level (it serves the texel level as it stands)");
+    static_assert(LEVEL >= 0 && LEVEL <= 3 && (LEVEL == 0 || MODE == 1), "only the split-bf16 kernel has a hoisted, a lean and a texel variant");
     constexpr bool HOIST = LEVEL >= 1;
     constexpr int WAVES_PER_BLOCK = WPB<MODE>;
     const int lane_k = threadIdx.x & 63;
@@ -790,7 +806,7 @@ __global__ __launch_bounds__(64 * WPB<MODE>, SPILL ? WAVES_PER_SIMD_SPILL : WAVE
             {
                 float pix[32], nn[32], tw[32];
                 [[maybe_unused]] float a0s[8];
-                geo0_gathers<HOIST>(P, x, y, h, nn_idx, tw_idx, pix, nn, tw, a0s);
+                geo0_gathers<HOIST, LEVEL == 3>(P, x, y, h, nn_idx, tw_idx, pix, nn, tw, a0s);
                 if constexpr (MODE == 0) geo1_gathers(P, x, y, h, nn_idx, tw_idx, pix8, nn8, tw8);
                 STAMP(2); // geo gathers
                 if constexpr (HOIST) geo_scale0_vp<MODE, LEVEL>(W, lane, la, r_at0, pix, a0s, nn, tw, sc0, sc1, g64);
@@ -929,7 +945,7 @@ QueryParams query_params(const VanerfFrame& f, const VanerfWeights& w, Stream s,
                          const uint8_t* query_vis, const int32_t* knn_idx, int raw, int64_t n, float* out)
 {
     QueryParams P = {};
-    P.f = f; P.w = w.stream[s]; P.wbytes = (unsigned)((w.words[s] + (s == STREAM_LEAN ? w.words[STREAM_LEAN_BIAS] : 0)) * sizeof(float));
+    P.f = f; P.w = w.stream[s]; P.wbytes = (unsigned)((w.words[s] + (s == STREAM_LEAN ? w.words[STREAM_LEAN_BIAS] : s == STREAM_TEXEL ? w.words[STREAM_TEXEL_BIAS] : 0)) * sizeof(float));
     P.pts = pts; P.qsdf = query_sdf; P.qvis = query_vis; P.knn_in = knn_idx; P.raw = raw; P.n = n; P.out = out;
     const int ws[4] = {f.wi, f.wt, f.w0, f.w1}, hs[4] = {f.hi, f.ht, f.h0, f.h1};
     for (int i = 0; i < 4; ++i) { P.wm1[i] = (float)(ws[i] - 1); P.hm1[i] = (float)(hs[i] - 1); }
@@ -997,6 +1013,13 @@ bool short_kernel_enabled()
     return !(e && e[0] == '0' && !e[1]);
 }
 
+// VANERF_TEXEL_PRODUCTS (read at every launch, for tests and A/B runs): 0 = the lean level even where the table holds the per-texel products.
+bool texel_products_enabled()
+{
+    const char* e = std::getenv("VANERF_TEXEL_PRODUCTS");
+    return !(e && e[0] == '0' && !e[1]);
+}
+
 } // namespace
 
 // vertex_products: the frame's table from vanerf_vertex_products (built with the same handle, after its last update), or NULL.  With the
@@ -1019,17 +1042,23 @@ extern "C" int vanerf_query_samples(const VanerfWeights* w, const VanerfFrame* f
         const bool hoist = vertex_products != nullptr;
         if (hoist && !w->stream[STREAM_HOISTED]) throw_error("vanerf_query_samples: a table of vertex products needs a bf16x3 weight handle");
         if (hoist && (reinterpret_cast<uintptr_t>(vertex_products) & 15u)) throw_error("vanerf_query_samples: the table must be 16-byte aligned");
-        const Stream s = !hoist ? forward_stream(w->mode) : w->stream[STREAM_LEAN] && lean_stream_enabled() ? STREAM_LEAN : STREAM_HOISTED;
+        // the texel level: the table's per-texel part is filled for this frame (vanerf_vertex_products asked the same question of the same fields)
+        const bool texel = hoist && w->stream[STREAM_TEXEL] && texel_products_fit(f.h0, f.w0) && lean_stream_enabled() && texel_products_enabled();
+        const Stream s = !hoist ? forward_stream(w->mode) : texel ? STREAM_TEXEL : w->stream[STREAM_LEAN] && lean_stream_enabled() ? STREAM_LEAN : STREAM_HOISTED;
         QueryParams P = query_params(f, *w, s, pts, query_sdf, query_vis, knn_idx, raw, n, out);
         P.noise = noise; P.order = order; P.valid = valid; P.short_groups = w->stats; P.vp = vertex_products;
         // with a partition (`order`: vanerf_query_order's, the all-invalid groups last) the lean kernel hands those groups over
-        const bool handover = order && s == STREAM_LEAN && short_kernel_enabled();
-        const QueryLaunch L = s == STREAM_LEAN      ? (handover ? query_launch<1, false, 2, true>() : query_launch<1, false, 2>())
+        const bool handover = order && (s == STREAM_LEAN || s == STREAM_TEXEL) && short_kernel_enabled();
+        const QueryLaunch L = s == STREAM_TEXEL     ? (handover ? query_launch<1, false, 3, true>() : query_launch<1, false, 3>())
+                              : s == STREAM_LEAN    ? (handover ? query_launch<1, false, 2, true>() : query_launch<1, false, 2>())
                               : s == STREAM_HOISTED ? query_launch<1, false, 1>()
                               : s == STREAM_BF16X3  ? query_launch<1>()
                                                     : query_launch<0>();
         launch_query(L, query_blocks(L, n), P, queue_word, stream);
-        if (handover) launch_short<2>(P, stream);
+        if (handover) { // the short path touches neither of the two shortened layers: the short-only kernel runs on the lean stream at either level
+            if (s == STREAM_TEXEL) { const QueryParams lean = query_params(f, *w, STREAM_LEAN, pts, query_sdf, query_vis, knn_idx, raw, n, out); P.w = lean.w; P.wbytes = lean.wbytes; }
+            launch_short<2>(P, stream);
+        }
     });
 }
 

@@ -86,7 +86,7 @@ Mat id_matrix(int l, int level = 0)
         m.b.resize(sh.nout);
         for (int o = 0; o < sh.nout; ++o) m.b[o] = (float)(base + m.w.size() + o);
     }
-    if (level == 2 && (l == L_MLP0 || l == L_MLP2)) {
+    if (lean_level(level) && (l == L_MLP0 || l == L_MLP2)) {
         const int c0 = l == L_MLP0 ? 294 : 128, nc = (int)(l == L_MLP0 ? FOLD0_COLS : FOLD1_COLS);
         const unsigned fold = (l == L_MLP0 ? EFF_FOLD0 : EFF_FOLD1) + 1u;
         for (int o = 0; o < sh.nout; ++o)
@@ -146,11 +146,12 @@ void emit_b_ids(std::vector<WordB>& out, int layer, const Mat& m, const Pairs& p
 
 // [pix | nn | twin] each `c` channels split in halves between the lane halves, then (sdf|qvis), (vis_nn|vis_twin)
 // (hoisted stream: the pixel feature and the scalar pairs only -- the vertex rows come from the table of per-vertex products)
-Pairs geo_input_pairs(int c, bool hoist = false)
+// (texel stream: the scalar pairs only -- the pixel feature's products come from the table as well)
+Pairs geo_input_pairs(int c, bool hoist = false, bool texel = false)
 {
     Pairs p;
     int hc = c / 2;
-    for (int grp = 0; grp < (hoist ? 1 : 3); ++grp)
+    for (int grp = 0; grp < (texel ? 0 : hoist ? 1 : 3); ++grp)
         for (int t = 0; t < hc; ++t) p.emplace_back(grp * c + t, grp * c + hc + t);
     p.emplace_back(3 * c + 0, 3 * c + 1);
     p.emplace_back(3 * c + 2, 3 * c + 3);
@@ -179,14 +180,14 @@ Pairs tex_input_pairs(bool hoist = false, bool merged = false)
 namespace {
 
 // k-pairs (input channel of lane half 0 / 1 per k-step) of every layer: structure only, no weights
-// (level: 0 the plain streams, 1 the hoisted bf16x3 stream, 2 the lean one -- layer_spec.h)
+// (level: 0 the plain streams, 1 the hoisted bf16x3 stream, 2 the lean one, 3 the texel one -- layer_spec.h)
 Pairs layer_pairs(int l, int level = 0)
 {
     Pairs p;
-    const bool hoist = level >= 1, lean = level == 2;
+    const bool hoist = level >= 1, lean = lean_level(level);
     auto bias_pair = [&](Pairs& q) { if (!(lean && lean_no_bias_pair(l))) ::bias_pair(q); };
     switch (l) {
-    case L_GEO_AT0_A: case L_GEO_ATED0_A: return geo_input_pairs(64, hoist);
+    case L_GEO_AT0_A: case L_GEO_ATED0_A: return geo_input_pairs(64, hoist, level == 3);
     case L_GEO_AT1_A: case L_GEO_ATED1_A: return geo_input_pairs(8);
     case L_GEO_AT0_B: case L_GEO_AT1_B: chain(p, 1, 6, 0, 10); return p;
     case L_GEO_ATED0_B: if (!lean) chain(p, 2, 16, 0, 64); return p; // (lean: folded into mlp0 / mlp2)
@@ -356,6 +357,8 @@ const PackTables& pack_tables()
         t.place[STREAM_HOISTED] = placement(place_bf16x3<1>, 2 * 64 * 4);
         t.place[STREAM_LEAN] = placement(place_bf16x3<2>, STREAM_SLACK_DW);
         t.place[STREAM_LEAN_BIAS] = placement(place_bias, 0);
+        t.place[STREAM_TEXEL] = placement(place_bf16x3<3>, STREAM_SLACK_DW);
+        t.place[STREAM_TEXEL_BIAS] = t.place[STREAM_LEAN_BIAS];
         for (int l = 0; l < NUM_LAYERS; ++l) t.offs.off[l] = layer_offset(l);
         if (t.words(STREAM_LEAN_BIAS) != BIAS_TABLE_FLOATS) throw_error("internal: bias table of %zu floats, layer_spec.h says %u", t.words(STREAM_LEAN_BIAS), BIAS_TABLE_FLOATS);
         t.n_eff = EFF_TOTAL;

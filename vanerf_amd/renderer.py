@@ -440,40 +440,57 @@ GEO_NN_COLS, GEO_TWIN_COLS = tuple(range(64, 128)), tuple(range(128, 192))
 TEX_NN_COLS = tuple(range(11, 22)) + tuple(range(33, 51))
 TEX_TWIN_COLS = tuple(range(22, 33)) + tuple(range(51, 69))
 VERTEX_PRODUCT_PARTS = (("A0", 10, 1, 8), ("N0", 64, 2, 16), ("T0", 64, 2, 16), ("P", 96, 3, 16))  # name, rows, output blocks, registers per block
+# Behind them, per texel of the 64-channel geometry map instead of per vertex (level 3 of layer_spec.h): the pixel columns 0..63 of the two geo
+# layers times geo0[texel].  The part has room for TEXELS_MAX texels whatever the frame; a larger map leaves it unwritten (the lean level runs).
+GEO_PIX_COLS = tuple(range(0, 64))
+TEXEL_PRODUCT_PARTS = (("GA", 10, 1, 8), ("GM", 64, 2, 16))
+TEXELS_MAX = 1024
 
 
 def twin_vertex(i):
     return (i + NV_HAND) % NV
 
 
-def vertex_products_reference(w_at, w_ated, w_tex, vfeat0, vfeat_tex):
-    """A0 (NV,10), N0, T0 (NV,64), P (NV,96) as plain matrix products in the dtype of the arguments: what vanerf_vertex_products computes in fp32."""
+def vertex_products_reference(w_at, w_ated, w_tex, vfeat0, vfeat_tex, geo0=None):
+    """A0 (NV,10), N0, T0 (NV,64), P (NV,96) as plain matrix products in the dtype of the arguments: what vanerf_vertex_products computes in fp32.
+    With geo0 (..., 64), channel-last: also the per-texel products GA (texels,10) and GM (texels,64), texel = y * w0 + x."""
     tw = twin_vertex(torch.arange(NV, device=vfeat0.device))
     nn_c, tw_c, tn_c, tt_c = (list(c) for c in (GEO_NN_COLS, GEO_TWIN_COLS, TEX_NN_COLS, TEX_TWIN_COLS))
-    return {"A0": vfeat0 @ w_at[:, nn_c].T + vfeat0[tw] @ w_at[:, tw_c].T,
-            "N0": vfeat0 @ w_ated[:, nn_c].T, "T0": vfeat0[tw] @ w_ated[:, tw_c].T,
-            "P": vfeat_tex[:, :29] @ w_tex[:, tn_c].T + vfeat_tex[tw, :29] @ w_tex[:, tt_c].T}
+    out = {"A0": vfeat0 @ w_at[:, nn_c].T + vfeat0[tw] @ w_at[:, tw_c].T,
+           "N0": vfeat0 @ w_ated[:, nn_c].T, "T0": vfeat0[tw] @ w_ated[:, tw_c].T,
+           "P": vfeat_tex[:, :29] @ w_tex[:, tn_c].T + vfeat_tex[tw, :29] @ w_tex[:, tt_c].T}
+    if geo0 is not None:
+        g = geo0.reshape(-1, 64)
+        out["GA"], out["GM"] = g @ w_at[:, list(GEO_PIX_COLS)].T, g @ w_ated[:, list(GEO_PIX_COLS)].T
+    return out
 
 
-def vertex_products_unpack(table):
+def vertex_products_unpack(table, texels=None):
     """The flat table of vanerf_vertex_products -> {"A0": (NV,10), "N0": (NV,64), "T0": (NV,64), "P": (NV,96)} in output-row order, and the
     largest magnitude among the padding entries (rows beyond a layer's outputs: must be 0).  A vertex's row of a part is laid out
-    [lane half h][block ob][register r] = output row 32 ob + (r & 3) + 8 (r >> 2) + 4 h."""
+    [lane half h][block ob][register r] = output row 32 ob + (r & 3) + 8 (r >> 2) + 4 h.
+    texels = h0 * w0 of a frame whose per-texel part is written (at most TEXELS_MAX): also "GA" (texels,10) and "GM" (texels,64), and the padding
+    then includes the rows of the texels beyond h0 * w0."""
     out, at, pad = {}, 0, 0.0
-    for name, rows, nb, nr in VERTEX_PRODUCT_PARTS:
-        width = 2 * nb * nr
-        part = table[at:at + NV * width].view(NV, 2, nb, nr)
-        at += NV * width
-        h, ob, r = torch.meshgrid(torch.arange(2), torch.arange(nb), torch.arange(nr), indexing="ij")
-        row = (32 * ob + (r & 3) + 8 * (r >> 2) + 4 * h).to(table.device)
-        flat = part.reshape(NV, width)
-        keep = (row < rows).reshape(-1)
-        res = torch.zeros(NV, rows, dtype=table.dtype, device=table.device)
-        res[:, row.reshape(-1)[keep]] = flat[:, keep]
-        assert int(keep.sum()) == rows
-        if (~keep).any():
-            pad = max(pad, float(flat[:, ~keep].abs().max()))
-        out[name] = res
+    for parts, n, used in ((VERTEX_PRODUCT_PARTS, NV, NV), (TEXEL_PRODUCT_PARTS, TEXELS_MAX, texels)):
+        for name, rows, nb, nr in parts:
+            width = 2 * nb * nr
+            part = table[at:at + n * width].view(n, 2, nb, nr)
+            at += n * width
+            if used is None:  # the per-texel part was not asked for (it is unwritten for a frame beyond the capacity)
+                continue
+            h, ob, r = torch.meshgrid(torch.arange(2), torch.arange(nb), torch.arange(nr), indexing="ij")
+            row = (32 * ob + (r & 3) + 8 * (r >> 2) + 4 * h).to(table.device)
+            flat = part.reshape(n, width)
+            keep = (row < rows).reshape(-1)
+            res = torch.zeros(n, rows, dtype=table.dtype, device=table.device)
+            res[:, row.reshape(-1)[keep]] = flat[:, keep]
+            assert int(keep.sum()) == rows
+            if (~keep).any():
+                pad = max(pad, float(flat[:, ~keep].abs().max()))
+            if used < n:
+                pad = max(pad, float(flat[used:].abs().max()))
+            out[name] = res[:used]
     assert at == table.numel()
     return out, pad
 
