@@ -1,4 +1,4 @@
-"""The forward and backward composite and the importance kernels at every width their launchers dispatch on (vanerf_amd/csrc/render_kernels.hip).
+"""The forward and backward composite and the importance kernels at every width their launchers dispatch on (vanerf_amd/csrc/render_kernels.hip; the composite's scan, sums, gather and width dispatch are csrc/wave_ray.h's).
 
 `launch_composite` picks composite_wave_kernel<1|2|3|4> for S <= 64 / 128 / 192 / 256 samples per ray and the one-thread-per-ray
 composite_kernel above; `vanerf_importance_merge` picks importance_merge_wave_kernel<1|2|4> for max(Sc, Sf) <= 64 / 128 / 256 and the serial

@@ -1,5 +1,6 @@
 """The baked hand in another pose (vanerf_amd/posed.py, vanerf_amd/csrc/pose_warp.hip) on a real MI355X: the per-face
-transforms against fp64, the march against its restatement at every sample count on both sides of a round of 64, an affine field seen through a
+transforms against fp64, the march against its restatement at every sample count on both sides of a round of 64, the identity pose against
+march_volume bit for bit, an affine field seen through a
 rigid map against its closed form, the empty rules, determinism, the end-to-end path on the synthetic two-hand frame and the argument checks.
 
 The restatements (`restate_transforms`, `restate_march`) and the drawn inputs are those of tests/test_posed_volume_cpu.py, which checks them on
@@ -113,6 +114,41 @@ def test_march_against_fp64(R, name, S, beta):
     flat = posed.march_volume_posed(B.volume_of(vox, grid, beta), *args, reach=P.REACH)  # the tile only decides which rays share a block
     for a, b, c in zip(got, by_handle, flat):
         assert torch.equal(bits(a), bits(b)) and torch.equal(bits(a), bits(c))
+
+
+IDENTITY_GRID = dict(dims=(7, 6, 5), origin=(-0.12, -0.1, 0.9), spacing=(0.04, 0.04, 0.05))
+
+
+@pytest.mark.parametrize("S", [1, 64, 130])
+def test_the_identity_pose_gives_the_bits_of_march_volume(R, S):
+    """Both marches are wave_ray.h's march_rounds on volume_field.h's field and differ by their sample functor alone.  With every record
+    exactly [I | 0], face = 0, sdf = 0 and reach = inf no sample is empty and the warp is exact -- for finite p, ((1 px + 0 py) + 0 pz) + 0
+    is px -- so march_volume_posed must return march_volume's bits.  Host-made inputs: 2 views of 5 x 3 rays (odd in both directions of the
+    2 x 2 tile) through a 7 x 6 x 5 grid, one ray with hit = 0, sample counts on both sides of a round of 64."""
+    from vanerf_amd import baked, posed
+    rng = np.random.default_rng(40 + S)
+    grid = IDENTITY_GRID
+    (nx, ny, nz), o, s = grid["dims"], np.array(grid["origin"]), np.array(grid["spacing"])
+    vox = rng.random((nz, ny, nx, 4), dtype=np.float32)
+    vox[..., 0] = vox[..., 0] * 0.07 - 0.02
+    V, row_rays, rows = 2, 5, 3
+    Rn = row_rays * rows
+    eyes = np.array([[0.01, -0.02, 0.0], [0.95, 0.03, 1.01]])
+    aims = o + rng.random((V, Rn, 3)) * s * (np.array([nx, ny, nz]) - 1)  # points of the grid's box
+    d = aims - eyes[:, None]
+    rays_d = dev((d / np.linalg.norm(d, axis=-1, keepdims=True)).astype(np.float32))
+    cam_pos = dev(np.concatenate([eyes, np.zeros((V, 1))], 1).astype(np.float32))
+    z = dev(np.sort(0.75 + 0.5 * rng.random((V, Rn, S), dtype=np.float32), axis=-1))  # from in front of the box to behind it
+    hit = np.ones((V, Rn), dtype=np.uint8)
+    hit[1, 4] = 0
+    vol = B.volume_of(torch.from_numpy(vox), grid, 0.05)
+    T = dev(np.tile(np.array([1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0], dtype=np.float32), (3, 1)))
+    face, sdf = torch.zeros(V, Rn, S, dtype=torch.int32, device="cuda"), torch.zeros(V, Rn, S, device="cuda")
+    plain = baked.march_volume(vol, rays_d, cam_pos, z, dev(hit), row_rays=row_rays)
+    warped = posed.march_volume_posed(vol, T, face, sdf, rays_d, cam_pos, z, dev(hit), reach=INF, row_rays=row_rays)
+    assert float(plain[2].max()) > 0.1 and torch.isfinite(plain[1]).all()  # the rays do see the volume
+    for k, a, b in zip(("color", "depth", "alpha"), plain, warped):
+        assert torch.equal(bits(a), bits(b)), k
 
 
 # ------------------------------------------------------------------------------------------------

@@ -129,26 +129,38 @@ def _check_out(out, shapes, dev):
     return out
 
 
+def _beta_args(volume):
+    """volume.beta as the marches pass it on: (weight handle or None, the number or 0.0); a handle must live on the voxels' device."""
+    from . import renderer as R
+    dev = volume.voxels.device
+    if not isinstance(volume.beta, R.PackedWeights):
+        return None, float(volume.beta)
+    if volume.beta.device_index is not None and volume.beta.device_index != dev.index:
+        raise ValueError(f"volume.beta: the weight handle lives on device {volume.beta.device_index}, the voxels on {dev}")
+    return volume.beta.handle, 0.0
+
+
+def _march_out(out, V, Rn, dev):
+    """(color (V, Rn, 3), depth (V, Rn), alpha (V, Rn)) of a march on dev: the caller's `out`, checked, or new tensors."""
+    if out is None:
+        out = (torch.empty(V, Rn, 3, dtype=torch.float32, device=dev), *(torch.empty(V, Rn, dtype=torch.float32, device=dev) for _ in range(2)))
+    return _check_out(out, (((V, Rn, 3), torch.float32, "color"), ((V, Rn), torch.float32, "depth"), ((V, Rn), torch.float32, "alpha")), dev)
+
+
 def march_volume(volume, rays_d, cam_pos, z, hit, row_rays=None, out=None):
     """vanerf_volume_render on rays laid out as renderer.ray_setup_views lays them out: rays_d (V, R, 3), cam_pos (V, 4), z (V, R, S) fp32 and
     hit (V, R) uint8 on the volume's device -> color (V, R, 3), depth (V, R), alpha (V, R).  row_rays: the rays of one pixel row (default R:
     it only decides which rays share a block).  out: (color, depth, alpha), contiguous fp32 device tensors to fill instead of new ones: every
     element is written, whatever they held.  One launch."""
-    from . import renderer as R
     nx, ny, nz = _check_volume(volume)
     V, Rn, S, ptrs = _check_rays(volume, rays_d, cam_pos, z, hit)
     dev = volume.voxels.device
     row_rays = Rn if row_rays is None else int(row_rays)
-    by_handle = isinstance(volume.beta, R.PackedWeights)
-    if by_handle and volume.beta.device_index is not None and volume.beta.device_index != dev.index:
-        raise ValueError(f"volume.beta: the weight handle lives on device {volume.beta.device_index}, the voxels on {dev}")
+    handle, beta = _beta_args(volume)
     with torch.cuda.device(dev):
-        if out is None:
-            out = (torch.empty(V, Rn, 3, dtype=torch.float32, device=dev), *(torch.empty(V, Rn, dtype=torch.float32, device=dev) for _ in range(2)))
-        color, depth, alpha = _check_out(out, (((V, Rn, 3), torch.float32, "color"), ((V, Rn), torch.float32, "depth"), ((V, Rn), torch.float32, "alpha")), dev)
-        check(lib.vanerf_volume_render(c_void_p(volume.voxels.data_ptr()), _f3(volume.origin), _f3(volume.spacing), nx, ny, nz,
-                                       volume.beta.handle if by_handle else None, 0.0 if by_handle else float(volume.beta), *ptrs, V * Rn, Rn, row_rays, S,
-                                       c_void_p(color.data_ptr()), c_void_p(depth.data_ptr()), c_void_p(alpha.data_ptr()), _stream()))
+        color, depth, alpha = _march_out(out, V, Rn, dev)
+        check(lib.vanerf_volume_render(c_void_p(volume.voxels.data_ptr()), _f3(volume.origin), _f3(volume.spacing), nx, ny, nz, handle, beta, *ptrs,
+                                       V * Rn, Rn, row_rays, S, c_void_p(color.data_ptr()), c_void_p(depth.data_ptr()), c_void_p(alpha.data_ptr()), _stream()))
     return color, depth, alpha
 
 

@@ -6,6 +6,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "wave_ray.h"
 
 using namespace vanerf;
 
@@ -191,13 +192,9 @@ __global__ void composite_kernel(const float* __restrict__ rgba, const float* __
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= R) return;
     if (beta_dev) beta = *beta_dev; // a handle re-packed on the device (vanerf_weights_update) carries sigmoid_beta there, already clamped
-    const float* qa = rgba + (size_t)r * Sa * 5;
-    const float* ma = msdf + (size_t)r * Sa;
-    const float* qb = rgba_b ? rgba_b + (size_t)r * Sb * 5 : nullptr;
-    const float* mb = msdf_b ? msdf_b + (size_t)r * Sb : nullptr;
-    const int32_t* sr = src ? src + (size_t)r * S : nullptr;
+    const SampleTables tables(rgba, msdf, rgba_b, msdf_b, src, Sa, Sb, S, r);
     const float* zr = z + (size_t)r * S;
-    double cr = 0, cg = 0, cb = 0, ca = 0, cs = 0, cd = 0;
+    RaySums<true> sums;
     float T = 1.0f;
     float zi = zr[0];
     for (int i = 0; i < S; ++i) {
@@ -205,31 +202,16 @@ __global__ void composite_kernel(const float* __restrict__ rgba, const float* __
         const float dist = i + 1 < S ? zn - zi : 1e10f;
         const float* q;
         float m;
-        if (sr) {
-            const int k = sr[i];
-            if (k >= 0) { q = qa + 5 * k; m = ma[k]; } else { q = qb + 5 * (~k); m = mb[~k]; }
-        } else {
-            q = qa + 5 * i; m = ma[i];
-        }
-        const float a = q[0] + m;
-        const float sg = (1.0f / (1.0f + expf(-(-a / beta)))) / beta; // sigmoid(-a / beta) / beta
+        tables.fetch(tables.origin(i), q, m);
+        const float sg = sdf_sigmoid(q[0] + m, beta) / beta;
         const float c = 1.0f - expf(-sg * dist);
         const float w = c * T;
         T = T * (1.0f - c);
         if (contrib) contrib[(size_t)r * S + i] = w;
-        cr += (double)(q[2] * w);
-        cg += (double)(q[3] * w);
-        cb += (double)(q[4] * w);
-        ca += (double)w;
-        cs += (double)(q[1] * w);
-        cd += (double)(zi * w);
+        sums.add(q[2], q[3], q[4], q[1], w, zi);
         zi = zn;
     }
-    const float acc = (float)ca;
-    color[3 * r] = (float)cr; color[3 * r + 1] = (float)cg; color[3 * r + 2] = (float)cb;
-    alpha[r] = acc;
-    sdf[r] = (float)cs / (acc + 1e-8f);
-    depth[r] = (float)cd / (acc + 1e-8f);
+    sums.store(color, depth, alpha, sdf, r); // the serial fallback: no butterfly, the same epilogue
 }
 
 // importance_sample + sort-merge, one thread per ray; per-thread arrays live in LDS with a 64-thread stride
@@ -408,11 +390,7 @@ __global__ __launch_bounds__(256) void composite_wave_kernel(const float* __rest
     const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (r >= R) return; // whole wave
     if (beta_dev) beta = *beta_dev; // a handle re-packed on the device (vanerf_weights_update) carries sigmoid_beta there, already clamped
-    const float* qa = rgba + (size_t)r * Sa * 5;
-    const float* ma = msdf + (size_t)r * Sa;
-    const float* qb = rgba_b ? rgba_b + (size_t)r * Sb * 5 : nullptr;
-    const float* mb = msdf_b ? msdf_b + (size_t)r * Sb : nullptr;
-    const int32_t* sr = src ? src + (size_t)r * S : nullptr;
+    const SampleTables tables(rgba, msdf, rgba_b, msdf_b, src, Sa, Sb, S, r);
     const float* zr = z + (size_t)r * S;
     float c[SPL], zi[SPL], q1[SPL], q2[SPL], q3[SPL], q4[SPL];
     float lane_keep = 1.0f; // prod over this lane's samples of (1 - c)
@@ -422,32 +400,18 @@ __global__ __launch_bounds__(256) void composite_wave_kernel(const float* __rest
         c[k] = 0.0f; zi[k] = 0.0f; q1[k] = q2[k] = q3[k] = q4[k] = 0.0f;
         if (i < S) {
             zi[k] = zr[i];
-            const float dist = i + 1 < S ? zr[i + 1] - zi[k] : 1e10f;
+            const float dist = sample_dist(zr, i, S, zi[k]);
             const float* q;
             float m;
-            if (sr) {
-                const int kk = sr[i];
-                if (kk >= 0) { q = qa + 5 * kk; m = ma[kk]; } else { q = qb + 5 * (~kk); m = mb[~kk]; }
-            } else {
-                q = qa + 5 * i; m = ma[i];
-            }
-            const float a = q[0] + m;
-            const float sg = (1.0f / (1.0f + expf(-(-a / beta)))) / beta; // sigmoid(-a / beta) / beta
+            tables.fetch(tables.origin(i), q, m);
+            const float sg = sdf_sigmoid(q[0] + m, beta) / beta;
             c[k] = 1.0f - expf(-sg * dist);
             q1[k] = q[1]; q2[k] = q[2]; q3[k] = q[3]; q4[k] = q[4];
         }
         lane_keep *= 1.0f - c[k];
     }
-    // exclusive multiplicative scan of lane_keep over the lanes
-    float incl = lane_keep;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const float v = __shfl_up(incl, d);
-        if (lane >= d) incl *= v;
-    }
-    float T = __shfl_up(incl, 1);
-    if (lane == 0) T = 1.0f;
-    double cr = 0, cg = 0, cb = 0, ca = 0, cs = 0, cd = 0;
+    float T = exclusive_product_scan(lane_keep, lane).before;
+    RaySums<true> sums;
 #pragma unroll
     for (int k = 0; k < SPL; ++k) {
         const int i = lane * SPL + k;
@@ -455,22 +419,11 @@ __global__ __launch_bounds__(256) void composite_wave_kernel(const float* __rest
         T = T * (1.0f - c[k]);
         if (i < S) {
             if (contrib) contrib[(size_t)r * S + i] = w;
-            cr += (double)(q2[k] * w); cg += (double)(q3[k] * w); cb += (double)(q4[k] * w);
-            ca += (double)w; cs += (double)(q1[k] * w); cd += (double)(zi[k] * w);
+            sums.add(q2[k], q3[k], q4[k], q1[k], w, zi[k]);
         }
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        cr += __shfl_xor(cr, d); cg += __shfl_xor(cg, d); cb += __shfl_xor(cb, d);
-        ca += __shfl_xor(ca, d); cs += __shfl_xor(cs, d); cd += __shfl_xor(cd, d);
-    }
-    if (lane == 0) {
-        const float acc = (float)ca;
-        color[3 * r] = (float)cr; color[3 * r + 1] = (float)cg; color[3 * r + 2] = (float)cb;
-        alpha[r] = acc;
-        sdf[r] = (float)cs / (acc + 1e-8f);
-        depth[r] = (float)cd / (acc + 1e-8f);
-    }
+    sums.butterfly();
+    if (lane == 0) sums.store(color, depth, alpha, sdf, r);
 }
 
 static void launch_composite(const float* rgba, const float* z, const float* msdf, const float* rgba_b, const float* msdf_b,
@@ -480,18 +433,14 @@ static void launch_composite(const float* rgba, const float* z, const float* msd
     if (R <= 0 || S <= 0) throw_error("vanerf_composite: R=%d S=%d", R, S);
     if (!beta_dev && !(beta > 0.0f)) throw_error("vanerf_composite: beta must be positive");
     if (beta < 2e-3f) beta = 2e-3f; // sdf_activation clamp (src/model.py:880)
-    const dim3 wg((R + 3) / 4), wb(256);
-#define VANERF_COMPOSITE_WAVE(SPL)                                                                                                  \
-    hipLaunchKernelGGL(composite_wave_kernel<SPL>, wg, wb, 0, (hipStream_t)stream, rgba, z, msdf, rgba_b, msdf_b, src, Sa, Sb, R, S, beta, \
-                       beta_dev, color, depth, alpha, sdf, contrib)
-    if (S <= 64) VANERF_COMPOSITE_WAVE(1);
-    else if (S <= 128) VANERF_COMPOSITE_WAVE(2);
-    else if (S <= 192) VANERF_COMPOSITE_WAVE(3);
-    else if (S <= 256) VANERF_COMPOSITE_WAVE(4);
-    else // more than 256 samples per ray: one thread per ray
+    if (S > 256) // more than 256 samples per ray: one thread per ray
         hipLaunchKernelGGL(composite_kernel, dim3((R + 63) / 64), dim3(64), 0, (hipStream_t)stream, rgba, z, msdf, rgba_b, msdf_b, src, Sa, Sb,
                            R, S, beta, beta_dev, color, depth, alpha, sdf, contrib);
-#undef VANERF_COMPOSITE_WAVE
+    else
+        dispatch_spl(S, [&](auto spl) {
+            hipLaunchKernelGGL(composite_wave_kernel<decltype(spl)::value>, dim3((R + 3) / 4), dim3(256), 0, (hipStream_t)stream, rgba, z, msdf, rgba_b,
+                               msdf_b, src, Sa, Sb, R, S, beta, beta_dev, color, depth, alpha, sdf, contrib);
+        });
     HIP_CHECK(hipGetLastError());
 }
 
@@ -565,11 +514,7 @@ __global__ __launch_bounds__(256) void composite_backward_kernel(const float* __
     const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (r >= R) return; // whole wave
     const float beta = *beta_dev;
-    const float* qa = rgba + (size_t)r * Sa * 5;
-    const float* ma = msdf + (size_t)r * Sa;
-    const float* qb = rgba_b ? rgba_b + (size_t)r * Sb * 5 : nullptr;
-    const float* mb = msdf_b ? msdf_b + (size_t)r * Sb : nullptr;
-    const int32_t* sr = src ? src + (size_t)r * S : nullptr;
+    const SampleTables tables(rgba, msdf, rgba_b, msdf_b, src, Sa, Sb, S, r);
     const float* zr = z + (size_t)r * S;
     float keep[SPL], zi[SPL], dist[SPL], x[SPL], sg[SPL], q1[SPL], q2[SPL], q3[SPL], q4[SPL]; // keep_i = 1 - c_i = exp(-sigma_i dist_i)
     int from[SPL]; // where the sample's gradient goes: >= 0 entry of table a, < 0 entry ~from of table b
@@ -580,32 +525,19 @@ __global__ __launch_bounds__(256) void composite_backward_kernel(const float* __
         keep[k] = 1.0f; zi[k] = 0.0f; dist[k] = 0.0f; x[k] = 0.0f; sg[k] = 0.0f; q1[k] = q2[k] = q3[k] = q4[k] = 0.0f; from[k] = 0;
         if (i < S) {
             zi[k] = zr[i];
-            dist[k] = i + 1 < S ? zr[i + 1] - zi[k] : 1e10f;
+            dist[k] = sample_dist(zr, i, S, zi[k]);
             const float* q;
             float m;
-            if (sr) {
-                const int kk = sr[i];
-                from[k] = kk;
-                if (kk >= 0) { q = qa + 5 * kk; m = ma[kk]; } else { q = qb + 5 * (~kk); m = mb[~kk]; }
-            } else {
-                from[k] = i;
-                q = qa + 5 * i; m = ma[i];
-            }
+            from[k] = tables.origin(i);
+            tables.fetch(from[k], q, m);
             x[k] = q[0] + m;
-            sg[k] = 1.0f / (1.0f + expf(-(-x[k] / beta))); // sigmoid(-x / beta)
+            sg[k] = sdf_sigmoid(x[k], beta);
             keep[k] = expf(-(sg[k] / beta) * dist[k]);
             q1[k] = q[1]; q2[k] = q[2]; q3[k] = q[3]; q4[k] = q[4];
         }
         lane_keep *= keep[k];
     }
-    float incl = lane_keep;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const float v = __shfl_up(incl, d);
-        if (lane >= d) incl *= v;
-    }
-    float T0 = __shfl_up(incl, 1);
-    if (lane == 0) T0 = 1.0f;
+    const float T0 = exclusive_product_scan(lane_keep, lane).before;
     float w[SPL], Tn[SPL]; // w_i and T_{i+1}
     float ca = 0.0f, cs = 0.0f, cd = 0.0f;
     {
@@ -668,15 +600,11 @@ extern "C" int vanerf_composite_backward(const VanerfWeights* w, const float* rg
         if (rgba_n && (!mesh_sdf_n || !src || Sn <= 0 || !d_rgba_n)) throw_error("vanerf_composite_backward: the second table needs mesh_sdf_n, src, d_rgba_n and Sn > 0");
         const int Sb = rgba_n ? Sn : 0, S = Sa + Sb;
         if (R <= 0 || Sa <= 0 || S > 256) throw_error("vanerf_composite_backward: R=%d, %d samples per ray (at most 256)", R, S);
-        const dim3 wg((R + 3) / 4), wb(256);
-#define VANERF_CB(SPL)                                                                                                                              \
-    hipLaunchKernelGGL(composite_backward_kernel<SPL>, wg, wb, 0, (hipStream_t)stream, rgba, z, mesh_sdf, rgba_n, rgba_n ? mesh_sdf_n : nullptr,          \
-                       rgba_n ? src : nullptr, Sa, Sb, R, S, w->dev_beta, g_color, g_depth, g_alpha, g_sdf, d_rgba, d_rgba_n, d_beta)
-        if (S <= 64) VANERF_CB(1);
-        else if (S <= 128) VANERF_CB(2);
-        else if (S <= 192) VANERF_CB(3);
-        else VANERF_CB(4);
-#undef VANERF_CB
+        dispatch_spl(S, [&](auto spl) {
+            hipLaunchKernelGGL(composite_backward_kernel<decltype(spl)::value>, dim3((R + 3) / 4), dim3(256), 0, (hipStream_t)stream, rgba, z, mesh_sdf, rgba_n,
+                               rgba_n ? mesh_sdf_n : nullptr, rgba_n ? src : nullptr, Sa, Sb, R, S, w->dev_beta, g_color, g_depth, g_alpha, g_sdf, d_rgba,
+                               d_rgba_n, d_beta);
+        });
         HIP_CHECK(hipGetLastError());
     });
 }

@@ -1,14 +1,17 @@
 // volume_surface.hip -- the surface of the baked volume as a camera sees it (the comment of vanerf_volume_surface in the
 // header): per ray the first crossing of f = iso, outside to inside, along the samples of the pass's own rays; the crossing refined by 65-way
 // splits; depth, normal (the gradient of the trilinear field), n . v and the interpolated colour there.  The field is the trilinear function
-// vanerf_volume_render composites (volume_render.hip), restated here so that file stays as it is: the same u, clamp, cell and (1 - w) a + w b
-// order.  The restatement the tests hold this kernel to is the numpy code of tests/test_baked_surface.py.
+// vanerf_volume_render composites: both read it through volume_field.h.  The restatement the tests hold this kernel to is the numpy code of
+// tests/test_baked_surface.py.
 //
 // The pattern is volume_render_kernel's: one wave per ray, lanes over samples in rounds of 64, the four waves of a block on a 2 x 2 pixel tile
-// of one view.  A lane gets its neighbour's value by a shuffle (lane 0: the value carried from the round before), "outside there, inside here"
-// is a 64-bit ballot and its lowest set bit the crossing; every branch on it is wave-uniform.  No LDS, no atomics, no device-side state.
+// of one view (wave_ray.h's tile_ray).  A lane gets its neighbour's value by a shuffle (lane 0: the value carried from the round before),
+// "outside there, inside here" is a 64-bit ballot and its lowest set bit the crossing; every branch on it is wave-uniform.  No LDS, no
+// atomics, no device-side state.
 // Built with -ffp-contract=off: every product and sum below is its own IEEE operation.
 #include "common.h"
+#include "volume_field.h"
+#include "wave_ray.h"
 
 #include <cfloat>
 #include <cmath>
@@ -18,53 +21,10 @@ using namespace vanerf;
 
 namespace {
 
-struct SurfGrid {
-    float o[3], s[3];
-    int nx, ny, nz;
-};
-
-constexpr int VS_TX = 2, VS_TY = 2; // the pixel tile of a block, as volume_render.hip's
-constexpr int VS_WAVES = VS_TX * VS_TY;
 constexpr int MAX_REFINE = 4;
 
-// the grid coordinate of p on one axis, clamped onto the grid (fmaxf(NaN, 0) is 0: never an address outside the grid)
-__device__ __forceinline__ float coord_of(float p, float origin, float spacing, int n)
-{
-    const float u = (p - origin) / spacing;
-    return fminf(fmaxf(u, 0.0f), (float)(n - 1));
-}
-
-// the lower corner i0 of u's cell and the weight w of the upper one (u already clamped)
-__device__ __forceinline__ void cell_of(float u, int n, int& i0, float& w)
-{
-    i0 = min((int)floorf(u), n - 2);
-    w = u - (float)i0;
-}
-
-__device__ __forceinline__ float blend(float w, float a, float b)
-{
-    return (1.0f - w) * a + w * b; // with 1e30 entries the difference b - a must not be formed
-}
-
-// channels C0 .. C0 + NC - 1 of the trilinear interpolation at the clamped grid coordinate (ux, uy, uz); NC == 1 reads one float per corner
-template <int C0, int NC>
-__device__ __forceinline__ void field_at(const float* __restrict__ voxels, const SurfGrid& G, float ux, float uy, float uz, float* out)
-{
-    int ix, iy, iz;
-    float wx, wy, wz;
-    cell_of(ux, G.nx, ix, wx);
-    cell_of(uy, G.ny, iy, wy);
-    cell_of(uz, G.nz, iz, wz);
-    const size_t row = 4 * (size_t)G.nx, slab = row * (size_t)G.ny;
-    const float* p = voxels + ((size_t)iz * slab + (size_t)iy * row + 4 * (size_t)ix + C0);
-#pragma unroll
-    for (int c = 0; c < NC; ++c)
-        out[c] = blend(wz, blend(wy, blend(wx, p[c], p[4 + c]), blend(wx, p[row + c], p[row + 4 + c])),
-                       blend(wy, blend(wx, p[slab + c], p[slab + 4 + c]), blend(wx, p[slab + row + c], p[slab + row + 4 + c])));
-}
-
 // g(zz): f at p = o + d zz per axis (sample_points_kernel's expression)
-__device__ __forceinline__ float f_along(const float* __restrict__ voxels, const SurfGrid& G, const float o[3], const float d[3], float zz)
+__device__ __forceinline__ float f_along(const float* __restrict__ voxels, const VolGrid& G, const float o[3], const float d[3], float zz)
 {
     float f;
     field_at<0, 1>(voxels, G, coord_of(o[0] + d[0] * zz, G.o[0], G.s[0], G.nx), coord_of(o[1] + d[1] * zz, G.o[1], G.s[1], G.ny),
@@ -72,7 +32,7 @@ __device__ __forceinline__ float f_along(const float* __restrict__ voxels, const
     return f;
 }
 
-__global__ __launch_bounds__(64 * VS_WAVES) void volume_surface_kernel(const float* __restrict__ voxels, const SurfGrid G, float iso, int refine,
+__global__ __launch_bounds__(64 * RAY_WAVES) void volume_surface_kernel(const float* __restrict__ voxels, const VolGrid G, float iso, int refine,
                                                                        const float* __restrict__ rays_d, const float* __restrict__ cam_pos,
                                                                        const float* __restrict__ z, const uint8_t* __restrict__ hit, int rays_per_view,
                                                                        int row_rays, int S, float* __restrict__ depth, float4* __restrict__ normal,
@@ -80,12 +40,9 @@ __global__ __launch_bounds__(64 * VS_WAVES) void volume_surface_kernel(const flo
 {
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int tiles_x = (row_rays + VS_TX - 1) / VS_TX;
-    const int px = (int)(blockIdx.x % tiles_x) * VS_TX + (wave % VS_TX);
-    const int py = (int)(blockIdx.x / tiles_x) * VS_TY + (wave / VS_TX);
-    if (px >= row_rays || py >= rays_per_view / row_rays) return; // whole wave
-    const int v = blockIdx.y;
-    const size_t r = (size_t)v * (size_t)rays_per_view + (size_t)py * (size_t)row_rays + (size_t)px;
+    int v;
+    size_t r;
+    if (!tile_ray<RAY_TX, RAY_TY>(blockIdx.x, blockIdx.y, wave, row_rays, rays_per_view, v, r)) return; // whole wave
     const float o[3] = {cam_pos[4 * v], cam_pos[4 * v + 1], cam_pos[4 * v + 2]};
     const float d[3] = {rays_d[3 * r], rays_d[3 * r + 1], rays_d[3 * r + 2]};
     const float* zr = z + r * (size_t)S;
@@ -179,18 +136,6 @@ __global__ __launch_bounds__(64 * VS_WAVES) void volume_surface_kernel(const flo
     found[r] = (uint8_t)kind;
 }
 
-void check_grid(const char* who, const float* origin, const float* spacing, int nx, int ny, int nz)
-{
-    if (!origin || !spacing) throw_error("%s: null argument", who);
-    if (nx < 2 || ny < 2 || nz < 2) throw_error("%s: a grid of (%d, %d, %d) points: every dimension must be at least 2", who, nx, ny, nz);
-    if (7LL * nx * ny >= (1LL << 31) || 7LL * nx * ny * nz >= (1LL << 31))
-        throw_error("%s: a grid of (%d, %d, %d) points is too large: 7 nx ny nz must stay below 2^31", who, nx, ny, nz);
-    for (int a = 0; a < 3; ++a) {
-        if (!std::isfinite(origin[a])) throw_error("%s: the grid origin must be finite", who);
-        if (!(std::isfinite(spacing[a]) && spacing[a] > 0.0f)) throw_error("%s: the grid spacing must be finite and positive", who);
-    }
-}
-
 } // namespace
 
 extern "C" int vanerf_volume_surface(const float* voxels, const float origin[3], const float spacing[3], int nx, int ny, int nz, float iso, int refine,
@@ -206,18 +151,10 @@ extern "C" int vanerf_volume_surface(const float* voxels, const float origin[3],
         if (S < 1) throw_error("%s: S = %d samples per ray (at least 1)", who, S);
         if (!std::isfinite(iso)) throw_error("%s: iso must be finite", who);
         if (refine < 0 || refine > MAX_REFINE) throw_error("%s: refine = %d outside [0, %d]", who, refine, MAX_REFINE);
-        if (R < 0 || rays_per_view < 1 || row_rays < 1) throw_error("%s: R=%d rays_per_view=%d row_rays=%d", who, R, rays_per_view, row_rays);
-        if (R % rays_per_view != 0) throw_error("%s: R = %d is not a whole number of views of %d rays", who, R, rays_per_view);
-        if (rays_per_view % row_rays != 0) throw_error("%s: rays_per_view = %d is not a whole number of rows of %d rays", who, rays_per_view, row_rays);
-        const int V = R / rays_per_view;
-        if (V > 65535) throw_error("%s: %d views (at most 65535)", who, V);
+        const int V = check_ray_grid(who, R, rays_per_view, row_rays);
         if (R == 0) return;
-        SurfGrid G;
-        for (int a = 0; a < 3; ++a) { G.o[a] = origin[a]; G.s[a] = spacing[a]; }
-        G.nx = nx; G.ny = ny; G.nz = nz;
-        const int rows = rays_per_view / row_rays;
-        const dim3 blocks((unsigned)(((row_rays + VS_TX - 1) / VS_TX) * ((rows + VS_TY - 1) / VS_TY)), (unsigned)V);
-        hipLaunchKernelGGL(volume_surface_kernel, blocks, dim3(64 * VS_WAVES), 0, (hipStream_t)stream, voxels, G, iso, refine, rays_d, cam_pos, z, hit,
+        hipLaunchKernelGGL(volume_surface_kernel, tile_blocks(row_rays, rays_per_view / row_rays, V), dim3(64 * RAY_WAVES), 0, (hipStream_t)stream, voxels,
+                           make_grid(origin, spacing, nx, ny, nz), iso, refine, rays_d, cam_pos, z, hit,
                            rays_per_view, row_rays, S, depth, reinterpret_cast<float4*>(normal), color, found);
         HIP_CHECK(hipGetLastError());
     });

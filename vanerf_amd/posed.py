@@ -17,7 +17,7 @@ from ctypes import c_void_p
 import torch
 
 from ._ffi import check, lib
-from .baked import _add_vert_xy, _check_out, _check_rays, _check_volume, _view_rays
+from .baked import _add_vert_xy, _beta_args, _check_rays, _check_volume, _march_out, _view_rays
 from .mask_at_box import frame_bounds
 from .surface import _dev_ptr, _f3, _stream
 
@@ -57,7 +57,6 @@ def march_volume_posed(volume, T, face, sdf, rays_d, cam_pos, z, hit, reach=REAC
     POSED mesh at renderer.sample_points of the same rays -> color (V, R, 3), depth (V, R), alpha (V, R).  A sample is empty when face is
     outside [0, nf), sdf is not finite or sdf > reach (reach: any float but NaN; inf disables it); the others read the volume at A p + t.
     row_rays, out: as march_volume takes them; every element of out is written.  One launch."""
-    from . import renderer as R
     nx, ny, nz = _check_volume(volume)
     V, Rn, S, ptrs = _check_rays(volume, rays_d, cam_pos, z, hit)
     dev = volume.voxels.device
@@ -73,17 +72,12 @@ def march_volume_posed(volume, T, face, sdf, rays_d, cam_pos, z, hit, reach=REAC
     if reach != reach:
         raise ValueError("reach: expected a number (inf disables it), got NaN")
     row_rays = Rn if row_rays is None else int(row_rays)
-    by_handle = isinstance(volume.beta, R.PackedWeights)
-    if by_handle and volume.beta.device_index is not None and volume.beta.device_index != dev.index:
-        raise ValueError(f"volume.beta: the weight handle lives on device {volume.beta.device_index}, the voxels on {dev}")
+    handle, beta = _beta_args(volume)
     with torch.cuda.device(dev):
-        if out is None:
-            out = (torch.empty(V, Rn, 3, dtype=torch.float32, device=dev), *(torch.empty(V, Rn, dtype=torch.float32, device=dev) for _ in range(2)))
-        color, depth, alpha = _check_out(out, (((V, Rn, 3), torch.float32, "color"), ((V, Rn), torch.float32, "depth"), ((V, Rn), torch.float32, "alpha")), dev)
-        check(lib.vanerf_volume_render_posed(c_void_p(volume.voxels.data_ptr()), _f3(volume.origin), _f3(volume.spacing), nx, ny, nz,
-                                             volume.beta.handle if by_handle else None, 0.0 if by_handle else float(volume.beta), *ptrs, V * Rn, Rn, row_rays,
-                                             S, tp, T.shape[0], fp, sp, reach, c_void_p(color.data_ptr()), c_void_p(depth.data_ptr()),
-                                             c_void_p(alpha.data_ptr()), _stream()))
+        color, depth, alpha = _march_out(out, V, Rn, dev)
+        check(lib.vanerf_volume_render_posed(c_void_p(volume.voxels.data_ptr()), _f3(volume.origin), _f3(volume.spacing), nx, ny, nz, handle, beta, *ptrs,
+                                             V * Rn, Rn, row_rays, S, tp, T.shape[0], fp, sp, reach, c_void_p(color.data_ptr()),
+                                             c_void_p(depth.data_ptr()), c_void_p(alpha.data_ptr()), _stream()))
     return color, depth, alpha
 
 
