@@ -677,6 +677,59 @@ int vanerf_volume_render_posed(const float* voxels, const float origin[3], const
                                int row_rays, int S, const float* T, int nf, const int32_t* face, const float* sdf, float reach, float* color,
                                float* depth, float* alpha, void* stream);
 
+/* Linear blend skinning of a MANO-shaped model for a batch of P poses: pose, shape and translation parameters -> the
+ * vertices and joints of every pose, on the device, with no host read.  What follows is the definition (it is what smplx 0.1.x computes with
+ * lbs and pose2rot = True, restated so that nothing here points anywhere else).
+ *
+ * The MODEL has nv vertices, nj joints (1 .. 32) and nb shape coefficients (1 .. 16), and carries, all fp32 and row-major:
+ *     v_template[nv][3];  shapedirs[nv][3][nb];  posedirs[(nj-1)*9][nv*3]: row (j-1)*9 + 3r + c belongs to joint j >= 1 and entry (r, c) of its
+ *     rotation, column 3v + k to vertex v and coordinate k;  J_regressor[nj][nv];  weights[nv][nj];  hands_mean[(nj-1)*3];  and parents[nj]
+ *     (int32) with parents[0] = -1 and 0 <= parents[j] < j.  With nj = 1 posedirs and hands_mean are empty and may be null.
+ * For one pose row pose[nj*3] (axis-angle per joint, the root first), betas[nb] and trans[3]:
+ *     1. full = pose; unless flat_hand_mean is set, full[3:] += hands_mean.
+ *     2. v_shaped = v_template + shapedirs . betas;  J = J_regressor . v_shaped  (= J_regressor . v_template + (J_regressor . shapedirs) . betas).
+ *     3. per joint j, with r = full[3j .. 3j+2]: angle = sqrt((r0 + 1e-8)^2 + (r1 + 1e-8)^2 + (r2 + 1e-8)^2) -- the constant is added to every
+ *        component and enters the norm only -- d = r / angle, K = [[0, -d2, d1], [d2, 0, -d0], [-d1, d0, 0]] and
+ *        R_j = I + sin(angle) K + (1 - cos(angle)) K K.  r = 0 gives R_j = I exactly.
+ *     4. v_posed = v_shaped + posedirs^T . f, the pose feature f[(j-1)*9 + 3r + c] = (R_j - I)[r][c] for j = 1 .. nj-1.
+ *     5. the chain: L_j = [R_j | J_j - J_parents[j]] (3 x 4; J_0 itself for the root), G_0 = L_0 and G_j = G_parents[j] L_j as rigid maps
+ *        (G^R = Gp^R L^R, G^t = Gp^R L^t + Gp^t).  A_j = [G_j^R | G_j^t - G_j^R J_j].
+ *     6. vertex v = (sum_j weights[v][j] A_j) . (v_posed_v, 1) + trans;  joint j = G_j^t + trans.
+ *     7. the seal (n_ring > 0): ONE more vertex, index nv, is appended: the mean of the vertices ring[0 .. n_ring-1].  Its arithmetic is fixed:
+ *        in fp32, s = x[ring[0]], then s = s + x[ring[u]] for u = 1 .. n_ring-1 over the vertices as WRITTEN by this call, times
+ *        (1.0f / (float)n_ring) -- so the appended vertex equals that expression of the call's own output bit for bit.
+ * Where the arithmetic happens: steps 1, 3, 5, J of step 2 and the joints of step 6 in fp64 (sin, cos and sqrt of the device's fp64 library),
+ * sums from the left, each rounded ONCE to fp32: A, f and the joints.  Steps 2 (v_shaped), 4 and the vertices of step 6 in fp32, every
+ * product and sum its own IEEE operation, in this order: s = 0, s = s + shapedirs[v][k][b] * betas[b] for b = 0 .. nb-1, x = v_template + s;
+ * o = 0, o = o + posedirs[row][3v+k] * f[row] for row = 0 .. (nj-1)*9 - 1, x = x + o; T = 0, T = T + weights[v][j] * A_j for j = 0 .. nj-1 (no
+ * term is skipped: a NaN or an infinity in a pose's parameters reaches every vertex of that pose, and no other pose);
+ * out_k = ((T_k0 x_0 + T_k1 x_1) + T_k2 x_2) + T_k3, then out_k + trans_k.  A pose's bits depend neither on P nor on its row in the batch.
+ *
+ *     vanerf_mano_packed_bytes (nv, nj, nb) -> the size of a model's packed tables;  vanerf_mano_workspace_bytes (nj, P) -> the workspace of a
+ *         call with P poses;  vanerf_mano_poses_per_lane () -> how many poses a lane of the vertex kernel carries (P just below, at and above it
+ *         are the batch sizes at which a block's last poses are, or are not, past the batch).  Host only; bad sizes give a negative error code.
+ *     vanerf_mano_pack: the model's arrays (DEVICE pointers; parents a HOST pointer, checked here) -> packed (DEVICE, 16-byte aligned, at least
+ *         vanerf_mano_packed_bytes): the tables transposed to [row][k][v], J_regressor . v_template and J_regressor . shapedirs in fp64 (sums
+ *         over the vertices from vertex 0), hands_mean as doubles and the parents.  Once per model; two launches.  The known sign error of the
+ *         left hand's shapedirs in the files smplx reads is the caller's data preparation: nothing is flipped here.
+ *     vanerf_mano_skin: packed with the SAME nv, nj, nb, and pose, betas, trans as P rows `*_stride` floats apart (DEVICE) -> verts: P rows
+ *         verts_stride floats apart, each (nv + (n_ring > 0)) x 3 floats, and joints: P rows joints_stride floats apart, each nj x 3 floats.
+ *         The strides let the right and the left hand read from, and write into, the halves of one tensor.  Every stride is at least its
+ *         row's length; rows must not overlap.  ring: a HOST pointer to n_ring ids in [0, nv), 0 <= n_ring <= 64; n_ring = 0: no seal (ring
+ *         may be null).  workspace: DEVICE, at least vanerf_mano_workspace_bytes, contents undefined before and after.  P = 0 is valid and a
+ *         no-op.  Launches: one wave per pose for the joints, one lane per vertex carrying several poses for the vertices, one thread per
+ *         pose and coordinate for the seal.
+ * All work goes to `stream`; no allocation, no host synchronisation, no atomics, no device-side state; every output element is written on every
+ * call: the same bits every call.  Arguments are checked before any launch.                                                               */
+int64_t vanerf_mano_packed_bytes(int nv, int nj, int nb);
+int64_t vanerf_mano_workspace_bytes(int nj, int P);
+int vanerf_mano_poses_per_lane(void);
+int vanerf_mano_pack(const float* v_template, const float* shapedirs, const float* posedirs, const float* J_regressor, const float* weights,
+                     const int32_t* parents, const float* hands_mean, int nv, int nj, int nb, void* packed, int64_t packed_bytes, void* stream);
+int vanerf_mano_skin(const void* packed, int nv, int nj, int nb, const float* pose, int64_t pose_stride, const float* betas, int64_t betas_stride,
+                     const float* trans, int64_t trans_stride, int P, int flat_hand_mean, const int32_t* ring, int n_ring, void* workspace,
+                     int64_t workspace_bytes, float* verts, int64_t verts_stride, float* joints, int64_t joints_stride, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,433 @@
+// mano_skin.hip -- linear blend skinning of a MANO-shaped model for a batch of poses (the comment of vanerf_mano_skin in
+// the header): pose, shape and translation parameters -> the frame's vertices and joints, on the device, no host read.  The restatement the
+// tests hold these kernels to is the numpy code of tests/test_mano_skin_cpu.py.
+//
+// Three stages per call, all on the caller's stream:
+//   mano_joint_kernel   one wave per pose.  Lane j: Rodrigues of joint j and J_j from the fp64 joint tables; then the chain joint by joint
+//                       (parents[j] < j, so a loop over j is every tree's order), the twelve elements of G_j on twelve lanes, through LDS.
+//                       All fp64, as the small fp64 cores of vis_vertex_kernel and pose_transforms_kernel.  A (nj x 12) and the pose feature
+//                       ((nj - 1) x 9, R_j - I) are rounded once to fp32 into the workspace; the joints are rounded once into the output.
+//   mano_vertex_kernel  one lane per vertex and MANO_POSES_PER_LANE poses per lane: every value of the transposed tables ([row][k][v]:
+//                       consecutive lanes read consecutive vertices) serves all of a lane's poses.  A, the pose feature, betas and trans of the
+//                       block's poses sit in LDS and are read with wave-uniform indices.  fp32, every product and sum its own IEEE operation
+//                       (-ffp-contract=off), in one fixed order: a pose's bits depend neither on P nor on its place in the batch.
+//   mano_seal_kernel    the appended wrist vertex: the fp32 sum of the WRITTEN ring vertices in the ring's order, from the left, times 1 / n.
+// The pack (once per model) transposes the tables and folds J_regressor into the template and the shape directions in fp64, so that J costs
+// 3 nj nb products per pose instead of a pass over the vertices.  No atomics, no device-side state; every output element is written.
+#include "common.h"
+
+#include <cmath>
+#include <cstdint>
+
+using namespace vanerf;
+
+#ifndef MANO_POSES_PER_LANE
+#define MANO_POSES_PER_LANE 4 // poses a lane of mano_vertex_kernel carries (tools/perf_mano.py times builds with another count)
+#endif
+
+namespace {
+
+constexpr int MANO_MAX_NJ = 32;
+constexpr int MANO_MAX_NB = 16;
+constexpr int MANO_MAX_RING = 64;
+constexpr int MV_BLOCK = 256;
+constexpr int PP = MANO_POSES_PER_LANE;
+static_assert(PP >= 1 && PP <= 16, "MANO_POSES_PER_LANE: 1 .. 16");
+
+// The packed model: a host-side description of one device buffer.  fp64 tables first (the buffer is 16-byte aligned), then parents, then the
+// transposed fp32 tables.
+struct ManoTables {
+    const double* Jt;      // [nj][3]        J_regressor . v_template
+    const double* Js;      // [nj][3][nb]    J_regressor . shapedirs
+    const double* hm;      // [nj][3]        hands_mean as doubles, zeros for the root
+    const int32_t* parents; // [nj]
+    const float* vt;       // [3][nv]
+    const float* sd;       // [nb][3][nv]
+    const float* pd;       // [(nj-1)*9][3][nv]
+    const float* wt;       // [nj][nv]
+};
+
+struct ManoLayout {
+    int64_t Jt, Js, hm, parents, vt, sd, pd, wt, bytes;
+};
+
+ManoLayout mano_layout(int nv, int nj, int nb)
+{
+    ManoLayout L;
+    int64_t at = 0;
+    L.Jt = at; at += (int64_t)nj * 3 * 8;
+    L.Js = at; at += (int64_t)nj * 3 * nb * 8;
+    L.hm = at; at += (int64_t)nj * 3 * 8;
+    L.parents = at; at += (int64_t)((nj + 3) / 4 * 4) * 4;
+    L.vt = at; at += (int64_t)3 * nv * 4;
+    L.sd = at; at += (int64_t)nb * 3 * nv * 4;
+    L.pd = at; at += (int64_t)(nj - 1) * 9 * 3 * nv * 4;
+    L.wt = at; at += (int64_t)nj * nv * 4;
+    L.bytes = (at + 15) / 16 * 16;
+    return L;
+}
+
+ManoTables mano_tables(const void* packed, int nv, int nj, int nb)
+{
+    const ManoLayout L = mano_layout(nv, nj, nb);
+    const char* b = static_cast<const char*>(packed);
+    ManoTables t;
+    t.Jt = reinterpret_cast<const double*>(b + L.Jt);
+    t.Js = reinterpret_cast<const double*>(b + L.Js);
+    t.hm = reinterpret_cast<const double*>(b + L.hm);
+    t.parents = reinterpret_cast<const int32_t*>(b + L.parents);
+    t.vt = reinterpret_cast<const float*>(b + L.vt);
+    t.sd = reinterpret_cast<const float*>(b + L.sd);
+    t.pd = reinterpret_cast<const float*>(b + L.pd);
+    t.wt = reinterpret_cast<const float*>(b + L.wt);
+    return t;
+}
+
+inline int ws_floats(int nj) { return nj * 12 + (nj - 1) * 9; } // per pose: A, then the pose feature
+
+void check_sizes(const char* who, int nv, int nj, int nb)
+{
+    if (nv < 1) throw_error("%s: nv=%d vertices (at least 1)", who, nv);
+    if (nj < 1 || nj > MANO_MAX_NJ) throw_error("%s: nj=%d joints (1 .. %d)", who, nj, MANO_MAX_NJ);
+    if (nb < 1 || nb > MANO_MAX_NB) throw_error("%s: nb=%d shape coefficients (1 .. %d)", who, nb, MANO_MAX_NB);
+    if ((int64_t)nv * 3 * (int64_t)(nj - 1) * 9 > 0x7fffffffLL) throw_error("%s: posedirs of nv=%d nj=%d has more than 2^31 - 1 values", who, nv, nj);
+}
+
+struct IntList32 { int32_t v[MANO_MAX_NJ]; };
+struct IntList64 { int32_t v[MANO_MAX_RING]; };
+
+// ------------------------------------------------------------------------------------------------------------------------------------------
+// pack
+// ------------------------------------------------------------------------------------------------------------------------------------------
+// One thread per value of the transposed fp32 tables.
+__global__ __launch_bounds__(MV_BLOCK) void mano_pack_tables_kernel(const float* __restrict__ v_template, const float* __restrict__ shapedirs,
+                                                                   const float* __restrict__ posedirs, const float* __restrict__ weights, int nv, int nj,
+                                                                   int nb, float* __restrict__ vt, float* __restrict__ sd, float* __restrict__ pd,
+                                                                   float* __restrict__ wt)
+{
+    const size_t i = (size_t)blockIdx.x * MV_BLOCK + threadIdx.x;
+    const size_t n_vt = (size_t)3 * nv, n_sd = (size_t)nb * 3 * nv, n_pd = (size_t)(nj - 1) * 9 * 3 * nv, n_wt = (size_t)nj * nv;
+    if (i < n_vt) {
+        const size_t k = i / nv, v = i % nv;
+        vt[i] = v_template[v * 3 + k];
+    } else if (i < n_vt + n_sd) {
+        const size_t o = i - n_vt, b = o / ((size_t)3 * nv), k = o / nv % 3, v = o % nv;
+        sd[o] = shapedirs[(v * 3 + k) * nb + b];
+    } else if (i < n_vt + n_sd + n_pd) {
+        const size_t o = i - n_vt - n_sd, row = o / ((size_t)3 * nv), k = o / nv % 3, v = o % nv;
+        pd[o] = posedirs[row * ((size_t)3 * nv) + v * 3 + k];
+    } else if (i < n_vt + n_sd + n_pd + n_wt) {
+        const size_t o = i - n_vt - n_sd - n_pd, j = o / nv, v = o % nv;
+        wt[o] = weights[v * nj + j];
+    }
+}
+
+// One thread per value of the joint tables: (j, k, c), c = 0 the template and c = 1 + b shape direction b; the sum over the vertices in
+// fp64, from vertex 0 upwards.  The first threads also write hands_mean as doubles and the parents.
+__global__ __launch_bounds__(64) void mano_pack_joints_kernel(const float* __restrict__ v_template, const float* __restrict__ shapedirs,
+                                                             const float* __restrict__ J_regressor, const float* __restrict__ hands_mean,
+                                                             const IntList32 parents, int nv, int nj, int nb, double* __restrict__ Jt,
+                                                             double* __restrict__ Js, double* __restrict__ hm, int32_t* __restrict__ par)
+{
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i < nj * 3) hm[i] = i < 3 ? 0.0 : (double)hands_mean[i - 3];
+    if (i < nj) {
+        int32_t p = -1;
+#pragma unroll
+        for (int u = 0; u < MANO_MAX_NJ; ++u) p = u == i ? parents.v[u] : p; // (compile-time indices: the list stays in scalar registers)
+        par[i] = p;
+    }
+    if (i >= nj * 3 * (nb + 1)) return;
+    const int c = i % (nb + 1), k = i / (nb + 1) % 3, j = i / (nb + 1) / 3;
+    const float* reg = J_regressor + (size_t)j * nv;
+    double s = 0.0;
+    for (int v = 0; v < nv; ++v) {
+        const double x = c == 0 ? (double)v_template[(size_t)v * 3 + k] : (double)shapedirs[((size_t)v * 3 + k) * nb + (c - 1)];
+        s = s + (double)reg[v] * x;
+    }
+    if (c == 0) Jt[j * 3 + k] = s;
+    else Js[(j * 3 + k) * nb + (c - 1)] = s;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------------------
+// joints: one wave per pose, fp64
+// ------------------------------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void mano_joint_kernel(const ManoTables t, int nj, int nb, const float* __restrict__ pose, int64_t pose_stride,
+                                                       const float* __restrict__ betas, int64_t betas_stride, const float* __restrict__ trans,
+                                                       int64_t trans_stride, int flat_hand_mean, float* __restrict__ ws, float* __restrict__ joints,
+                                                       int64_t joints_stride)
+{
+    __shared__ double sR[MANO_MAX_NJ][9], sJ[MANO_MAX_NJ][3], sG[MANO_MAX_NJ][12];
+    const size_t p = blockIdx.x;
+    const int lane = threadIdx.x;
+    const int wsf = nj * 12 + (nj - 1) * 9;
+    float* A = ws + p * wsf;
+    float* pf = A + nj * 12;
+    if (lane < nj) {
+        double r[3];
+        for (int k = 0; k < 3; ++k) r[k] = (double)pose[p * pose_stride + 3 * lane + k] + (flat_hand_mean ? 0.0 : t.hm[3 * lane + k]);
+        const double e0 = r[0] + 1e-8, e1 = r[1] + 1e-8, e2 = r[2] + 1e-8; // the constant enters the norm only
+        const double angle = sqrt((e0 * e0 + e1 * e1) + e2 * e2);
+        const double dx = r[0] / angle, dy = r[1] / angle, dz = r[2] / angle;
+        const double s = sin(angle), c1 = 1.0 - cos(angle);
+        // R - I = sin K + (1 - cos) K^2 with K = skew(d); r = 0 gives d = 0 and R = I exactly
+        double m[9];
+        m[0] = c1 * -(dz * dz + dy * dy);
+        m[1] = s * -dz + c1 * (dx * dy);
+        m[2] = s * dy + c1 * (dx * dz);
+        m[3] = s * dz + c1 * (dx * dy);
+        m[4] = c1 * -(dz * dz + dx * dx);
+        m[5] = s * -dx + c1 * (dy * dz);
+        m[6] = s * -dy + c1 * (dx * dz);
+        m[7] = s * dx + c1 * (dy * dz);
+        m[8] = c1 * -(dx * dx + dy * dy);
+        for (int e = 0; e < 9; ++e) {
+            sR[lane][e] = (e % 4 == 0 ? 1.0 : 0.0) + m[e];
+            if (lane >= 1) pf[(lane - 1) * 9 + e] = (float)m[e];
+        }
+        for (int k = 0; k < 3; ++k) {
+            double sum = 0.0;
+            for (int b = 0; b < nb; ++b) sum = sum + t.Js[(lane * 3 + k) * nb + b] * (double)betas[p * betas_stride + b];
+            sJ[lane][k] = t.Jt[lane * 3 + k] + sum;
+        }
+    }
+    __syncthreads();
+    // the chain, joint by joint; element (row, col) of G_j on lane 4 row + col
+    const int row = (lane >> 2) % 3, col = lane & 3;
+    for (int j = 0; j < nj; ++j) {
+        if (lane < 12) {
+            double g;
+            if (j == 0) {
+                g = col < 3 ? sR[0][row * 3 + col] : sJ[0][row];
+            } else {
+                int par = t.parents[j];
+                par = par < 0 ? 0 : (par > j - 1 ? j - 1 : par); // (checked at the pack; a foreign buffer must not index outside the block's LDS)
+                const double* G = sG[par];
+                double l0, l1, l2;
+                if (col < 3) { l0 = sR[j][col]; l1 = sR[j][3 + col]; l2 = sR[j][6 + col]; }
+                else { l0 = sJ[j][0] - sJ[par][0]; l1 = sJ[j][1] - sJ[par][1]; l2 = sJ[j][2] - sJ[par][2]; }
+                g = (G[row * 4] * l0 + G[row * 4 + 1] * l1) + G[row * 4 + 2] * l2;
+                if (col == 3) g = g + G[row * 4 + 3];
+            }
+            sG[j][row * 4 + col] = g;
+        }
+        __syncthreads();
+    }
+    if (lane < nj) {
+        const double* G = sG[lane];
+        for (int k = 0; k < 3; ++k) {
+            for (int c = 0; c < 3; ++c) A[lane * 12 + k * 4 + c] = (float)G[k * 4 + c];
+            A[lane * 12 + k * 4 + 3] = (float)(G[k * 4 + 3] - ((G[k * 4] * sJ[lane][0] + G[k * 4 + 1] * sJ[lane][1]) + G[k * 4 + 2] * sJ[lane][2]));
+            joints[p * joints_stride + 3 * lane + k] = (float)(G[k * 4 + 3] + (double)trans[p * trans_stride + k]);
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------------------
+// vertices: one lane per vertex, PP poses per lane, fp32
+// ------------------------------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(MV_BLOCK) void mano_vertex_kernel(const ManoTables t, int nv, int nj, int nb, int nvb, const float* __restrict__ betas,
+                                                              int64_t betas_stride, const float* __restrict__ trans, int64_t trans_stride, int P,
+                                                              const float* __restrict__ ws, float* __restrict__ verts, int64_t verts_stride)
+{
+    extern __shared__ float sm[]; // per pose of the block: A [nj][12], pose feature [(nj-1)*9], betas [nb], trans [3]
+    const int wsf = nj * 12 + (nj - 1) * 9, per = wsf + nb + 3;
+    const size_t p0 = (size_t)(blockIdx.x / nvb) * PP;
+    const int vb = blockIdx.x % nvb;
+    for (int i = threadIdx.x; i < PP * per; i += MV_BLOCK) {
+        const int q = i / per, o = i % per;
+        size_t p = p0 + q;
+        p = p < (size_t)P ? p : (size_t)P - 1; // past the batch: the last pose again, computed and not written
+        sm[i] = o < wsf ? ws[p * wsf + o] : o < wsf + nb ? betas[p * betas_stride + (o - wsf)] : trans[p * trans_stride + (o - wsf - nb)];
+    }
+    __syncthreads();
+    const int v = vb * MV_BLOCK + threadIdx.x;
+    if (v >= nv) return;
+    const size_t n = (size_t)nv;
+    float acc[PP][3], vp[PP][3];
+    const float t0 = t.vt[v], t1 = t.vt[n + v], t2 = t.vt[2 * n + v];
+    // v_shaped = v_template + (sum over b, from b = 0, of shapedirs_b betas_b)
+#pragma unroll
+    for (int q = 0; q < PP; ++q) acc[q][0] = acc[q][1] = acc[q][2] = 0.0f;
+    for (int b = 0; b < nb; ++b) {
+        const float x0 = t.sd[(size_t)(b * 3) * n + v], x1 = t.sd[(size_t)(b * 3 + 1) * n + v], x2 = t.sd[(size_t)(b * 3 + 2) * n + v];
+#pragma unroll
+        for (int q = 0; q < PP; ++q) {
+            const float be = sm[q * per + wsf + b];
+            acc[q][0] = acc[q][0] + x0 * be;
+            acc[q][1] = acc[q][1] + x1 * be;
+            acc[q][2] = acc[q][2] + x2 * be;
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < PP; ++q) {
+        vp[q][0] = t0 + acc[q][0];
+        vp[q][1] = t1 + acc[q][1];
+        vp[q][2] = t2 + acc[q][2];
+        acc[q][0] = acc[q][1] = acc[q][2] = 0.0f;
+    }
+    // v_posed = v_shaped + (sum over the rows, from row 0, of posedirs_row feature_row)
+    const int rows = (nj - 1) * 9;
+    for (int r = 0; r < rows; ++r) {
+        const float x0 = t.pd[(size_t)(r * 3) * n + v], x1 = t.pd[(size_t)(r * 3 + 1) * n + v], x2 = t.pd[(size_t)(r * 3 + 2) * n + v];
+#pragma unroll
+        for (int q = 0; q < PP; ++q) {
+            const float f = sm[q * per + nj * 12 + r];
+            acc[q][0] = acc[q][0] + x0 * f;
+            acc[q][1] = acc[q][1] + x1 * f;
+            acc[q][2] = acc[q][2] + x2 * f;
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < PP; ++q) {
+        vp[q][0] = vp[q][0] + acc[q][0];
+        vp[q][1] = vp[q][1] + acc[q][1];
+        vp[q][2] = vp[q][2] + acc[q][2];
+    }
+    // T = sum over j, from j = 0, of w_vj A_j
+    float T[PP][12];
+#pragma unroll
+    for (int q = 0; q < PP; ++q)
+#pragma unroll
+        for (int e = 0; e < 12; ++e) T[q][e] = 0.0f;
+    for (int j = 0; j < nj; ++j) {
+        const float w = t.wt[(size_t)j * n + v];
+#pragma unroll
+        for (int q = 0; q < PP; ++q)
+#pragma unroll
+            for (int e = 0; e < 12; ++e) T[q][e] = T[q][e] + w * sm[q * per + j * 12 + e];
+    }
+#pragma unroll
+    for (int q = 0; q < PP; ++q) {
+        if (p0 + q < (size_t)P) { // (block-uniform)
+            float* o = verts + (p0 + q) * verts_stride + (size_t)v * 3;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const float x = ((T[q][4 * k] * vp[q][0] + T[q][4 * k + 1] * vp[q][1]) + T[q][4 * k + 2] * vp[q][2]) + T[q][4 * k + 3];
+                o[k] = x + sm[q * per + wsf + nb + k];
+            }
+        }
+    }
+}
+
+// The appended vertex: one thread per pose and coordinate; the ring's ids are kernel arguments read with compile-time indices.
+__global__ __launch_bounds__(MV_BLOCK) void mano_seal_kernel(float* __restrict__ verts, int64_t verts_stride, int nv, int P, const IntList64 ring, int n_ring)
+{
+    const size_t i = (size_t)blockIdx.x * MV_BLOCK + threadIdx.x;
+    if (i >= (size_t)P * 3) return;
+    float* rowp = verts + (i / 3) * verts_stride;
+    const int k = (int)(i % 3);
+    float s = rowp[(size_t)ring.v[0] * 3 + k];
+#pragma unroll
+    for (int u = 1; u < MANO_MAX_RING; ++u)
+        if (u < n_ring) s = s + rowp[(size_t)ring.v[u] * 3 + k];
+    rowp[(size_t)nv * 3 + k] = s * (1.0f / (float)n_ring);
+}
+
+unsigned blocks_of(const char* who, int64_t n, int per)
+{
+    const int64_t b = (n + per - 1) / per;
+    if (b > 0x7fffffffLL) throw_error("%s: %lld blocks exceed a launch's 2^31 - 1", who, (long long)b);
+    return (unsigned)b;
+}
+
+} // namespace
+
+extern "C" int64_t vanerf_mano_packed_bytes(int nv, int nj, int nb)
+{
+    int64_t bytes = -1;
+    const int rc = guarded([&] {
+        check_sizes("vanerf_mano_packed_bytes", nv, nj, nb);
+        bytes = mano_layout(nv, nj, nb).bytes;
+    });
+    return rc == VANERF_OK ? bytes : (int64_t)rc;
+}
+
+extern "C" int64_t vanerf_mano_workspace_bytes(int nj, int P)
+{
+    int64_t bytes = -1;
+    const int rc = guarded([&] {
+        if (nj < 1 || nj > MANO_MAX_NJ) throw_error("vanerf_mano_workspace_bytes: nj=%d joints (1 .. %d)", nj, MANO_MAX_NJ);
+        if (P < 0) throw_error("vanerf_mano_workspace_bytes: P=%d poses (at least 0)", P);
+        bytes = (int64_t)P * ws_floats(nj) * 4;
+    });
+    return rc == VANERF_OK ? bytes : (int64_t)rc;
+}
+
+extern "C" int vanerf_mano_poses_per_lane(void) { return PP; }
+
+extern "C" int vanerf_mano_pack(const float* v_template, const float* shapedirs, const float* posedirs, const float* J_regressor, const float* weights,
+                                const int32_t* parents, const float* hands_mean, int nv, int nj, int nb, void* packed, int64_t packed_bytes, void* stream)
+{
+    return guarded([&] {
+        const char* who = "vanerf_mano_pack";
+        if (!v_template || !shapedirs || !J_regressor || !weights || !parents || !packed) throw_error("%s: null argument", who);
+        check_sizes(who, nv, nj, nb);
+        if (nj > 1 && (!posedirs || !hands_mean)) throw_error("%s: null argument (posedirs and hands_mean are needed with nj=%d)", who, nj);
+        if (parents[0] != -1) throw_error("%s: parents[0]=%d (the root has parent -1)", who, parents[0]);
+        IntList32 par;
+        for (int j = 0; j < MANO_MAX_NJ; ++j) par.v[j] = -1;
+        for (int j = 1; j < nj; ++j) {
+            if (parents[j] < 0 || parents[j] >= j) throw_error("%s: parents[%d]=%d (expected 0 <= parents[j] < j)", who, j, parents[j]);
+            par.v[j] = parents[j];
+        }
+        const ManoLayout L = mano_layout(nv, nj, nb);
+        if (packed_bytes < L.bytes) throw_error("%s: packed_bytes=%lld, the model needs %lld (vanerf_mano_packed_bytes)", who, (long long)packed_bytes, (long long)L.bytes);
+        if ((uintptr_t)packed & 15) throw_error("%s: packed must be 16-byte aligned", who);
+        const ManoTables t = mano_tables(packed, nv, nj, nb);
+        const int64_t n_float = (L.bytes - L.vt) / 4;
+        const unsigned b_tab = blocks_of(who, n_float, MV_BLOCK), b_j = blocks_of(who, (int64_t)nj * 3 * (nb + 1), 64);
+        hipLaunchKernelGGL(mano_pack_tables_kernel, dim3(b_tab), dim3(MV_BLOCK), 0, (hipStream_t)stream, v_template, shapedirs, posedirs, weights, nv, nj, nb,
+                           const_cast<float*>(t.vt), const_cast<float*>(t.sd), const_cast<float*>(t.pd), const_cast<float*>(t.wt));
+        HIP_CHECK(hipGetLastError());
+        hipLaunchKernelGGL(mano_pack_joints_kernel, dim3(b_j), dim3(64), 0, (hipStream_t)stream, v_template, shapedirs, J_regressor, hands_mean, par, nv, nj, nb,
+                           const_cast<double*>(t.Jt), const_cast<double*>(t.Js), const_cast<double*>(t.hm), const_cast<int32_t*>(t.parents));
+        HIP_CHECK(hipGetLastError());
+    });
+}
+
+extern "C" int vanerf_mano_skin(const void* packed, int nv, int nj, int nb, const float* pose, int64_t pose_stride, const float* betas,
+                                int64_t betas_stride, const float* trans, int64_t trans_stride, int P, int flat_hand_mean, const int32_t* ring, int n_ring,
+                                void* workspace, int64_t workspace_bytes, float* verts, int64_t verts_stride, float* joints, int64_t joints_stride, void* stream)
+{
+    return guarded([&] {
+        const char* who = "vanerf_mano_skin";
+        check_sizes(who, nv, nj, nb);
+        if (P < 0) throw_error("%s: P=%d poses (at least 0)", who, P);
+        if (n_ring < 0 || n_ring > MANO_MAX_RING) throw_error("%s: n_ring=%d (0 = no seal .. %d)", who, n_ring, MANO_MAX_RING);
+        if (n_ring > 0 && !ring) throw_error("%s: null argument (ring with n_ring=%d)", who, n_ring);
+        IntList64 rg;
+        for (int u = 0; u < MANO_MAX_RING; ++u) rg.v[u] = 0;
+        for (int u = 0; u < n_ring; ++u) {
+            if (ring[u] < 0 || ring[u] >= nv) throw_error("%s: ring[%d]=%d names no vertex of nv=%d", who, u, ring[u], nv);
+            rg.v[u] = ring[u];
+        }
+        const int64_t row = ((int64_t)nv + (n_ring > 0 ? 1 : 0)) * 3;
+        if (pose_stride < (int64_t)nj * 3) throw_error("%s: pose_stride=%lld is below a row's %d floats", who, (long long)pose_stride, nj * 3);
+        if (betas_stride < nb) throw_error("%s: betas_stride=%lld is below a row's %d floats", who, (long long)betas_stride, nb);
+        if (trans_stride < 3) throw_error("%s: trans_stride=%lld is below a row's 3 floats", who, (long long)trans_stride);
+        if (verts_stride < row) throw_error("%s: verts_stride=%lld is below a row's %lld floats", who, (long long)verts_stride, (long long)row);
+        if (joints_stride < (int64_t)nj * 3) throw_error("%s: joints_stride=%lld is below a row's %d floats", who, (long long)joints_stride, nj * 3);
+        if (P == 0) return;
+        if (!packed || !pose || !betas || !trans || !workspace || !verts || !joints) throw_error("%s: null argument", who);
+        if ((uintptr_t)packed & 15) throw_error("%s: packed must be 16-byte aligned", who);
+        const int64_t need = (int64_t)P * ws_floats(nj) * 4;
+        if (workspace_bytes < need) throw_error("%s: workspace_bytes=%lld, %d poses need %lld (vanerf_mano_workspace_bytes)", who, (long long)workspace_bytes, P, (long long)need);
+        const int nvb = (nv + MV_BLOCK - 1) / MV_BLOCK;
+        const unsigned b_v = blocks_of(who, (int64_t)((P + PP - 1) / PP) * nvb, 1);
+        const unsigned b_s = blocks_of(who, (int64_t)P * 3, MV_BLOCK);
+        const ManoTables t = mano_tables(packed, nv, nj, nb);
+        float* ws = static_cast<float*>(workspace);
+        hipLaunchKernelGGL(mano_joint_kernel, dim3((unsigned)P), dim3(64), 0, (hipStream_t)stream, t, nj, nb, pose, pose_stride, betas, betas_stride, trans,
+                           trans_stride, flat_hand_mean, ws, joints, joints_stride);
+        HIP_CHECK(hipGetLastError());
+        const size_t lds = (size_t)PP * (ws_floats(nj) + nb + 3) * sizeof(float);
+        hipLaunchKernelGGL(mano_vertex_kernel, dim3(b_v), dim3(MV_BLOCK), lds, (hipStream_t)stream, t, nv, nj, nb, nvb, betas, betas_stride, trans, trans_stride,
+                           P, ws, verts, verts_stride);
+        HIP_CHECK(hipGetLastError());
+        if (n_ring > 0) {
+            hipLaunchKernelGGL(mano_seal_kernel, dim3(b_s), dim3(MV_BLOCK), 0, (hipStream_t)stream, verts, verts_stride, nv, P, rg, n_ring);
+            HIP_CHECK(hipGetLastError());
+        }
+    });
+}

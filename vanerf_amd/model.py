@@ -657,6 +657,13 @@ class VANeRF(nn.Module):
         vol = baked.bake_volume(self, tr_batch, resolution=resolution) if volume is None else volume
         return posed.render_posed_views(vol, posed._frame_faces(tr_batch, vol.voxels.device), verts_pose, cam_tars, **kwargs)
 
+    @torch.no_grad()
+    def mano_sequence(self, tr_batch, right, left, pose, betas, trans, cam_tars, **kwargs):
+        """The hand of tr_batch animated by a MANO pose track: vanerf_amd.posed.mano_sequence on this module (kwargs: its
+        flat_hand_mean, seal, resolution, samples, reach, volume).  The frames as a list."""
+        from . import posed
+        return list(posed.mano_sequence(self, tr_batch, right, left, pose, betas, trans, cam_tars, **kwargs))
+
     def attach_autograd(self, out, img_in, feat_geo, feat_tex, targets, sp_data, fg_mask):
         """Replaces the differentiable entries of `out` (a batch_render_pifu_nerf result computed with _autograd=True) by tensors that
         carry the HIP values and, in backward, the gradients of the networks evaluated at the same samples (same points, same importance

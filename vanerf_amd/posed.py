@@ -9,7 +9,8 @@ the posed surface are empty.
 This is a PREVIEW, like the baked volume itself: it approximates the field under the usual surface-aligned deformation model (each point
 moves with its closest face; nothing is smoothed across face boundaries).  It does not claim what VANeRF would render from a photograph of
 the new pose: the networks are conditioned on the source image and the source mesh, and are not evaluated here.  Poses arrive as vertices;
-MANO skinning is the caller's.
+mano_sequence takes MANO pose, shape and translation parameters instead and skins them on the device first (vanerf_amd/mano.py, DESIGN.md
+section 0j).
 """
 import dataclasses
 from ctypes import c_void_p
@@ -163,4 +164,15 @@ def posed_sequence(net, tr_batch, poses, cam_tars, resolution=128, samples=128, 
     return frames()
 
 
-__all__ = ["REACH", "pose_transforms", "march_volume_posed", "render_posed_volume", "render_posed_views", "posed_sequence"]
+def mano_sequence(net, tr_batch, right, left, pose, betas, trans, cam_tars, flat_hand_mean=False, seal=True, resolution=128, samples=128, reach=REACH,
+                  volume=None):
+    """posed_sequence driven by a pose track: right, left are mano.ManoModels and pose (P, 2, nj*3), betas (P, 2, nb), trans (P, 2, 3) the
+    parameters of P frames, the right hand at index 0.  All P poses are skinned in ONE mano.skin_two_hands call, on the device, when this is
+    called; the result is posed_sequence's generator on those vertices (one bake, at the first frame, unless volume= hands one in): the same
+    bits as posed_sequence fed with skin_two_hands' vertices.  The skinned frame must have the topology of tr_batch's mesh."""
+    from . import mano
+    verts, _ = mano.skin_two_hands(right, left, pose, betas, trans, flat_hand_mean=flat_hand_mean, seal=seal)
+    return posed_sequence(net, tr_batch, [verts[p] for p in range(verts.shape[0])], cam_tars, resolution, samples, reach, volume)
+
+
+__all__ = ["REACH", "pose_transforms", "march_volume_posed", "render_posed_volume", "render_posed_views", "posed_sequence", "mano_sequence"]

@@ -120,6 +120,34 @@ def nested_shells():
     return np.concatenate([sv, inner], 0).astype(np.float32), np.concatenate([sf, sf + sv.shape[0]], 0)
 
 
+def mano_like_model(seed, nv=778, nj=16, nb=10, parents=None):
+    """A seeded model of MANO's shapes for vanerf_amd.mano (no licensed file): a dict of numpy arrays under smplx's names, ready for
+    ManoModel.from_arrays(**model).  v_template (nv, 3): the points of fingered_hand(seed) (past 779 they repeat, shifted by a millimetre per
+    round); shapedirs (nv, 3, nb) with sigma 2 mm and posedirs ((nj-1)*9, nv*3) with sigma 1 mm; J_regressor (nj, nv): per joint up to eight
+    vertices with non-negative weights that sum to 1; weights (nv, nj): per vertex up to four joints, likewise; hands_mean ((nj-1)*3) with
+    sigma 0.2 rad.  parents: default the wrist with fingers of three joints each, parents[j] = 0 if (j - 1) % 3 == 0 else j - 1, which is
+    MANO's tree at nj = 16."""
+    rng = np.random.RandomState(seed)
+    base, _ = fingered_hand(seed)
+    i = np.arange(nv)
+    v_template = (base[i % NV_HAND].astype(np.float64) + 1e-3 * (i // NV_HAND)[:, None]).astype(np.float32)
+    shapedirs = (2e-3 * rng.standard_normal((nv, 3, nb))).astype(np.float32)
+    posedirs = (1e-3 * rng.standard_normal(((nj - 1) * 9, nv * 3))).astype(np.float32)
+    J_regressor = np.zeros((nj, nv), dtype=np.float64)
+    for j in range(nj):
+        ids = rng.choice(nv, size=min(8, nv), replace=False)
+        J_regressor[j, ids] = rng.dirichlet(np.ones(len(ids)))
+    weights = np.zeros((nv, nj), dtype=np.float64)
+    for v in range(nv):
+        ids = rng.choice(nj, size=min(4, nj), replace=False)
+        weights[v, ids] = rng.dirichlet(np.ones(len(ids)))
+    hands_mean = (0.2 * rng.standard_normal((nj - 1) * 3)).astype(np.float32)
+    if parents is None:
+        parents = [-1] + [0 if (j - 1) % 3 == 0 else j - 1 for j in range(1, nj)]
+    return {"v_template": v_template, "shapedirs": shapedirs, "posedirs": posedirs, "J_regressor": J_regressor.astype(np.float32),
+            "weights": weights.astype(np.float32), "parents": np.asarray(parents, dtype=np.int32), "hands_mean": hands_mean}
+
+
 def look_at_extrinsic(eye, target, up=(0.0, -1.0, 0.0)):
     """World->camera 4x4 (x right, y down, z forward)."""
     eye, target, up = (np.asarray(a, dtype=np.float64) for a in (eye, target, up))
