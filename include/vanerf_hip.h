@@ -677,6 +677,39 @@ int vanerf_volume_render_posed(const float* voxels, const float origin[3], const
                                int row_rays, int S, const float* T, int nf, const int32_t* face, const float* sdf, float reach, float* color,
                                float* depth, float* alpha, void* stream);
 
+/* The surface of the baked volume as a camera sees it in ANOTHER POSE of the same mesh: vanerf_volume_surface's depth,
+ * normal and colour maps along rays through the POSED hand.  The grid, rays, layouts, iso and refine (0 .. 4) are vanerf_volume_surface's;
+ * T[nf][12], face[R][S], sdf[R][S] and reach are vanerf_volume_render_posed's; voxels, T and normal 16-byte aligned; any S >= 1; nf >= 1;
+ * V <= 65535; R == 0 is a no-op.  -> depth[R], normal[R][4] = (nx, ny, nz, n . v), color[R][3], found[R] (0, 1, 2 or 3).  Per ray, all in fp32,
+ * every product and sum its own operation:
+ *     - hit == 0: found = 0 and every output is +0.
+ *     - sample i is EMPTY by vanerf_volume_render_posed's rule, unchanged: face < 0, face >= nf, sdf not finite or sdf > reach.  For a face F,
+ *       q_F(zz) = A_F p + t_F with p = o + d zz per axis, qx = ((A00 px + A01 py) + A02 pz) + tx and likewise for y and z, and g_F(zz) is
+ *       channel 0 of vanerf_volume_render's trilinear interpolation at q_F(zz).  Sample i has g_i = g_face_i(z_i).  It is INSIDE iff it is not
+ *       empty and g_i < iso: an empty sample is outside, and g == iso is outside.
+ *     - sample 0 inside: found = 2, z* = z_0, F = face_0.  With S == 1 this is the only way to be found.
+ *     - otherwise the smallest k with sample k not inside and sample k + 1 inside.  None: found = 0 and every output is +0.
+ *       F = face_k+1: the map of the INSIDE end carries the whole bracket, because the refinement points have no mesh query of their own.
+ *       za = z_k, zb = z_k+1, gb = g_k+1, and ga = g_F(z_k), re-evaluated under F whatever sample k was (empty, or carried by another face).
+ *     - ga < iso: found = 3 and z* = za.  Under F's map the surface lies at or in front of sample k; the depth is held at the bracket's near
+ *       end and nothing is refined.
+ *     - otherwise found = 1: `refine` rounds of vanerf_volume_surface's 65-way split with g_F (one (outside, inside) pair always exists), then
+ *       its linear step, w = fminf(fmaxf((iso - ga) / (gb - ga), 0), 1), z* = za + w * (zb - za).
+ *     - at q* = q_F(z*): color = channels 1..3 of the interpolation, G = vanerf_volume_surface's clamped central difference of channel 0 in
+ *       SOURCE space.  The normal in POSED space is the gradient of f(A p + t) with respect to p, N = A^T G:
+ *       N_j = (A_0j G_0 + A_1j G_1) + A_2j G_2.  Then vanerf_volume_surface's normalisation of N (m = max |N_j|; m == 0 or not finite: the
+ *       normal and n . v are 0; scaled by 1 / m first) and n . v = fmaxf(0, -((n . d) / |d|)) with the POSED ray's d.  depth = z*.
+ * One wave per ray, the samples over the lanes in rounds of 64 ("was the last sample inside" carried into the next), coalesced loads of face
+ * and sdf and three 16-byte loads of the record per live lane; a round all of whose samples are empty issues no gather (the same bits either
+ * way); "not inside there, inside here" is a 64-bit ballot, the march stops at the first round with a crossing, and F comes by shuffle from
+ * the crossing lane: from there on the record is wave-uniform.  All pointers but origin and spacing are DEVICE pointers.  All work goes to
+ * `stream`; no allocation, no host synchronisation, no atomics, no device-side state; every output element is written on every call: the same
+ * bits every call.  Arguments are checked before any launch.  One launch.                                                                  */
+int vanerf_volume_surface_posed(const float* voxels, const float origin[3], const float spacing[3], int nx, int ny, int nz, float iso, int refine,
+                                const float* rays_d, const float* cam_pos, const float* z, const uint8_t* hit, int R, int rays_per_view, int row_rays,
+                                int S, const float* T, int nf, const int32_t* face, const float* sdf, float reach, float* depth, float* normal,
+                                float* color, uint8_t* found, void* stream);
+
 /* Linear blend skinning of a MANO-shaped model for a batch of P poses: pose, shape and translation parameters -> the
  * vertices and joints of every pose, on the device, with no host read.  What follows is the definition (it is what smplx 0.1.x computes with
  * lbs and pose2rot = True, restated so that nothing here points anywhere else).

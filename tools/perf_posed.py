@@ -7,6 +7,8 @@ the frame's vertices under a smooth bend, the cameras are a get_360cameras orbit
   * in the same run: render_baked_views (section 0g: no pose, no mesh query) and the exact pass (64 + 64 samples) on the same cameras.
 --dump FILE marches seeded host-made inputs instead (no network, no timing) and writes the group's colour, depth and alpha at the first sample
 count to FILE (.npz): two builds of the library (VANERF_HIP_LIB; e.g. one with -DVANERF_POSED_NO_SKIP) are compared bit for bit through it.
+--surface times the geometry path instead, per sample count on posed_samples of the group: march_surface_posed and
+march_volume_posed on the SAME prepared samples, the mesh query, render_posed_surface_views per view, and the share of found rays with found == 3.
 Kernel times: rocprofv3 --kernel-trace --stats -d <dir> -- python tools/perf_posed.py (volume_render_posed_kernel, pose_transforms_kernel)."""
 import argparse
 import os
@@ -75,6 +77,34 @@ def dump(a):
     print(f"wrote {a.dump}")
 
 
+def surface(a, vol, faces, pose, cams, fmt):
+    """--surface: the march of section 0k next to the colour march of the same prepared samples, the query both wait for, and whole frames."""
+    V, Rn = len(cams), a.image * a.image
+    accel = R.MeshAccel(pose, faces)
+    no_vis = torch.zeros(pose.shape[0], device="cuda")
+    for S in a.samples:
+        p = posed.posed_samples(vol, faces, pose, cams, samples=S, accel=accel)
+        tail = (p.T, p.face, p.sdf, p.rays_d, p.cam_pos, p.z, p.hit)
+        found = posed.march_surface_posed(vol, *tail, refine=a.refine, reach=a.reach, row_rays=p.row_rays)[3]
+        seen = int((found != 0).sum())
+        print(f"{S:3d} samples: {seen} of {found.numel()} rays found ({100 * seen / found.numel():.1f} %); found == 1 / 2 / 3: "
+              + " / ".join(str(int((found == k).sum())) for k in (1, 2, 3)) + f"; found == 3 on {100 * int((found == 3).sum()) / max(seen, 1):.2f} % of the found rays")
+        t_s = median_ms(lambda: posed.march_surface_posed(vol, *tail, refine=a.refine, reach=a.reach, row_rays=p.row_rays), a.calls, a.reps)
+        print(f"{S:3d} samples: surface march (march_surface_posed, refine {a.refine}): {fmt(t_s)} per group, {t_s[0] / V:8.3f} ms per view")
+        t_c = median_ms(lambda: posed.march_volume_posed(vol, *tail, a.reach, row_rays=p.row_rays), a.calls, a.reps)
+        print(f"{S:3d} samples: colour march of the same samples (march_volume_posed): {fmt(t_c)} per group, {t_c[0] / V:8.3f} ms per view; "
+              f"surface / colour = {t_s[0] / t_c[0]:.2f}", flush=True)
+        pts = R.sample_points(p.rays_d.view(-1, 3), p.cam_pos, p.z.view(-1, S), rays_per_view=Rn)
+        t = median_ms(lambda: R.mesh_query_accel(accel, pose, faces, no_vis, pts, want_face=True, want_knn=False, grid=(a.image, V * a.image, S)), a.calls, a.reps)
+        print(f"{S:3d} samples: mesh query (face, sdf) of {pts.shape[0] / 1e6:.1f} M points: {fmt(t)} per group, {t[0] / V:8.3f} ms per view", flush=True)
+        del pts
+        t = median_ms(lambda: posed.render_posed_surface_views(vol, faces, pose, cams, S, refine=a.refine, reach=a.reach, accel=accel), a.calls, a.reps)
+        print(f"{S:3d} samples: render_posed_surface_views with accel= handed in, group of {V}: {fmt(t)} per group, {t[0] / V:8.3f} ms per view")
+        t = median_ms(lambda: posed.render_posed_surface_views(vol, faces, pose, cams, S, refine=a.refine, reach=a.reach, prepared=p), a.calls, a.reps)
+        print(f"{S:3d} samples: render_posed_surface_views with prepared= handed in (march + images): {fmt(t)} per group, {t[0] / V:8.3f} ms per view", flush=True)
+        del p, tail
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--size", type=int, default=128)
@@ -86,6 +116,8 @@ def main():
     ap.add_argument("--reach", type=float, default=posed.REACH)
     ap.add_argument("--precision", default="bf16x3")
     ap.add_argument("--dump", default=None)
+    ap.add_argument("--surface", action="store_true")
+    ap.add_argument("--refine", type=int, default=1)
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("perf_posed.py measures on the GPU: no device found")
@@ -117,6 +149,8 @@ def main():
         nx, ny, nz = vol.dims
         print(f"{a.image} x {a.image}, {V} orbit views [{a.precision}]; grid {nx} x {ny} x {nz}; {faces.shape[0]} faces; reach {a.reach}; "
               f"the bend moves the vertices by up to {1e3 * float((pose - vol.verts).norm(dim=1).max()):.1f} mm", flush=True)
+        if a.surface:
+            return surface(a, vol, faces, pose, cams, fmt)
         t = median_ms(lambda: posed.pose_transforms(vol.verts, pose, faces), 20, a.reps)
         print(f"pose_transforms: {fmt(t)}")
         t = median_ms(lambda: R.MeshAccel(pose, faces), 20, a.reps)

@@ -140,6 +140,8 @@ _SIGS = {
     "vanerf_pose_transforms": (c_int, [_FP, _FP, c_int, _FP, c_int, _FP, c_void_p]),
     "vanerf_volume_render_posed": (c_int, [_FP, POINTER(c_float), POINTER(c_float), c_int, c_int, c_int, c_void_p, c_float, _FP, _FP, _FP, _FP, c_int, c_int,
                                            c_int, c_int, _FP, c_int, _FP, _FP, c_float, _FP, _FP, _FP, c_void_p]),
+    "vanerf_volume_surface_posed": (c_int, [_FP, POINTER(c_float), POINTER(c_float), c_int, c_int, c_int, c_float, c_int, _FP, _FP, _FP, _FP, c_int, c_int,
+                                            c_int, c_int, _FP, c_int, _FP, _FP, c_float, _FP, _FP, _FP, _FP, c_void_p]),
     "vanerf_mano_packed_bytes": (c_int64, [c_int, c_int, c_int]),
     "vanerf_mano_workspace_bytes": (c_int64, [c_int, c_int]),
     "vanerf_mano_poses_per_lane": (c_int, []),

@@ -274,6 +274,15 @@ def _check_surface(iso, refine):
     return iso, refine
 
 
+def _surface_out(out, V, Rn, dev):
+    """(depth (V, Rn), normal (V, Rn, 4), color (V, Rn, 3), found (V, Rn) uint8) of a surface march on dev: the caller's `out`, checked, or new tensors."""
+    if out is None:
+        out = (torch.empty(V, Rn, dtype=torch.float32, device=dev), torch.empty(V, Rn, 4, dtype=torch.float32, device=dev),
+               torch.empty(V, Rn, 3, dtype=torch.float32, device=dev), torch.empty(V, Rn, dtype=torch.uint8, device=dev))
+    return _check_out(out, (((V, Rn), torch.float32, "depth"), ((V, Rn, 4), torch.float32, "normal"), ((V, Rn, 3), torch.float32, "color"),
+                            ((V, Rn), torch.uint8, "found")), dev)
+
+
 def march_surface(volume, rays_d, cam_pos, z, hit, iso=0.0, refine=1, row_rays=None, out=None):
     """vanerf_volume_surface on the rays march_volume takes (rays_d (V, R, 3), cam_pos (V, 4), z (V, R, S), hit (V, R) uint8, on the volume's
     device) -> depth (V, R), normal (V, R, 4) = (nx, ny, nz, n . v), color (V, R, 3) fp32 and found (V, R) uint8.  Per ray the first sample
@@ -287,11 +296,7 @@ def march_surface(volume, rays_d, cam_pos, z, hit, iso=0.0, refine=1, row_rays=N
     dev = volume.voxels.device
     row_rays = Rn if row_rays is None else int(row_rays)
     with torch.cuda.device(dev):
-        if out is None:
-            out = (torch.empty(V, Rn, dtype=torch.float32, device=dev), torch.empty(V, Rn, 4, dtype=torch.float32, device=dev),
-                   torch.empty(V, Rn, 3, dtype=torch.float32, device=dev), torch.empty(V, Rn, dtype=torch.uint8, device=dev))
-        depth, normal, color, found = _check_out(out, (((V, Rn), torch.float32, "depth"), ((V, Rn, 4), torch.float32, "normal"),
-                                                       ((V, Rn, 3), torch.float32, "color"), ((V, Rn), torch.uint8, "found")), dev)
+        depth, normal, color, found = _surface_out(out, V, Rn, dev)
         check(lib.vanerf_volume_surface(c_void_p(volume.voxels.data_ptr()), _f3(volume.origin), _f3(volume.spacing), nx, ny, nz, iso, refine, *ptrs,
                                         V * Rn, Rn, row_rays, S, c_void_p(depth.data_ptr()), c_void_p(normal.data_ptr()), c_void_p(color.data_ptr()),
                                         c_void_p(found.data_ptr()), _stream()))
@@ -330,10 +335,20 @@ def render_baked_surface_views(volume, cam_tars, samples=128, iso=0.0, refine=1,
         tex_fg (3, H, W) by `mode`: "shaded" colour x shade, "clay" 0.8 shade, "normal" normal_img, "depth" (zfar - depth) / (zfar - znear);
     these three hold `background` where found == 0.  tex_fg_fine is the same tensor as tex_fg (what novel_views.arrange_nerf_images reads),
     vert_xy as in render_baked_views.  The images are elementwise torch ops on H x W; no host read."""
+    _check_mode(mode)
+    cam_tars = list(cam_tars)
+    return _surface_frames(render_volume_surface(volume, cam_tars, samples, iso, refine), volume, cam_tars, mode, ambient, background)
+
+
+def _check_mode(mode):
     if mode not in SURFACE_MODES:
         raise ValueError(f"mode: expected one of {SURFACE_MODES}, got {mode!r}")
-    cam_tars = list(cam_tars)
-    o = render_volume_surface(volume, cam_tars, samples, iso, refine)
+
+
+def _surface_frames(o, volume, cam_tars, mode, ambient, background):
+    """The image half of render_baked_surface_views, which documents the formulas: o, the maps of a surface march over whole frames of the
+    cameras cam_tars (render_volume_surface's dict, or posed.render_posed_surface's) -> one dict per camera.  A pixel is seen iff
+    found != 0; vert_xy comes from volume.verts."""
     cams, (width, height) = _cameras(volume, cam_tars)
     dev = volume.voxels.device
     ambient, background = float(ambient), float(background)

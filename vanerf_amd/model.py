@@ -664,6 +664,22 @@ class VANeRF(nn.Module):
         from . import posed
         return list(posed.mano_sequence(self, tr_batch, right, left, pose, betas, trans, cam_tars, **kwargs))
 
+    @torch.no_grad()
+    def render_posed_surface_views(self, tr_batch, verts_pose, cam_tars, resolution=128, volume=None, **kwargs):
+        """Depth, normal and shaded views of the hand of tr_batch in ANOTHER pose of its mesh: the frame baked at
+        `resolution` (bake_volume, unless volume= hands one in) and vanerf_amd.posed.render_posed_surface_views (kwargs: its samples, iso, refine,
+        reach, bounds, accel, prepared, mode, ambient, background) on it.  The same preview as render_posed_views, seen as geometry."""
+        from . import baked, posed
+        vol = baked.bake_volume(self, tr_batch, resolution=resolution) if volume is None else volume
+        return posed.render_posed_surface_views(vol, posed._frame_faces(tr_batch, vol.voxels.device), verts_pose, cam_tars, **kwargs)
+
+    @torch.no_grad()
+    def mano_surface_sequence(self, tr_batch, right, left, pose, betas, trans, cam_tars, **kwargs):
+        """The geometry frames of a MANO pose track: vanerf_amd.posed.mano_surface_sequence on this module (kwargs: its
+        flat_hand_mean, seal, resolution, samples, reach, volume, iso, refine, mode, ambient, background).  The frames as a list."""
+        from . import posed
+        return list(posed.mano_surface_sequence(self, tr_batch, right, left, pose, betas, trans, cam_tars, **kwargs))
+
     def attach_autograd(self, out, img_in, feat_geo, feat_tex, targets, sp_data, fg_mask):
         """Replaces the differentiable entries of `out` (a batch_render_pifu_nerf result computed with _autograd=True) by tensors that
         carry the HIP values and, in backward, the gradients of the networks evaluated at the same samples (same points, same importance
