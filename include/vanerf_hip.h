@@ -763,6 +763,41 @@ int vanerf_mano_skin(const void* packed, int nv, int nj, int nb, const float* po
                      const float* trans, int64_t trans_stride, int P, int flat_hand_mean, const int32_t* ring, int n_ring, void* workspace,
                      int64_t workspace_bytes, float* verts, int64_t verts_stride, float* joints, int64_t joints_stride, void* stream);
 
+/* The vector-Jacobian product of vanerf_mano_skin: the gradients of a scalar with respect to the vertices and joints of
+ * P poses -> its gradients with respect to pose, betas and trans, on the device, with no host read.  The function differentiated is the
+ * definition above exactly as written, steps 1-7: the constant 1e-8 sits in the angle (so the gradient at r = 0 is finite: sin(angle) / angle
+ * is), hands_mean is an additive constant, and the seal passes (1.0f / (float)n_ring) of the appended vertex's gradient to ring[u] for EVERY
+ * u, so an id that the ring repeats receives it as often as it occurs.  The roundings of the forward are not differentiated.
+ *
+ * Stateless: R, J, the chain, A, the pose feature, v_posed and T are recomputed from pose and betas (the forward's arithmetic and bits); nothing
+ * is taken from a forward call, and trans is not an input.  packed, nv, nj, nb, pose, betas, P, flat_hand_mean, ring and n_ring are the
+ * forward's.  grad_verts: P rows grad_verts_stride floats apart, each (nv + (n_ring > 0)) x 3 floats; grad_joints: P rows of nj x 3 floats.
+ * Either may be null, which is read as zeros; both null is an error.  grad_pose (P rows of nj x 3), grad_betas (P rows of nb) and grad_trans
+ * (P rows of 3), each with its own stride: any may be null, which means not wanted, and every element of the others is written.  The strides
+ * let one hand address its half of a (P, 2, .) tensor; every stride is at least its row's length.  workspace: DEVICE, 8-byte aligned, at least
+ * vanerf_mano_skin_backward_workspace_bytes (nv, nj, nb, P), contents undefined before and after (not read when grad_verts is null).  P = 0
+ * is valid and a no-op.
+ *
+ * Where the arithmetic happens.  Vertex side, fp32, every product and sum its own IEEE operation: x = v_posed and T as the forward computes
+ * them; g = the vertex's gradient, then g = g + (grad of the appended vertex) * (1.0f / n_ring) once per occurrence in the ring's order;
+ * g_x[c] = (T_0c g_0 + T_1c g_1) + T_2c g_2.  The sums over the vertices -- dA_j[r][c] = sum_v (w_vj g_r) (x_c | 1), df[row] = sum_v sum_k
+ * posedirs[row][3v+k] g_x[k], the direct part of grad_betas = sum_v sum_k shapedirs[v][k][b] g_x[k], and sum_v g -- take fp32 products and
+ * add them in fp64: per chunk of 256 vertices, lane l of a wave adds its vertices l, l + 64, l + 128, l + 192 (k innermost), a butterfly adds
+ * the 64 lanes, and the chunks' sums are added in chunk order.  Joint side, fp64: dG_j^t = dA_j^t + grad_joint_j, dG_j^R = dA_j^R - dA_j^t
+ * J_j^T, dJ_j = -G_j^R^T dA_j^t; for j = nj-1 .. 1 with p = parents[j]: dR_j = G_p^R^T dG_j^R, dG_p^R += dG_j^R R_j^T + dG_j^t (J_j - J_p)^T,
+ * dl = G_p^R^T dG_j^t, dJ_j += dl, dJ_p -= dl, dG_p^t += dG_j^t; the root: dR_0 = dG_0^R, dJ_0 += dG_0^t; dR_j += df_j for j >= 1; the
+ * Rodrigues backward of step 3 gives grad_pose; grad_betas = direct part + (J_regressor . shapedirs)^T dJ; grad_trans = sum_v g + sum_j
+ * grad_joint_j.  Each output is rounded once to fp32.  A pose's gradient bits depend neither on P nor on its row in the batch; a NaN in one
+ * pose's gradients stays in that pose.
+ * Three launches (one when grad_verts is null).  All work goes to `stream`; no allocation, no host synchronisation, no atomics, no device-side
+ * state: the same bits every call.  Arguments are checked before any launch.                                                              */
+int64_t vanerf_mano_skin_backward_workspace_bytes(int nv, int nj, int nb, int P);
+int vanerf_mano_skin_backward(const void* packed, int nv, int nj, int nb, const float* pose, int64_t pose_stride, const float* betas,
+                              int64_t betas_stride, int P, int flat_hand_mean, const int32_t* ring, int n_ring, const float* grad_verts,
+                              int64_t grad_verts_stride, const float* grad_joints, int64_t grad_joints_stride, void* workspace,
+                              int64_t workspace_bytes, float* grad_pose, int64_t grad_pose_stride, float* grad_betas, int64_t grad_betas_stride,
+                              float* grad_trans, int64_t grad_trans_stride, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

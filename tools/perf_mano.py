@@ -7,7 +7,12 @@
     the rate that implies, and its share of the HBM bandwidth a copy reaches (6.3 TB/s) and of the L2's (34.5 TB/s); and what the vertex
     kernel actually asks of the L2: the tables once per group of vanerf_mano_poses_per_lane poses.
 The count of poses a lane carries is a build constant: time a library built with VANERF_HIPCC_FLAGS=-DMANO_POSES_PER_LANE=n (vanerf_amd.build,
-out=) by naming it in VANERF_HIP_LIB.  Kernel times: rocprofv3 --kernel-trace --stats -d <dir> -- python tools/perf_mano.py."""
+out=) by naming it in VANERF_HIP_LIB.  Kernel times: rocprofv3 --kernel-trace --stats -d <dir> -- python tools/perf_mano.py.
+`--backward` adds, per P: the backward alone (two vanerf_mano_skin_backward calls into preallocated gradients), and
+skin_two_hands under autograd with torch.autograd.grad for given upstream gradients of the vertices and joints -- forward + backward -- against
+the same of the PyTorch fp32 restatement, with the largest difference between the two sets of gradients relative to each gradient's largest
+value.  `--fit` adds mano.fit_two_hands at `--fit-steps` steps from a tracking start against the same count of steps of torch.optim.Adam on
+the restatement (one loss for both hands), per call and per step."""
 import argparse
 import os
 import statistics
@@ -71,12 +76,73 @@ def torch_hand(m, pose, betas, trans, ring):
     return torch.cat([verts, verts[:, ring].mean(1, keepdim=True)], 1), G[:, :, :3, 3] + trans[:, None]
 
 
+def torch_two_hands(tens, ring_t, pose, betas, trans):
+    vj = [torch_hand(tens[h], pose[:, h], betas[:, h], trans[:, h], ring_t[h]) for h in range(2)]
+    return torch.cat([vj[0][0], vj[1][0]], 1), torch.cat([vj[0][1], vj[1][1]], 1)
+
+
+def backward_rows(a, P, hands, tens, ring_t, pose, betas, trans, fmt):
+    nv, nj = hands[0].nv, hands[0].nj
+    gen = torch.Generator(device="cuda").manual_seed(1)
+    gv, gj = torch.randn(P, 2 * (nv + 1), 3, device="cuda", generator=gen), torch.randn(P, 2 * nj, 3, device="cuda", generator=gen)
+    grads = [torch.empty_like(t) for t in (pose, betas, trans)]
+
+    def backward_alone():
+        for h in range(2):
+            mano._skin_backward(hands[h], pose[:, h], betas[:, h], False, True, gv[:, (nv + 1) * h:(nv + 1) * (h + 1)], gj[:, nj * h:nj * (h + 1)],
+                                out=[g[:, h] for g in grads])
+
+    leaves = [t.clone().requires_grad_() for t in (pose, betas, trans)]
+    by_hip = lambda: torch.autograd.grad(mano.skin_two_hands(*hands, *leaves), leaves, (gv, gj))  # noqa: E731
+    by_torch = lambda: torch.autograd.grad(torch_two_hands(tens, ring_t, *leaves), leaves, (gv, gj))  # noqa: E731
+    tb, th = median_ms(backward_alone, a.calls, a.reps), median_ms(by_hip, a.calls, a.reps)
+    print(f"P={P:5d}: backward alone {fmt(tb)} per call, {1e3 * tb[0] / P:9.3f} us per pose; skin_two_hands forward + backward through autograd {fmt(th)}, "
+          f"{1e3 * th[0] / P:9.3f} us per pose", flush=True)
+    if a.no_torch:
+        return
+    tt = median_ms(by_torch, max(1, a.calls // 4), a.reps)
+    worst = max(float((x - y).abs().max() / y.abs().max()) for x, y in zip(by_hip(), by_torch()))
+    print(f"P={P:5d}: PyTorch fp32 forward + backward {fmt(tt)} per call, {1e3 * tt[0] / P:9.3f} us per pose: {tt[0] / th[0]:6.1f} x the HIP path; "
+          f"largest difference between the gradients, relative to the largest of each, {worst:.2e}", flush=True)
+
+
+def fit_rows(a, P, hands, tens, ring_t, pose, betas, trans, fmt):
+    steps, n = a.fit_steps, hands[0].nv + 1
+    with torch.no_grad():
+        target = mano.skin_two_hands(*hands, pose, betas, trans)[0]
+    gen = torch.Generator(device="cuda").manual_seed(9)
+    init = (pose + 0.2 * torch.randn(pose.shape, device="cuda", generator=gen), torch.zeros_like(betas),
+            trans + 0.02 * torch.randn(trans.shape, device="cuda", generator=gen))
+    tf = median_ms(lambda: mano.fit_two_hands(*hands, target, init=init, steps=steps), max(1, a.calls // 10), a.reps)
+    rms = mano.fit_two_hands(*hands, target, init=init, steps=300)["rms"]
+    print(f"P={P:5d}: fit_two_hands, {steps} steps {fmt(tf)} per call, {1e3 * tf[0] / steps:8.2f} us per step; 300 steps from 0.2 rad / 2 cm off end at "
+          f"{1e3 * float(rms.max()):.4f} mm rms (worst pose and hand)", flush=True)
+    if a.no_torch:
+        return
+
+    def by_torch():
+        leaves = [t.clone().requires_grad_() for t in init]
+        opt = torch.optim.Adam([{"params": [leaves[0]], "lr": 0.03}, {"params": [leaves[1]], "lr": 0.06}, {"params": [leaves[2]], "lr": 0.006}])
+        for _ in range(steps):
+            opt.zero_grad()
+            v = torch_two_hands(tens, ring_t, *leaves)[0]
+            ((v[:, :n] - target[:, :n]) ** 2).sum(-1).mean(1).sum().add(((v[:, n:] - target[:, n:]) ** 2).sum(-1).mean(1).sum()).backward()
+            opt.step()
+
+    tt = median_ms(by_torch, 1, a.reps)
+    print(f"P={P:5d}: torch.optim.Adam on the PyTorch fp32 restatement, {steps} steps {fmt(tt)} per call, {1e3 * tt[0] / steps:8.2f} us per step: "
+          f"{tt[0] / tf[0]:6.1f} x the HIP path", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--poses", type=int, nargs="+", default=[1, 64, 1024])
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--calls", type=int, default=20)
     ap.add_argument("--no-torch", action="store_true", help="time the HIP path only (for comparing builds)")
+    ap.add_argument("--backward", action="store_true", help="also time the backward and forward + backward against PyTorch autograd")
+    ap.add_argument("--fit", action="store_true", help="also time mano.fit_two_hands against torch.optim.Adam on the restatement")
+    ap.add_argument("--fit-steps", type=int, default=50)
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("perf_mano.py measures on the GPU: no device found")
@@ -105,20 +171,17 @@ def main():
         print(f"P={P:5d}: skin_two_hands {fmt(t)} per call, {1e3 * t[0] / P:9.3f} us per pose; must move {must / 1e6:8.2f} MB = {rate / 1e9:7.1f} GB/s, "
               f"{100 * rate / HBM_COPY:5.2f} % of HBM copy rate, {100 * rate / L2_RATE:5.2f} % of L2; the vertex kernel asks the L2 for {asked / 1e6:8.1f} MB "
               f"= {asked / (t[0] * 1e-3) / 1e12:5.2f} TB/s", flush=True)
-        if a.no_torch:
-            continue
-
-        def by_torch():
-            vj = [torch_hand(tens[h], pose[:, h], betas[:, h], trans[:, h], ring_t[h]) for h in range(2)]
-            return torch.cat([vj[0][0], vj[1][0]], 1), torch.cat([vj[0][1], vj[1][1]], 1)
-
-        with torch.no_grad():
-            tt = median_ms(by_torch, max(1, a.calls // 4), a.reps)
-            ref = by_torch()
-        worst = max(float((ref[0] - out[0]).abs().max()), float((ref[1] - out[1]).abs().max()))
-        print(f"P={P:5d}: PyTorch fp32 restatement {fmt(tt)} per call, {1e3 * tt[0] / P:9.3f} us per pose: {tt[0] / t[0]:6.1f} x the HIP path; "
-              f"largest difference between the two {worst:.2e}", flush=True)
-
+        if not a.no_torch:
+            with torch.no_grad():
+                tt = median_ms(lambda: torch_two_hands(tens, ring_t, pose, betas, trans), max(1, a.calls // 4), a.reps)
+                ref = torch_two_hands(tens, ring_t, pose, betas, trans)
+            worst = max(float((ref[0] - out[0]).abs().max()), float((ref[1] - out[1]).abs().max()))
+            print(f"P={P:5d}: PyTorch fp32 restatement {fmt(tt)} per call, {1e3 * tt[0] / P:9.3f} us per pose: {tt[0] / t[0]:6.1f} x the HIP path; "
+                  f"largest difference between the two {worst:.2e}", flush=True)
+        if a.backward:
+            backward_rows(a, P, hands, tens, ring_t, pose, betas, trans, fmt)
+        if a.fit:
+            fit_rows(a, P, hands, tens, ring_t, pose, betas, trans, fmt)
 
 if __name__ == "__main__":
     main()

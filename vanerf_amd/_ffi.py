@@ -148,6 +148,9 @@ _SIGS = {
     "vanerf_mano_pack": (c_int, [_FP, _FP, _FP, _FP, _FP, POINTER(c_int), _FP, c_int, c_int, c_int, c_void_p, c_int64, c_void_p]),
     "vanerf_mano_skin": (c_int, [c_void_p, c_int, c_int, c_int, _FP, c_int64, _FP, c_int64, _FP, c_int64, c_int, c_int, POINTER(c_int), c_int, c_void_p,
                                  c_int64, _FP, c_int64, _FP, c_int64, c_void_p]),
+    "vanerf_mano_skin_backward_workspace_bytes": (c_int64, [c_int, c_int, c_int, c_int]),
+    "vanerf_mano_skin_backward": (c_int, [c_void_p, c_int, c_int, c_int, _FP, c_int64, _FP, c_int64, c_int, c_int, POINTER(c_int), c_int, _FP, c_int64, _FP,
+                                          c_int64, c_void_p, c_int64, _FP, c_int64, _FP, c_int64, _FP, c_int64, c_void_p]),
 }
 EXPORTS = tuple(_SIGS)
 

@@ -3,6 +3,10 @@ poses -> the frame's vertices and joints, in one call, on the device, with no ho
 include/vanerf_hip.h (what smplx computes with lbs and pose2rot=True); the output plugs straight into posed.render_posed_views and
 posed.posed_sequence (posed.mano_sequence does it).
 
+The opposite direction (vanerf_amd/csrc/mano_skin_backward.hip): skin_hand and skin_two_hands are differentiable with
+respect to pose, betas and trans (vanerf_mano_skin_backward, first order), and fit_hand / fit_two_hands recover the parameters of a mesh in the
+model's topology by Adam on the device.
+
 The licensed MANO file is not part of this project: a model comes in as arrays (ManoModel.from_arrays, or from_npz for arrays saved under
 smplx's attribute names).  The known sign error of the LEFT hand's shapedirs in the files smplx reads (shapedirs[:, 0, :] has the right hand's
 sign) is the caller's data preparation; nothing is flipped here.  synth.mano_like_model draws a seeded model of MANO's shapes.
@@ -12,6 +16,7 @@ from ctypes import c_void_p
 
 import numpy as np
 import torch
+from torch.autograd.function import once_differentiable
 
 from ._ffi import check, lib
 from .surface import _stream
@@ -130,12 +135,8 @@ def _out_rows(t, n, P, dev, what):
     return c_void_p(t.data_ptr()), (t.stride(0) if P > 1 else 3 * n)
 
 
-def skin_hand(model, pose, betas, trans, flat_hand_mean=False, seal=True, out=None):
-    """vanerf_mano_skin: pose (P, nj*3) axis-angle per joint with the root first, betas (P, nb), trans (P, 3), fp32 on the model's device (rows
-    contiguous; the row stride is free, so one hand of a (P, 2, .) tensor is passed as a view) -> verts (P, nv + 1, 3) with the wrist sealed by
-    the mean of model.seal_ring as its last vertex (seal=False: (P, nv, 3)) and joints (P, nj, 3).  flat_hand_mean=False adds the model's
-    hands_mean to the finger poses, as the reference's layers do.  out=(verts, joints): written in place (views of a larger tensor are
-    fine); every element is written.  P = 0 is valid."""
+def _skin(model, pose, betas, trans, flat_hand_mean=False, seal=True, out=None):
+    """skin_hand without autograd: the checks and the one call into the library."""
     for t, what in ((pose, "pose"), (betas, "betas"), (trans, "trans")):
         if not torch.is_tensor(t) or not t.is_cuda:
             raise ValueError(f"{what}: expected a fp32 device tensor (no CPU fallback)")
@@ -166,10 +167,124 @@ def skin_hand(model, pose, betas, trans, flat_hand_mean=False, seal=True, out=No
     return verts, joints
 
 
-def skin_two_hands(right, left, pose, betas, trans, flat_hand_mean=False, seal=True, out=None):
-    """The frame's mesh: pose (P, 2, nj*3), betas (P, 2, nb), trans (P, 2, 3) with the RIGHT hand at index 0 -> verts (P, nvr + nvl, 3), right
-    then left (each nv + 1 vertices when sealed: (P, 1558, 3) for MANO), and joints (P, 2 nj, 3).  Two skin_hand calls that read the halves of
-    the inputs and write the halves of the outputs in place: no copy, and the same bits as those calls."""
+def _wants_grad(*tensors):
+    return torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in tensors)
+
+
+def _grad_rows(t, n, P, dev, what):
+    """An upstream gradient (P, n, 3), or None -> (the tensor to keep alive, pointer or None, row stride).  Whatever layout autograd hands over
+    (an expanded scalar, a transposed view) is made contiguous; a half of a contiguous (P, n + m, 3) tensor is taken as it is."""
+    if t is None:
+        return None, None, 3 * n
+    if t.dtype != torch.float32 or tuple(t.shape) != (P, n, 3) or t.device != dev:
+        raise ValueError(f"{what}: expected a fp32 tensor ({P}, {n}, 3) on {dev}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+    if P > 0 and n > 0 and (t.stride(2) != 1 or (n > 1 and t.stride(1) != 3) or (P > 1 and t.stride(0) < 3 * n)):
+        t = t.contiguous()
+    return t, c_void_p(t.data_ptr()), (t.stride(0) if P > 1 else 3 * n)
+
+
+def _skin_backward(model, pose, betas, flat_hand_mean, seal, grad_verts, grad_joints, want=(True, True, True), out=None):
+    """vanerf_mano_skin_backward: the gradients of the vertices (P, nv + seal, 3) and joints (P, nj, 3) -- either may be None, which is zeros
+    -> (grad_pose, grad_betas, grad_trans), None where `want` says not wanted.  out=(gp, gb, gt): written in place (one hand's half of a
+    (P, 2, .) tensor is a view); entries that are not wanted are ignored."""
+    dev, P = model.device, pose.shape[0]
+    pp, ps = _rows(pose, model.nj * 3, None, dev, "pose")
+    bp, bs = _rows(betas, model.nb, P, dev, "betas")
+    if seal and model.seal_ring is None:
+        raise ValueError("seal=True: the model carries no seal_ring")
+    ring, n_ring = _ring_arg(model.seal_ring if seal else None, model.nv)
+    nvo = model.nv + (1 if seal else 0)
+    with torch.cuda.device(dev):
+        gv, gvp, gvs = _grad_rows(grad_verts, nvo, P, dev, "grad_verts")
+        gj, gjp, gjs = _grad_rows(grad_joints, model.nj, P, dev, "grad_joints")
+        if gv is None and gj is None:
+            raise ValueError("grad_verts, grad_joints: both are None (nothing to differentiate)")
+        grads, ptrs = [], []
+        for i, (cols, what) in enumerate(((model.nj * 3, "grad_pose"), (model.nb, "grad_betas"), (3, "grad_trans"))):
+            if not want[i]:
+                grads.append(None)
+                ptrs += [None, cols]
+                continue
+            g = out[i] if out is not None and out[i] is not None else torch.empty(P, cols, dtype=torch.float32, device=dev)
+            grads.append(g)
+            ptrs += list(_rows(g, cols, P, dev, what))
+        nbytes = lib.vanerf_mano_skin_backward_workspace_bytes(model.nv, model.nj, model.nb, P)
+        if nbytes < 0:
+            check(int(nbytes))
+        ws = torch.empty(max(int(nbytes), 8), dtype=torch.uint8, device=dev)
+        check(lib.vanerf_mano_skin_backward(c_void_p(model.packed.data_ptr()), model.nv, model.nj, model.nb, pp, ps, bp, bs, P, int(bool(flat_hand_mean)),
+                                            ring, n_ring, gvp, gvs, gjp, gjs, c_void_p(ws.data_ptr()), nbytes, *ptrs, _stream()))
+    return tuple(grads)
+
+
+class _SkinHand(torch.autograd.Function):
+    """skin_hand under autograd: the forward is _skin (the same call, the same bits); the backward recomputes what it needs from pose and betas."""
+
+    @staticmethod
+    def forward(ctx, model, flat_hand_mean, seal, pose, betas, trans):
+        ctx.model, ctx.flat, ctx.seal = model, flat_hand_mean, seal
+        ctx.save_for_backward(pose, betas)
+        ctx.set_materialize_grads(False)
+        return _skin(model, pose, betas, trans, flat_hand_mean, seal)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_verts, grad_joints):
+        want = tuple(ctx.needs_input_grad[3:6])
+        if (grad_verts is None and grad_joints is None) or not any(want):
+            return (None,) * 6
+        pose, betas = ctx.saved_tensors
+        return (None, None, None) + _skin_backward(ctx.model, pose, betas, ctx.flat, ctx.seal, grad_verts, grad_joints, want)
+
+
+class _SkinTwoHands(torch.autograd.Function):
+    """skin_two_hands under autograd: two backward calls that read the halves of the gradients and write the halves of (P, 2, .) tensors."""
+
+    @staticmethod
+    def forward(ctx, right, left, flat_hand_mean, seal, pose, betas, trans):
+        ctx.hands, ctx.flat, ctx.seal = (right, left), flat_hand_mean, seal
+        ctx.save_for_backward(pose, betas)
+        ctx.set_materialize_grads(False)
+        return _skin_two(right, left, pose, betas, trans, flat_hand_mean, seal)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_verts, grad_joints):
+        want = tuple(ctx.needs_input_grad[4:7])
+        if (grad_verts is None and grad_joints is None) or not any(want):
+            return (None,) * 7
+        pose, betas = ctx.saved_tensors
+        right, left = ctx.hands
+        P, dev, nj = pose.shape[0], right.device, right.nj
+        nvr, nvl = right.nv + (1 if ctx.seal else 0), left.nv + (1 if ctx.seal else 0)
+        with torch.cuda.device(dev):
+            gv = None if grad_verts is None else _grad_rows(grad_verts, nvr + nvl, P, dev, "grad_verts")[0]
+            gj = None if grad_joints is None else _grad_rows(grad_joints, 2 * nj, P, dev, "grad_joints")[0]
+            grads = [torch.empty(P, 2, c, dtype=torch.float32, device=dev) if w else None for c, w in zip((nj * 3, right.nb, 3), want)]
+        for h, (mm, v0, v1) in enumerate(((right, 0, nvr), (left, nvr, nvr + nvl))):
+            _skin_backward(mm, pose[:, h], betas[:, h], ctx.flat, ctx.seal, None if gv is None else gv[:, v0:v1],
+                           None if gj is None else gj[:, nj * h:nj * (h + 1)], want, out=[None if g is None else g[:, h] for g in grads])
+        return (None, None, None, None) + tuple(grads)
+
+
+def skin_hand(model, pose, betas, trans, flat_hand_mean=False, seal=True, out=None):
+    """vanerf_mano_skin: pose (P, nj*3) axis-angle per joint with the root first, betas (P, nb), trans (P, 3), fp32 on the model's device (rows
+    contiguous; the row stride is free, so one hand of a (P, 2, .) tensor is passed as a view) -> verts (P, nv + 1, 3) with the wrist sealed by
+    the mean of model.seal_ring as its last vertex (seal=False: (P, nv, 3)) and joints (P, nj, 3).  flat_hand_mean=False adds the model's
+    hands_mean to the finger poses, as the reference's layers do.  out=(verts, joints): written in place (views of a larger tensor are
+    fine); every element is written.  P = 0 is valid.
+    Differentiable: with grad mode on and pose, betas or trans requiring grad, the result carries vanerf_mano_skin_backward as its backward
+    (first order only; inputs that do not require grad are not differentiated); the forward's bits are the same either way.  out= cannot be
+    combined with that and raises."""
+    if _wants_grad(pose, betas, trans):
+        if out is not None:
+            raise ValueError("out=: cannot be combined with an input that requires grad (autograd needs outputs of its own)")
+        return _SkinHand.apply(model, bool(flat_hand_mean), bool(seal), pose, betas, trans)
+    return _skin(model, pose, betas, trans, flat_hand_mean, seal, out)
+
+
+def _skin_two(right, left, pose, betas, trans, flat_hand_mean=False, seal=True, out=None):
+    """skin_two_hands without autograd."""
     for t, what in ((pose, "pose"), (betas, "betas"), (trans, "trans")):
         if not torch.is_tensor(t) or not t.is_cuda:
             raise ValueError(f"{what}: expected a fp32 device tensor (P, 2, .) (no CPU fallback)")
@@ -190,9 +305,209 @@ def skin_two_hands(right, left, pose, betas, trans, flat_hand_mean=False, seal=T
     verts, joints = out
     _out_rows(verts, nvr + nvl, P, dev, "out[0] (verts)")
     _out_rows(joints, 2 * right.nj, P, dev, "out[1] (joints)")
-    skin_hand(right, pose[:, 0], betas[:, 0], trans[:, 0], flat_hand_mean, seal, out=(verts[:, :nvr], joints[:, :right.nj]))
-    skin_hand(left, pose[:, 1], betas[:, 1], trans[:, 1], flat_hand_mean, seal, out=(verts[:, nvr:], joints[:, right.nj:]))
+    _skin(right, pose[:, 0], betas[:, 0], trans[:, 0], flat_hand_mean, seal, out=(verts[:, :nvr], joints[:, :right.nj]))
+    _skin(left, pose[:, 1], betas[:, 1], trans[:, 1], flat_hand_mean, seal, out=(verts[:, nvr:], joints[:, right.nj:]))
     return verts, joints
 
 
-__all__ = ["MANO_PARENTS", "MANO_SEAL_RING", "ManoModel", "skin_hand", "skin_two_hands"]
+def skin_two_hands(right, left, pose, betas, trans, flat_hand_mean=False, seal=True, out=None):
+    """The frame's mesh: pose (P, 2, nj*3), betas (P, 2, nb), trans (P, 2, 3) with the RIGHT hand at index 0 -> verts (P, nvr + nvl, 3), right
+    then left (each nv + 1 vertices when sealed: (P, 1558, 3) for MANO), and joints (P, 2 nj, 3).  Two skin_hand calls that read the halves of
+    the inputs and write the halves of the outputs in place: no copy, and the same bits as those calls.  Differentiable as skin_hand is: two
+    backward calls on the halves of the gradient tensors, no copy; out= with an input that requires grad raises."""
+    if _wants_grad(pose, betas, trans):
+        if out is not None:
+            raise ValueError("out=: cannot be combined with an input that requires grad (autograd needs outputs of its own)")
+        return _SkinTwoHands.apply(right, left, bool(flat_hand_mean), bool(seal), pose, betas, trans)
+    return _skin_two(right, left, pose, betas, trans, flat_hand_mean, seal, out)
+
+
+# ------------------------------------------------------------------------------------------------
+# fitting pose, shape and translation to a mesh in the model's topology (DESIGN.md section 0l)
+# ------------------------------------------------------------------------------------------------
+ADAM_BETAS, ADAM_EPS = (0.9, 0.999), 1e-8
+FIT_LR_RATIOS = (1.0, 2.0, 0.2)  # pose, betas, trans: multiples of lr
+
+
+def _cross_rows(M):
+    """(..., 3, 3) -> the cofactor matrix (rows m1 x m2, m2 x m0, m0 x m1) and the determinant, without a solver library."""
+    m0, m1, m2 = M[..., 0, :], M[..., 1, :], M[..., 2, :]
+    cof = torch.stack([torch.linalg.cross(m1, m2), torch.linalg.cross(m2, m0), torch.linalg.cross(m0, m1)], -2)
+    return cof, (m0 * cof[..., 0, :]).sum(-1)
+
+
+def _polar_rotation(M, iterations=30):
+    """The orthogonal polar factor of M (..., 3, 3) by a fixed count of Newton steps Q <- (Q + Q^-T) / 2 from M scaled to unit size: the
+    rotation nearest to M when det M > 0."""
+    Q = M * (3.0 ** 0.5 / M.flatten(-2).norm(dim=-1).clamp_min(1e-30))[..., None, None]
+    for _ in range(iterations):
+        cof, det = _cross_rows(Q)
+        Q = 0.5 * (Q + cof / det[..., None, None])
+    return Q
+
+
+def _kabsch(src, tgt, use_svd=True):
+    """src (n, 3), tgt (P, n, 3) -> the rotations (P, 3, 3) with R (src - mean) ~ tgt - mean in the least-squares sense.  One batched 3 x 3
+    SVD; where the device has no SVD, the polar iteration."""
+    a, b = src - src.mean(0), tgt - tgt.mean(1, keepdim=True)
+    H = torch.einsum("ni,pnj->pij", a, b)  # sum of a b^T: R = V diag(1, 1, det) U^T of H = U S V^T
+    if use_svd:
+        try:
+            U, _, Vh = torch.linalg.svd(H)
+        except RuntimeError:
+            U = None
+        if U is not None:
+            V = Vh.transpose(-1, -2)
+            d = _cross_rows(V @ U.transpose(-1, -2))[1]
+            flip = torch.ones_like(H[:, 0])
+            flip[:, 2] = torch.where(d < 0, -1.0, 1.0).to(H.dtype)
+            return (V * flip[:, None, :]) @ U.transpose(-1, -2)
+    return _polar_rotation(H.transpose(-1, -2))
+
+
+def _axis_angle(R):
+    """Rotations (P, 3, 3) -> axis-angle (P, 3); the identity gives zeros (a half turn, whose axis this formula cannot see, does too)."""
+    w = torch.stack([R[:, 2, 1] - R[:, 1, 2], R[:, 0, 2] - R[:, 2, 0], R[:, 1, 0] - R[:, 0, 1]], -1)
+    s2 = w.norm(dim=-1, keepdim=True)
+    angle = torch.atan2(s2, (R[:, 0, 0] + R[:, 1, 1] + R[:, 2, 2] - 1.0)[:, None])
+    return w * (angle / s2.clamp_min(1e-20))
+
+
+def _rigid_start(rest, root, target, use_svd=True):
+    """The zero-pose mesh `rest` (n, 3) with its root joint `root` (3) and the targets (P, n, 3) -> the root's axis-angle (P, 3) and the
+    translation (P, 3) that carry the one onto the other rigidly: the root turns the mesh about its own joint."""
+    R = _kabsch(rest, target, use_svd)
+    moved = torch.einsum("pij,j->pi", R, rest.mean(0) - root) + root
+    return _axis_angle(R), target.mean(1) - moved
+
+
+def _fit(forward, backward, params, target_verts, target_joints, vert_weight, full_offset, steps, lr, prior):
+    """Adam (torch.optim.Adam's arithmetic) on pose, betas, trans -- updated in place -- for a fixed count of steps, on whatever device the tensors are
+    on, with nothing read back.  forward(pose, betas, trans) -> verts, joints; backward(pose, betas, grad_verts, grad_joints) -> the three
+    gradients.  The loss, per pose: mean_v w_v |v - v*|^2 + mean_j |j - j*|^2 (either term absent if its target is)
+    + prior[0] |pose[3:] + full_offset|^2 + prior[1] |betas|^2."""
+    pose, betas, trans = params
+    moments = [(torch.zeros_like(p), torch.zeros_like(p)) for p in params]
+    b1, b2 = ADAM_BETAS
+    for step in range(1, int(steps) + 1):
+        verts, joints = forward(pose, betas, trans)
+        gv = gj = None
+        if target_verts is not None:
+            gv = (verts - target_verts) * (2.0 / verts.shape[1])
+            if vert_weight is not None:
+                gv = gv * vert_weight
+        if target_joints is not None:
+            gj = (joints - target_joints) * (2.0 / joints.shape[1])
+        grads = backward(pose, betas, gv, gj)
+        if prior[0]:
+            grads[0][:, 3:] += (2.0 * prior[0]) * (pose[:, 3:] + full_offset)
+        if prior[1]:
+            grads[1].add_(betas, alpha=2.0 * prior[1])
+        c1, c2 = 1.0 - b1 ** step, 1.0 - b2 ** step
+        for p, g, (m, v), ratio in zip(params, grads, moments, FIT_LR_RATIOS):
+            m.mul_(b1).add_(g, alpha=1.0 - b1)
+            v.mul_(b2).addcmul_(g, g, value=1.0 - b2)
+            p.addcdiv_(m, (v.sqrt() / c2 ** 0.5).add_(ADAM_EPS), value=-(lr * ratio) / c1)
+
+
+def fit_hand(model, target_verts=None, target_joints=None, init=None, steps=300, lr=0.03, vert_weight=None, prior=(0.0, 0.0), flat_hand_mean=False,
+             seal=True):
+    """Pose, shape and translation of `model` for a batch of meshes in its topology: target_verts (P, nv + 1, 3) (seal=False: (P, nv, 3))
+    and / or target_joints (P, nj, 3), fp32 on the model's device.  Minimises, per pose, mean_v w_v |v - v*|^2 + mean_j |j - j*|^2
+    + prior[0] |full[3:]|^2 + prior[1] |betas|^2 (full = pose with hands_mean added unless flat_hand_mean; vert_weight (nv + seal) or
+    (P, nv + seal), default ones) by `steps` steps of Adam on the device -- skin_hand's forward and vanerf_mano_skin_backward per step, learning
+    rates lr for pose, 2 lr for betas and 0.2 lr for trans -- with nothing read back to the host.  init=(pose, betas, trans) starts from those
+    values (tracking); init=None starts from the rigid alignment of the zero-pose mesh onto the target (Kabsch by one batched 3 x 3 SVD; the
+    rotation becomes the root's axis-angle, the translation follows from the centroids) and zeros elsewhere.
+    -> dict: pose (P, nj*3), betas (P, nb), trans (P, 3), verts, joints (of those parameters) and rms (P), the root mean square distance
+    of the vertices (of the joints when there is no vertex target) to the target in the target's unit, a device tensor."""
+    if not isinstance(model, ManoModel):
+        raise ValueError("model: expected a ManoModel")
+    if target_verts is None and target_joints is None:
+        raise ValueError("target_verts, target_joints: expected at least one target")
+    dev = model.device
+    if seal and model.seal_ring is None:
+        raise ValueError("seal=True: the model carries no seal_ring")
+    nvo = model.nv + (1 if seal else 0)
+    first = target_verts if target_verts is not None else target_joints
+    P = first.shape[0] if torch.is_tensor(first) and first.dim() == 3 else None
+    for t, n, what in ((target_verts, nvo, "target_verts"), (target_joints, model.nj, "target_joints")):
+        if t is None:
+            continue
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise ValueError(f"{what}: expected a fp32 device tensor (P, {n}, 3) (no CPU fallback)")
+        if t.dtype != torch.float32 or t.dim() != 3 or tuple(t.shape[1:]) != (n, 3) or t.shape[0] != P or t.device != dev:
+            raise ValueError(f"{what}: expected a fp32 tensor ({P}, {n}, 3) on {dev}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+    if len(prior) != 2 or steps < 0:
+        raise ValueError("prior: expected (pose weight, betas weight); steps: at least 0")
+    with torch.cuda.device(dev), torch.no_grad():
+        tv = None if target_verts is None else target_verts.detach().contiguous()
+        tj = None if target_joints is None else target_joints.detach().contiguous()
+        w = None
+        if vert_weight is not None:
+            if not torch.is_tensor(vert_weight) or not vert_weight.is_cuda:
+                raise ValueError(f"vert_weight: expected a device tensor ({nvo},) or ({P}, {nvo}) (no CPU fallback)")
+            if tuple(vert_weight.shape) not in ((nvo,), (P, nvo)):
+                raise ValueError(f"vert_weight: expected ({nvo},) or ({P}, {nvo}), got {tuple(vert_weight.shape)}")
+            w = vert_weight.detach().to(dev, torch.float32)[..., None]
+        shapes = ((P, model.nj * 3), (P, model.nb), (P, 3))
+        if init is not None:
+            params = []
+            for t, shape, what in zip(init, shapes, ("init[0] (pose)", "init[1] (betas)", "init[2] (trans)")):
+                if not torch.is_tensor(t) or not t.is_cuda:
+                    raise ValueError(f"{what}: expected a fp32 device tensor {shape} (no CPU fallback)")
+                if t.dtype != torch.float32 or tuple(t.shape) != shape or t.device != dev:
+                    raise ValueError(f"{what}: expected a fp32 tensor {shape} on {dev}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+                params.append(t.detach().clone().contiguous())
+        else:
+            params = [torch.zeros(shape, dtype=torch.float32, device=dev) for shape in shapes]
+            if P > 0:
+                rest_v, rest_j = _skin(model, params[0][:1], params[1][:1], params[2][:1], flat_hand_mean, seal)
+                rest, target = (rest_v[0], tv) if tv is not None else (rest_j[0], tj)
+                params[0][:, :3], params[2][:] = _rigid_start(rest, rest_j[0, 0], target)
+        offset = 0.0
+        if not flat_hand_mean and model.nj > 1:
+            offset = torch.from_numpy(model.arrays["hands_mean"]).to(dev)
+        verts = torch.empty(P, nvo, 3, dtype=torch.float32, device=dev)
+        joints = torch.empty(P, model.nj, 3, dtype=torch.float32, device=dev)
+        grads = tuple(torch.empty(shape, dtype=torch.float32, device=dev) for shape in shapes)
+        forward = lambda p, b, t: _skin(model, p, b, t, flat_hand_mean, seal, out=(verts, joints))  # noqa: E731
+        backward = lambda p, b, gv, gj: _skin_backward(model, p, b, flat_hand_mean, seal, gv, gj, out=grads)  # noqa: E731
+        if P > 0:
+            _fit(forward, backward, params, tv, tj, w, offset, steps, lr, prior)
+        forward(*params)
+        d = (verts - tv) if tv is not None else (joints - tj)
+        rms = (d * d).sum(-1).mean(-1).sqrt()
+    return {"pose": params[0], "betas": params[1], "trans": params[2], "verts": verts, "joints": joints, "rms": rms}
+
+
+def fit_two_hands(right, left, target_verts, target_joints=None, init=None, steps=300, lr=0.03, vert_weight=None, prior=(0.0, 0.0),
+                  flat_hand_mean=False, seal=True):
+    """fit_hand for the frame's mesh: target_verts (P, nvr + nvl, 3), right then left, as skin_two_hands and surface.register_surface produce
+    it ((P, 1558, 3) for MANO, sealed), optionally target_joints (P, 2 nj, 3); init=(pose (P, 2, nj*3), betas (P, 2, nb), trans (P, 2, 3));
+    vert_weight (nvr + nvl) or (P, nvr + nvl).  -> dict: pose (P, 2, nj*3), betas (P, 2, nb), trans (P, 2, 3) -- what skin_two_hands and
+    posed.mano_sequence take --, verts (P, nvr + nvl, 3), joints (P, 2 nj, 3) and rms (P, 2), the right hand at index 0."""
+    if not (isinstance(right, ManoModel) and isinstance(left, ManoModel)):
+        raise ValueError("right, left: expected two ManoModels")
+    if right.device != left.device or right.nj != left.nj or right.nb != left.nb:
+        raise ValueError("right, left: expected models of the same nj and nb on one device")
+    nvr, nvl, nj = right.nv + (1 if seal else 0), left.nv + (1 if seal else 0), right.nj
+    if not torch.is_tensor(target_verts) or not target_verts.is_cuda:
+        raise ValueError(f"target_verts: expected a fp32 device tensor (P, {nvr + nvl}, 3) (no CPU fallback)")
+    if target_verts.dim() != 3 or tuple(target_verts.shape[1:]) != (nvr + nvl, 3):
+        raise ValueError(f"target_verts: expected (P, {nvr + nvl}, 3), got {tuple(target_verts.shape)}")
+    if target_joints is not None and (not torch.is_tensor(target_joints) or target_joints.dim() != 3 or tuple(target_joints.shape[1:]) != (2 * nj, 3)):
+        raise ValueError(f"target_joints: expected a fp32 device tensor (P, {2 * nj}, 3) (no CPU fallback)")
+    if vert_weight is not None and (not torch.is_tensor(vert_weight) or vert_weight.shape[-1] != nvr + nvl):
+        raise ValueError(f"vert_weight: expected a device tensor ({nvr + nvl},) or (P, {nvr + nvl}) (no CPU fallback)")
+    fits = []
+    for h, (mm, v0, v1) in enumerate(((right, 0, nvr), (left, nvr, nvr + nvl))):
+        fits.append(fit_hand(mm, target_verts[:, v0:v1], None if target_joints is None else target_joints[:, nj * h:nj * (h + 1)],
+                             None if init is None else tuple(t[:, h] for t in init), steps, lr,
+                             None if vert_weight is None else vert_weight[..., v0:v1], prior, flat_hand_mean, seal))
+    out = {k: torch.stack([fits[0][k], fits[1][k]], 1) for k in ("pose", "betas", "trans", "rms")}
+    out.update({k: torch.cat([fits[0][k], fits[1][k]], 1) for k in ("verts", "joints")})
+    return out
+
+
+__all__ = ["MANO_PARENTS", "MANO_SEAL_RING", "ManoModel", "skin_hand", "skin_two_hands", "fit_hand", "fit_two_hands"]
