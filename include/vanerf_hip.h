@@ -798,6 +798,63 @@ int vanerf_mano_skin_backward(const void* packed, int nv, int nj, int nb, const 
                               int64_t workspace_bytes, float* grad_pose, int64_t grad_pose_stride, float* grad_betas, int64_t grad_betas_stride,
                               float* grad_trans, int64_t grad_trans_stride, void* stream);
 
+/* The normal equations of fitting vanerf_mano_skin to a mesh: what one Gauss-Newton / Levenberg-Marquardt iteration
+ * needs, on the device, with no host read.  The unknowns of a pose are ordered x = (pose[3 nj], betas[nb], trans[3]), n = 3 nj + nb + 3 (at most
+ * 115).  The residuals are r = (v - v*, j - j*): the (nv + (n_ring > 0)) vertices of the definition above, steps 1-7, against target_verts, then
+ * the nj joints against target_joints; the sealed vertex is a residual like any other.  The weights are W = (w_v / nv_out, 1 / nj) with
+ * nv_out = nv + (n_ring > 0) and w_v = vert_weight[v] (null: ones), each repeated for its three coordinates.  With J = dr/dx, per pose:
+ *     H = J^T W J   (n x n, fp32, the full symmetric matrix: both triangles are written and equal bit for bit),
+ *     g = J^T W r   (n),        loss = r^T W r   (a scalar).
+ * So mean_v w_v |v - v*|^2 + mean_j |j - j*|^2 = loss, and its gradient is 2 g.  J is the derivative of the definition exactly as
+ * vanerf_mano_skin_backward differentiates it: the 1e-8 sits in the angle, hands_mean is additive, the seal's rows are (1.0f / (float)n_ring)
+ * times the sum of its ring's rows, once per occurrence, and the forward's roundings are not differentiated.
+ *
+ * packed, nv, nj, nb, pose, betas, trans, P, flat_hand_mean, ring and n_ring are the forward's.  target_verts: P rows target_verts_stride
+ * floats apart, each nv_out x 3; target_joints: P rows of nj x 3.  Either may be null, which takes its residuals out; both null is an error.
+ * vert_weight: P rows of nv_out floats, vert_weight_stride apart; a stride of 0 means one row shared by all poses; null means ones (and it
+ * must be null when target_verts is).  Weights are expected to be >= 0.  H: P matrices H_stride floats apart (at least n * n), row-major;
+ * g: P rows g_stride apart; loss: P scalars loss_stride apart.  Any of H, g, loss may be null, which means not written; every element of the
+ * others is written.  workspace: DEVICE, 16-byte aligned, at least vanerf_mano_skin_normal_workspace_bytes (nv, nj, nb, P), contents
+ * undefined before and after.  P = 0 is valid and a no-op.  Stateless: nothing is taken from a forward call.
+ *
+ * Where the arithmetic happens.  Joint side, fp64, one wave per pose: steps 1, 3, 5 and J of step 2 as the forward computes them (A and the
+ * pose feature have the forward's bits), the derivative dR_a/dr_x of step 3, D_ax = G_parents[a]^R dR_a/dr_x G_a^R^-1 (the inverse by
+ * cofactors: with the 1e-8 in the angle R is orthogonal only to 1e-8 |r|; the root: dR_0/dr_x G_0^R^-1), G_a^t, and down the chain
+ * dG_j^t/dbeta_b = G_p^R ((JS)_j - (JS)_p)_b + dG_p^t/dbeta_b with JS = J_regressor . shapedirs, dA_j^t/dbeta_b
+ * = dG_j^t/dbeta_b - G_j^R (JS)_jb; each rounded ONCE to fp32.  A pose parameter (a, x) moves A_j for j = a and every joint below a, by
+ * dA_j = D_ax [A_j^R | A_j^t - G_a^t], and no other; so the tables do not grow with the depth of the tree.
+ * Vertex side, fp32, every product and sum its own IEEE operation unless said otherwise: x = v_posed, T and the vertex as the forward computes
+ * them (the residual is the forward's vertex minus its target).  Column (a, x) of a vertex's 3 x n block of J: S = sum over j = a .. nj-1
+ * that are a or below it, in that order, of w_vj (A_j (x, 1)), Ws = the sum of those w_vj, u = S - Ws G_a^t, column = D_ax u + T^R (sum over
+ * e = 0 .. 8 of posedirs[(a-1)*9 + e][3v + .] dR_a/dr_x[e]) (the second term for a >= 1).  Column of beta_b: T^R shapedirs[v][.][b] + sum over
+ * j from 0 of w_vj dA_j^t/dbeta_b.  The columns of trans: the identity.  The sealed vertex: the rows of ring[0 .. n_ring-1] recomputed, added
+ * in the ring's order from the left and multiplied by (1.0f / (float)n_ring), on every column and on the position (the forward's sum).
+ * The sums over the residual rows: per chunk of 64 vertices (the sealed vertex is a chunk of its own, the last), over the chunk's 192 rows in
+ * the order coordinate-major, vertex-minor, acc = fmaf(a, w * b, acc) in fp32 -- an fp32 product w * b, then a FUSED multiply-add: the chain
+ * the exact-fp32 matrix instruction v_mfma_f32_32x32x2_f32 computes per element, two rows per instruction -- for the lower triangle of
+ * (J | r)^T W (J | r) -- but r^T W r itself, one entry, as (double)(w * r) * (double)r added in fp64, a lane's three rows from coordinate 0,
+ * then a butterfly over the 64 lanes, rounded to fp32 per chunk --; the chunks' sums are added in chunk order in fp64; the joints' rows
+ * (dG_j^t/dx = D_ax (G_j^t - G_a^t)
+ * for a above j, dG_j^t/dbeta_b, the identity; r_j = the forward's fp32 joint minus its target) are multiplied and added in fp64, row by row,
+ * and divided by nj; one rounding to fp32.  The upper triangle of H is a copy of the lower.  A pose's bits depend neither on P nor on its
+ * row in the batch; a NaN in one pose's inputs stays in that pose.
+ * Three launches (two when target_verts is null).  All work goes to `stream`; no allocation, no host synchronisation, no atomics, no
+ * device-side state: the same bits every call.  Arguments are checked before any launch.
+ *
+ * vanerf_mano_lm_solve: delta = -M^-1 g for P symmetric positive definite systems of 1 <= n <= 128 unknowns.  M: P matrices M_stride floats
+ * apart (at least n * n), row-major, of which the LOWER triangle is read; g, delta: P rows with their strides (at least n); ok: P int32.  One
+ * wave per system, the matrix in LDS in fp64: Cholesky column by column (s = M_ij, s = s - L_ik L_jk for k = 0 .. j-1), the two triangular
+ * solves, one rounding to fp32.  A pivot that is not positive or not finite, or a result that is not finite, gives that system ok = 0 and
+ * delta = 0; the others are untouched; otherwise ok = 1.  No host read; P = 0 is a no-op; one launch on `stream`.                          */
+int64_t vanerf_mano_skin_normal_workspace_bytes(int nv, int nj, int nb, int P);
+int vanerf_mano_skin_normal(const void* packed, int nv, int nj, int nb, const float* pose, int64_t pose_stride, const float* betas,
+                            int64_t betas_stride, const float* trans, int64_t trans_stride, int P, int flat_hand_mean, const int32_t* ring, int n_ring,
+                            const float* target_verts, int64_t target_verts_stride, const float* vert_weight, int64_t vert_weight_stride,
+                            const float* target_joints, int64_t target_joints_stride, void* workspace, int64_t workspace_bytes, float* H,
+                            int64_t H_stride, float* g, int64_t g_stride, float* loss, int64_t loss_stride, void* stream);
+int vanerf_mano_lm_solve(const float* M, int64_t M_stride, const float* g, int64_t g_stride, int n, int P, float* delta, int64_t delta_stride,
+                         int32_t* ok, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

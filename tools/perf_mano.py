@@ -12,7 +12,9 @@ out=) by naming it in VANERF_HIP_LIB.  Kernel times: rocprofv3 --kernel-trace --
 skin_two_hands under autograd with torch.autograd.grad for given upstream gradients of the vertices and joints -- forward + backward -- against
 the same of the PyTorch fp32 restatement, with the largest difference between the two sets of gradients relative to each gradient's largest
 value.  `--fit` adds mano.fit_two_hands at `--fit-steps` steps from a tracking start against the same count of steps of torch.optim.Adam on
-the restatement (one loss for both hands), per call and per step."""
+the restatement (one loss for both hands), per call and per step.  `--lm` adds, per P: one vanerf_mano_skin_normal call
+per hand (two calls) and one vanerf_mano_lm_solve call per hand, and mano.fit_two_hands_lm at its default iterations next to mano.fit_two_hands at
+300 steps from the same tracking start, each with the worst rms over poses and hands."""
 import argparse
 import os
 import statistics
@@ -134,6 +136,33 @@ def fit_rows(a, P, hands, tens, ring_t, pose, betas, trans, fmt):
           f"{tt[0] / tf[0]:6.1f} x the HIP path", flush=True)
 
 
+def lm_rows(a, P, hands, pose, betas, trans, fmt):
+    with torch.no_grad():
+        target = mano.skin_two_hands(*hands, pose, betas, trans)[0]
+    nvo, n = hands[0].nv + 1, hands[0].nj * 3 + hands[0].nb + 3
+    gen = torch.Generator(device="cuda").manual_seed(9)
+    init = (pose + 0.2 * torch.randn(pose.shape, device="cuda", generator=gen), torch.zeros_like(betas),
+            trans + 0.02 * torch.randn(trans.shape, device="cuda", generator=gen))
+    tv = [target[:, nvo * h:nvo * (h + 1)].contiguous() for h in range(2)]
+    outs = [(torch.empty(P, n, n, device="cuda"), torch.empty(P, n, device="cuda"), torch.empty(P, device="cuda")) for _ in range(2)]
+
+    def normal():
+        for h in range(2):
+            mano._skin_normal(hands[h], init[0][:, h], init[1][:, h], init[2][:, h], tv[h], None, None, False, True, out=outs[h])
+
+    tn = median_ms(normal, a.calls, a.reps)
+    M = [o[0] + 1e-3 * torch.diag_embed(torch.diagonal(o[0], dim1=1, dim2=2) + 1e-9) for o in outs]
+    ts = median_ms(lambda: [mano.lm_solve(M[h], outs[h][1]) for h in range(2)], a.calls, a.reps)
+    print(f"P={P:5d}: skin_normal, two hands {fmt(tn)} per call pair, {1e3 * tn[0] / P:9.3f} us per pose; lm_solve (n = {n}), two hands {fmt(ts)}, "
+          f"{1e3 * ts[0] / P:9.3f} us per pose", flush=True)
+    tl = median_ms(lambda: mano.fit_two_hands_lm(*hands, target, init=init), max(1, a.calls // 10), a.reps)
+    ta = median_ms(lambda: mano.fit_two_hands(*hands, target, init=init, steps=300), 1, max(1, a.reps // 2))
+    lm, adam = mano.fit_two_hands_lm(*hands, target, init=init), mano.fit_two_hands(*hands, target, init=init, steps=300)
+    print(f"P={P:5d}: fit_two_hands_lm, default iterations {fmt(tl)} per call, worst rms {1e3 * float(lm['rms'].max()):.5f} mm, fewest accepted steps "
+          f"{int(lm['accepted'].min())}; fit_two_hands, 300 steps {fmt(ta)} per call, worst rms {1e3 * float(adam['rms'].max()):.5f} mm: {ta[0] / tl[0]:6.1f} x the time",
+          flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--poses", type=int, nargs="+", default=[1, 64, 1024])
@@ -143,6 +172,7 @@ def main():
     ap.add_argument("--backward", action="store_true", help="also time the backward and forward + backward against PyTorch autograd")
     ap.add_argument("--fit", action="store_true", help="also time mano.fit_two_hands against torch.optim.Adam on the restatement")
     ap.add_argument("--fit-steps", type=int, default=50)
+    ap.add_argument("--lm", action="store_true", help="also time skin_normal, lm_solve and mano.fit_two_hands_lm against mano.fit_two_hands at 300 steps")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("perf_mano.py measures on the GPU: no device found")
@@ -182,6 +212,8 @@ def main():
             backward_rows(a, P, hands, tens, ring_t, pose, betas, trans, fmt)
         if a.fit:
             fit_rows(a, P, hands, tens, ring_t, pose, betas, trans, fmt)
+        if a.lm:
+            lm_rows(a, P, hands, pose, betas, trans, fmt)
 
 if __name__ == "__main__":
     main()

@@ -151,6 +151,10 @@ _SIGS = {
     "vanerf_mano_skin_backward_workspace_bytes": (c_int64, [c_int, c_int, c_int, c_int]),
     "vanerf_mano_skin_backward": (c_int, [c_void_p, c_int, c_int, c_int, _FP, c_int64, _FP, c_int64, c_int, c_int, POINTER(c_int), c_int, _FP, c_int64, _FP,
                                           c_int64, c_void_p, c_int64, _FP, c_int64, _FP, c_int64, _FP, c_int64, c_void_p]),
+    "vanerf_mano_skin_normal_workspace_bytes": (c_int64, [c_int, c_int, c_int, c_int]),
+    "vanerf_mano_skin_normal": (c_int, [c_void_p, c_int, c_int, c_int, _FP, c_int64, _FP, c_int64, _FP, c_int64, c_int, c_int, POINTER(c_int), c_int, _FP, c_int64,
+                                        _FP, c_int64, _FP, c_int64, c_void_p, c_int64, _FP, c_int64, _FP, c_int64, _FP, c_int64, c_void_p]),
+    "vanerf_mano_lm_solve": (c_int, [_FP, c_int64, _FP, c_int64, c_int, c_int, _FP, c_int64, c_void_p, c_void_p]),
 }
 EXPORTS = tuple(_SIGS)
 

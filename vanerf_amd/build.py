@@ -7,7 +7,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "lib", "libvanerf_hip.so")
-SOURCES = ["api.cpp", "weights_pack.cpp", "pass.cpp", "query_kernel.hip", "query_order.hip", "render_kernels.hip", "mesh_kernels.hip", "mesh_accel_query.hip", "mesh_accel_build.hip", "train_kernels.hip", "query_backward.hip", "weights_update.hip", "weight_products.hip", "vis_render.hip", "image_metrics.hip", "mask_at_box.hip", "vertex_products.hip", "surface.hip", "surface_lines.hip", "volume_render.hip", "volume_surface.hip", "pose_warp.hip", "mano_skin.hip", "mano_skin_backward.hip"]
+SOURCES = ["api.cpp", "weights_pack.cpp", "pass.cpp", "query_kernel.hip", "query_order.hip", "render_kernels.hip", "mesh_kernels.hip", "mesh_accel_query.hip", "mesh_accel_build.hip", "train_kernels.hip", "query_backward.hip", "weights_update.hip", "weight_products.hip", "vis_render.hip", "image_metrics.hip", "mask_at_box.hip", "vertex_products.hip", "surface.hip", "surface_lines.hip", "volume_render.hip", "volume_surface.hip", "pose_warp.hip", "mano_skin.hip", "mano_skin_backward.hip", "mano_skin_normal.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
          "-Wall", "-Wextra", "-Wno-unused-parameter"]
 # per-file flags.  query_kernel.hip: MFMA results are allocated in VGPRs (the chained layers read every accumulator element once with VALU

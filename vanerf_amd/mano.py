@@ -7,6 +7,10 @@ The opposite direction (vanerf_amd/csrc/mano_skin_backward.hip, DESIGN.md sectio
 respect to pose, betas and trans (vanerf_mano_skin_backward, first order), and fit_hand / fit_two_hands recover the parameters of a mesh in the
 model's topology by Adam on the device.
 
+The same fit by Levenberg-Marquardt (vanerf_amd/csrc/mano_skin_normal.hip): skin_normal_equations returns J^T W J, J^T W r
+and the loss of the fit's data term (vanerf_mano_skin_normal), lm_solve is a Cholesky solve with one wave per pose (vanerf_mano_lm_solve), and
+fit_hand_lm / fit_two_hands_lm take fit_hand's arguments and need some ten iterations.
+
 The licensed MANO file is not part of this project: a model comes in as arrays (ManoModel.from_arrays, or from_npz for arrays saved under
 smplx's attribute names).  The known sign error of the LEFT hand's shapedirs in the files smplx reads (shapedirs[:, 0, :] has the right hand's
 sign) is the caller's data preparation; nothing is flipped here.  synth.mano_like_model draws a seeded model of MANO's shapes.
@@ -410,17 +414,10 @@ def _fit(forward, backward, params, target_verts, target_joints, vert_weight, fu
             p.addcdiv_(m, (v.sqrt() / c2 ** 0.5).add_(ADAM_EPS), value=-(lr * ratio) / c1)
 
 
-def fit_hand(model, target_verts=None, target_joints=None, init=None, steps=300, lr=0.03, vert_weight=None, prior=(0.0, 0.0), flat_hand_mean=False,
-             seal=True):
-    """Pose, shape and translation of `model` for a batch of meshes in its topology: target_verts (P, nv + 1, 3) (seal=False: (P, nv, 3))
-    and / or target_joints (P, nj, 3), fp32 on the model's device.  Minimises, per pose, mean_v w_v |v - v*|^2 + mean_j |j - j*|^2
-    + prior[0] |full[3:]|^2 + prior[1] |betas|^2 (full = pose with hands_mean added unless flat_hand_mean; vert_weight (nv + seal) or
-    (P, nv + seal), default ones) by `steps` steps of Adam on the device -- skin_hand's forward and vanerf_mano_skin_backward per step, learning
-    rates lr for pose, 2 lr for betas and 0.2 lr for trans -- with nothing read back to the host.  init=(pose, betas, trans) starts from those
-    values (tracking); init=None starts from the rigid alignment of the zero-pose mesh onto the target (Kabsch by one batched 3 x 3 SVD; the
-    rotation becomes the root's axis-angle, the translation follows from the centroids) and zeros elsewhere.
-    -> dict: pose (P, nj*3), betas (P, nb), trans (P, 3), verts, joints (of those parameters) and rms (P), the root mean square distance
-    of the vertices (of the joints when there is no vertex target) to the target in the target's unit, a device tensor."""
+def _fit_setup(model, target_verts, target_joints, init, steps, vert_weight, prior, flat_hand_mean, seal, count="steps"):
+    """The checks and the start that fit_hand and fit_hand_lm share -> (P, nvo, tv, tj, w, params, offset): the targets detached and contiguous,
+    the weights as (nvo, 1) or (P, nvo, 1) or None, the three parameter tensors (clones of init, or the rigid start) and what flat_hand_mean=False
+    adds to pose[3:] (0.0 or hands_mean on the device).  `count` is what the caller calls `steps` in its refusal."""
     if not isinstance(model, ManoModel):
         raise ValueError("model: expected a ManoModel")
     if target_verts is None and target_joints is None:
@@ -439,7 +436,7 @@ def fit_hand(model, target_verts=None, target_joints=None, init=None, steps=300,
         if t.dtype != torch.float32 or t.dim() != 3 or tuple(t.shape[1:]) != (n, 3) or t.shape[0] != P or t.device != dev:
             raise ValueError(f"{what}: expected a fp32 tensor ({P}, {n}, 3) on {dev}, got {t.dtype} {tuple(t.shape)} on {t.device}")
     if len(prior) != 2 or steps < 0:
-        raise ValueError("prior: expected (pose weight, betas weight); steps: at least 0")
+        raise ValueError(f"prior: expected (pose weight, betas weight); {count}: at least 0")
     with torch.cuda.device(dev), torch.no_grad():
         tv = None if target_verts is None else target_verts.detach().contiguous()
         tj = None if target_joints is None else target_joints.detach().contiguous()
@@ -468,6 +465,24 @@ def fit_hand(model, target_verts=None, target_joints=None, init=None, steps=300,
         offset = 0.0
         if not flat_hand_mean and model.nj > 1:
             offset = torch.from_numpy(model.arrays["hands_mean"]).to(dev)
+    return P, nvo, tv, tj, w, params, offset
+
+
+def fit_hand(model, target_verts=None, target_joints=None, init=None, steps=300, lr=0.03, vert_weight=None, prior=(0.0, 0.0), flat_hand_mean=False,
+             seal=True):
+    """Pose, shape and translation of `model` for a batch of meshes in its topology: target_verts (P, nv + 1, 3) (seal=False: (P, nv, 3))
+    and / or target_joints (P, nj, 3), fp32 on the model's device.  Minimises, per pose, mean_v w_v |v - v*|^2 + mean_j |j - j*|^2
+    + prior[0] |full[3:]|^2 + prior[1] |betas|^2 (full = pose with hands_mean added unless flat_hand_mean; vert_weight (nv + seal) or
+    (P, nv + seal), default ones) by `steps` steps of Adam on the device -- skin_hand's forward and vanerf_mano_skin_backward per step, learning
+    rates lr for pose, 2 lr for betas and 0.2 lr for trans -- with nothing read back to the host.  init=(pose, betas, trans) starts from those
+    values (tracking); init=None starts from the rigid alignment of the zero-pose mesh onto the target (Kabsch by one batched 3 x 3 SVD; the
+    rotation becomes the root's axis-angle, the translation follows from the centroids) and zeros elsewhere.
+    -> dict: pose (P, nj*3), betas (P, nb), trans (P, 3), verts, joints (of those parameters) and rms (P), the root mean square distance
+    of the vertices (of the joints when there is no vertex target) to the target in the target's unit, a device tensor."""
+    P, nvo, tv, tj, w, params, offset = _fit_setup(model, target_verts, target_joints, init, steps, vert_weight, prior, flat_hand_mean, seal)
+    dev = model.device
+    shapes = ((P, model.nj * 3), (P, model.nb), (P, 3))
+    with torch.cuda.device(dev), torch.no_grad():
         verts = torch.empty(P, nvo, 3, dtype=torch.float32, device=dev)
         joints = torch.empty(P, model.nj, 3, dtype=torch.float32, device=dev)
         grads = tuple(torch.empty(shape, dtype=torch.float32, device=dev) for shape in shapes)
@@ -481,12 +496,9 @@ def fit_hand(model, target_verts=None, target_joints=None, init=None, steps=300,
     return {"pose": params[0], "betas": params[1], "trans": params[2], "verts": verts, "joints": joints, "rms": rms}
 
 
-def fit_two_hands(right, left, target_verts, target_joints=None, init=None, steps=300, lr=0.03, vert_weight=None, prior=(0.0, 0.0),
-                  flat_hand_mean=False, seal=True):
-    """fit_hand for the frame's mesh: target_verts (P, nvr + nvl, 3), right then left, as skin_two_hands and surface.register_surface produce
-    it ((P, 1558, 3) for MANO, sealed), optionally target_joints (P, 2 nj, 3); init=(pose (P, 2, nj*3), betas (P, 2, nb), trans (P, 2, 3));
-    vert_weight (nvr + nvl) or (P, nvr + nvl).  -> dict: pose (P, 2, nj*3), betas (P, 2, nb), trans (P, 2, 3) -- what skin_two_hands and
-    posed.mano_sequence take --, verts (P, nvr + nvl, 3), joints (P, 2 nj, 3) and rms (P, 2), the right hand at index 0."""
+def _fit_two(fit_one, stacked, right, left, target_verts, target_joints, init, vert_weight, seal):
+    """What fit_two_hands and fit_two_hands_lm share: the checks, the two fits one after the other -- fit_one(model, target_verts, target_joints,
+    init, vert_weight) on the halves -- and the stacking; `stacked` names the per-hand results that become (P, 2, ...)."""
     if not (isinstance(right, ManoModel) and isinstance(left, ManoModel)):
         raise ValueError("right, left: expected two ManoModels")
     if right.device != left.device or right.nj != left.nj or right.nb != left.nb:
@@ -502,12 +514,165 @@ def fit_two_hands(right, left, target_verts, target_joints=None, init=None, step
         raise ValueError(f"vert_weight: expected a device tensor ({nvr + nvl},) or (P, {nvr + nvl}) (no CPU fallback)")
     fits = []
     for h, (mm, v0, v1) in enumerate(((right, 0, nvr), (left, nvr, nvr + nvl))):
-        fits.append(fit_hand(mm, target_verts[:, v0:v1], None if target_joints is None else target_joints[:, nj * h:nj * (h + 1)],
-                             None if init is None else tuple(t[:, h] for t in init), steps, lr,
-                             None if vert_weight is None else vert_weight[..., v0:v1], prior, flat_hand_mean, seal))
-    out = {k: torch.stack([fits[0][k], fits[1][k]], 1) for k in ("pose", "betas", "trans", "rms")}
+        fits.append(fit_one(mm, target_verts[:, v0:v1], None if target_joints is None else target_joints[:, nj * h:nj * (h + 1)],
+                            None if init is None else tuple(t[:, h] for t in init), None if vert_weight is None else vert_weight[..., v0:v1]))
+    out = {k: torch.stack([fits[0][k], fits[1][k]], 1) for k in stacked}
     out.update({k: torch.cat([fits[0][k], fits[1][k]], 1) for k in ("verts", "joints")})
     return out
 
 
-__all__ = ["MANO_PARENTS", "MANO_SEAL_RING", "ManoModel", "skin_hand", "skin_two_hands", "fit_hand", "fit_two_hands"]
+def fit_two_hands(right, left, target_verts, target_joints=None, init=None, steps=300, lr=0.03, vert_weight=None, prior=(0.0, 0.0),
+                  flat_hand_mean=False, seal=True):
+    """fit_hand for the frame's mesh: target_verts (P, nvr + nvl, 3), right then left, as skin_two_hands and surface.register_surface produce
+    it ((P, 1558, 3) for MANO, sealed), optionally target_joints (P, 2 nj, 3); init=(pose (P, 2, nj*3), betas (P, 2, nb), trans (P, 2, 3));
+    vert_weight (nvr + nvl) or (P, nvr + nvl).  -> dict: pose (P, 2, nj*3), betas (P, 2, nb), trans (P, 2, 3) -- what skin_two_hands and
+    posed.mano_sequence take --, verts (P, nvr + nvl, 3), joints (P, 2 nj, 3) and rms (P, 2), the right hand at index 0."""
+    return _fit_two(lambda mm, tv, tj, start, w: fit_hand(mm, tv, tj, start, steps, lr, w, prior, flat_hand_mean, seal), ("pose", "betas", "trans", "rms"),
+                    right, left, target_verts, target_joints, init, vert_weight, seal)
+
+
+# ------------------------------------------------------------------------------------------------
+# the same fit by Levenberg-Marquardt (DESIGN.md section 0m)
+# ------------------------------------------------------------------------------------------------
+LM_MAX_UNKNOWNS = 128
+LM_DAMPING_FLOOR, LM_TRACE_FLOOR = 1e-12, 1e-9
+
+
+def _skin_normal(model, pose, betas, trans, tv, tj, w, flat_hand_mean, seal, out=None):
+    """vanerf_mano_skin_normal after the checks of its callers: tv (P, nvo, 3) and tj (P, nj, 3) contiguous or None, w (nvo,) or (P, nvo)
+    contiguous fp32 or None -> (H (P, n, n), g (P, n), loss (P)); out=(H, g, loss): written in place, None entries are not written."""
+    dev, P, n = model.device, pose.shape[0], model.nj * 3 + model.nb + 3
+    pp, ps = _rows(pose, model.nj * 3, None, dev, "pose")
+    bp, bs = _rows(betas, model.nb, P, dev, "betas")
+    tp, ts = _rows(trans, 3, P, dev, "trans")
+    ring, n_ring = _ring_arg(model.seal_ring if seal else None, model.nv)
+    nvo = model.nv + (1 if seal else 0)
+    with torch.cuda.device(dev):
+        if out is None:
+            out = (torch.empty(P, n, n, dtype=torch.float32, device=dev), torch.empty(P, n, dtype=torch.float32, device=dev),
+                   torch.empty(P, dtype=torch.float32, device=dev))
+        ptr = lambda t: None if t is None else c_void_p(t.data_ptr())  # noqa: E731
+        nbytes = lib.vanerf_mano_skin_normal_workspace_bytes(model.nv, model.nj, model.nb, P)
+        if nbytes < 0:
+            check(int(nbytes))
+        ws = torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=dev)
+        check(lib.vanerf_mano_skin_normal(c_void_p(model.packed.data_ptr()), model.nv, model.nj, model.nb, pp, ps, bp, bs, tp, ts, P, int(bool(flat_hand_mean)),
+                                          ring, n_ring, ptr(tv), nvo * 3, ptr(w), 0 if w is None or w.dim() == 1 else nvo, ptr(tj), model.nj * 3,
+                                          c_void_p(ws.data_ptr()), nbytes, ptr(out[0]), n * n, ptr(out[1]), n, ptr(out[2]), 1, _stream()))
+    return out
+
+
+def _normal_targets(model, P, target_verts, target_joints, vert_weight, seal):
+    """The targets and weights of skin_normal_equations, checked -> contiguous fp32 tensors or None."""
+    dev, nvo = model.device, model.nv + (1 if seal else 0)
+    if target_verts is None and target_joints is None:
+        raise ValueError("target_verts, target_joints: expected at least one target")
+    got = []
+    for t, n, what in ((target_verts, nvo, "target_verts"), (target_joints, model.nj, "target_joints")):
+        if t is not None:
+            if not torch.is_tensor(t) or not t.is_cuda:
+                raise ValueError(f"{what}: expected a fp32 device tensor ({P}, {n}, 3) (no CPU fallback)")
+            if t.dtype != torch.float32 or tuple(t.shape) != (P, n, 3) or t.device != dev:
+                raise ValueError(f"{what}: expected a fp32 tensor ({P}, {n}, 3) on {dev}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+            t = t.detach().contiguous()
+        got.append(t)
+    w = None
+    if vert_weight is not None:
+        if not torch.is_tensor(vert_weight) or not vert_weight.is_cuda:
+            raise ValueError(f"vert_weight: expected a device tensor ({nvo},) or ({P}, {nvo}) (no CPU fallback)")
+        if target_verts is None or tuple(vert_weight.shape) not in ((nvo,), (P, nvo)) or vert_weight.device != dev:
+            raise ValueError(f"vert_weight: expected ({nvo},) or ({P}, {nvo}) on {dev} beside target_verts, got {tuple(vert_weight.shape)}")
+        w = vert_weight.detach().to(torch.float32).contiguous()
+    return got[0], got[1], w
+
+
+def skin_normal_equations(model, pose, betas, trans, target_verts=None, target_joints=None, vert_weight=None, flat_hand_mean=False, seal=True):
+    """vanerf_mano_skin_normal: the normal equations of fit_hand's data term at pose (P, nj*3), betas (P, nb), trans (P, 3).  With the unknowns
+    ordered x = (pose, betas, trans), n = 3 nj + nb + 3, the residuals r = (verts - target_verts, joints - target_joints) (either target may be
+    None), J = dr/dx and W = (vert_weight / (nv + seal), 1 / nj): -> H = J^T W J (P, n, n), symmetric bit for bit, g = J^T W r (P, n) and
+    loss = r^T W r (P), fp32 device tensors.  fit_hand's loss is loss + its priors and the loss's gradient is 2 g."""
+    for t, what in ((pose, "pose"), (betas, "betas"), (trans, "trans")):
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise ValueError(f"{what}: expected a fp32 device tensor (no CPU fallback)")
+    if not isinstance(model, ManoModel):
+        raise ValueError("model: expected a ManoModel")
+    if seal and model.seal_ring is None:
+        raise ValueError("seal=True: the model carries no seal_ring")
+    _rows(pose, model.nj * 3, None, model.device, "pose")
+    tv, tj, w = _normal_targets(model, pose.shape[0], target_verts, target_joints, vert_weight, seal)
+    return _skin_normal(model, pose.detach(), betas.detach(), trans.detach(), tv, tj, w, flat_hand_mean, seal)
+
+
+def lm_solve(M, g):
+    """vanerf_mano_lm_solve: M (P, n, n) symmetric positive definite (its lower triangle is read) and g (P, n), fp32 device tensors, n <= 128
+    -> delta = -M^-1 g (P, n) by a Cholesky factorisation in fp64, one wave per system, and ok (P) int32: 0 where a pivot was not positive or
+    not finite, and delta = 0 there.  Nothing is read back."""
+    for t, what in ((M, "M"), (g, "g")):
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise ValueError(f"{what}: expected a fp32 device tensor (no CPU fallback)")
+    if M.dtype != torch.float32 or M.dim() != 3 or M.shape[1] != M.shape[2] or not 1 <= M.shape[1] <= LM_MAX_UNKNOWNS:
+        raise ValueError(f"M: expected a fp32 tensor (P, n, n) with 1 <= n <= {LM_MAX_UNKNOWNS}, got {M.dtype} {tuple(M.shape)}")
+    P, n = M.shape[0], M.shape[1]
+    if g.dtype != torch.float32 or tuple(g.shape) != (P, n) or g.device != M.device:
+        raise ValueError(f"g: expected a fp32 tensor ({P}, {n}) on {M.device}, got {g.dtype} {tuple(g.shape)} on {g.device}")
+    M, g = M.contiguous(), g.contiguous()
+    with torch.cuda.device(M.device):
+        delta, ok = torch.empty(P, n, dtype=torch.float32, device=M.device), torch.empty(P, dtype=torch.int32, device=M.device)
+        check(lib.vanerf_mano_lm_solve(c_void_p(M.data_ptr()), n * n, c_void_p(g.data_ptr()), n, n, P, c_void_p(delta.data_ptr()), n,
+                                       c_void_p(ok.data_ptr()), _stream()))
+    return delta, ok
+
+
+def fit_hand_lm(model, target_verts=None, target_joints=None, init=None, iterations=10, damping=1e-3, vert_weight=None, prior=(0.0, 0.0),
+                flat_hand_mean=False, seal=True):
+    """fit_hand by Levenberg-Marquardt: the same arguments, checks, loss, rigid start and results, with `iterations` Gauss-Newton steps in place
+    of Adam's.  Per iteration and pose: M = H + the priors' diagonal + lambda (diag H + 1e-9 trace H / n), delta = -M^-1 (g + the priors' share)
+    (lm_solve), and one skin_normal_equations call at x + delta; where the loss with its priors went down (and the solve succeeded) the step is
+    taken and lambda = max(lambda / 10, 1e-12), elsewhere the state is kept and lambda = 10 lambda; a loss that is not finite rejects.  lambda
+    starts at `damping`.  Everything is a device tensor selected by torch.where; nothing is read back.
+    -> fit_hand's dict and damping (P), the last lambda, and accepted (P), the count of steps taken."""
+    P, nvo, tv, tj, w, params, offset = _fit_setup(model, target_verts, target_joints, init, iterations, vert_weight, prior, flat_hand_mean, seal, "iterations")
+    dev, nj3, nb = model.device, model.nj * 3, model.nb
+    n = nj3 + nb + 3
+    with torch.cuda.device(dev), torch.no_grad():
+        w = None if w is None else w[..., 0].contiguous()
+        x = torch.cat(params, 1)
+        split = lambda t: (t[:, :nj3], t[:, nj3:nj3 + nb], t[:, nj3 + nb:])  # noqa: E731  (views: the entry takes row strides)
+        pd, off = torch.zeros(n, dtype=torch.float32, device=dev), torch.zeros(n, dtype=torch.float32, device=dev)
+        pd[3:nj3], pd[nj3:nj3 + nb] = float(prior[0]), float(prior[1])
+        off[3:nj3] = offset
+        lam = torch.full((P,), float(damping), dtype=torch.float32, device=dev)
+        accepted = torch.zeros(P, dtype=torch.int64, device=dev)
+        if P > 0 and iterations > 0:
+            H, g, L = _skin_normal(model, *split(x), tv, tj, w, flat_hand_mean, seal)
+            L = L + (pd * (x + off) ** 2).sum(1)
+            for _ in range(int(iterations)):
+                d = torch.diagonal(H, dim1=1, dim2=2)
+                M = H.clone()
+                torch.diagonal(M, dim1=1, dim2=2).add_(pd + lam[:, None] * (d + LM_TRACE_FLOOR * d.sum(1, keepdim=True) / n))
+                delta, ok = lm_solve(M, g + pd * (x + off))
+                x2 = x + delta
+                H2, g2, L2 = _skin_normal(model, *split(x2), tv, tj, w, flat_hand_mean, seal)
+                L2 = L2 + (pd * (x2 + off) ** 2).sum(1)
+                take = (L2 < L) & (ok != 0) & torch.isfinite(L2)
+                x, g, L = torch.where(take[:, None], x2, x), torch.where(take[:, None], g2, g), torch.where(take, L2, L)
+                H = torch.where(take[:, None, None], H2, H)
+                lam = torch.where(take, (lam / 10).clamp_min(LM_DAMPING_FLOOR), lam * 10)
+                accepted += take
+        params = [t.contiguous() for t in split(x)]
+        verts, joints = _skin(model, *params, flat_hand_mean, seal)
+        d = (verts - tv) if tv is not None else (joints - tj)
+        rms = (d * d).sum(-1).mean(-1).sqrt()
+    return {"pose": params[0], "betas": params[1], "trans": params[2], "verts": verts, "joints": joints, "rms": rms, "damping": lam, "accepted": accepted}
+
+
+def fit_two_hands_lm(right, left, target_verts, target_joints=None, init=None, iterations=10, damping=1e-3, vert_weight=None, prior=(0.0, 0.0),
+                     flat_hand_mean=False, seal=True):
+    """fit_two_hands by fit_hand_lm: the same arguments and stacking, two hands one after the other.  -> fit_two_hands' dict, whose pose, betas and
+    trans go into skin_two_hands and posed.mano_sequence unchanged, and damping (P, 2), accepted (P, 2)."""
+    return _fit_two(lambda mm, tv, tj, start, w: fit_hand_lm(mm, tv, tj, start, iterations, damping, w, prior, flat_hand_mean, seal),
+                    ("pose", "betas", "trans", "rms", "damping", "accepted"), right, left, target_verts, target_joints, init, vert_weight, seal)
+
+
+__all__ = ["MANO_PARENTS", "MANO_SEAL_RING", "ManoModel", "skin_hand", "skin_two_hands", "fit_hand", "fit_two_hands", "skin_normal_equations", "lm_solve",
+           "fit_hand_lm", "fit_two_hands_lm"]
