@@ -161,6 +161,26 @@ def test_a_nan_target_stays_in_its_pose(R, where):
     assert not torch.isfinite(got[1][5]).all() and not torch.isfinite(got[2][5]).all()  # (H does not see the targets)
 
 
+@pytest.mark.parametrize("case, seal", [((257, 16, 10, 5, "mano"), True), ((65, 32, 16, 2, "chain"), False)], ids=["sealed", "open"])
+def test_the_forward_is_its_own_exact_target(R, case, seal):
+    """What the shared forward of csrc/mano_forward.h is for: skin_hand's vertices and joints, passed as the targets, leave no residual at all --
+    loss is exactly 0.0 and g is zero in every element (the sign of a zero is not pinned) -- because the normal equations' vertex, joint and
+    sealed vertex are the forward's, operation for operation, and a chain fmaf(a, w * 0, acc) from +0 stays +0.  nv = 257 crosses a border of
+    64-vertex and of 256-vertex chunks, P = 5 is no multiple of the poses a lane carries.
+    Mutant: two addends of one ((a + b) + c) swapped.  With one vertex_forward() for all three files no single consumer can be edited so;
+    swapped inside the shared function all consumers move together and this test still holds, as it should."""
+    from vanerf_amd import mano
+    mm, pose, betas, trans = device_case(case)
+    verts, joints = mano.skin_hand(mm, pose, betas, trans, flat_hand_mean=False, seal=seal)
+    gen = torch.Generator(device="cuda").manual_seed(5)
+    w = torch.rand(verts.shape[:2], device="cuda", generator=gen) + 0.5
+    H, g, loss = mano.skin_normal_equations(mm, pose, betas, trans, verts, joints, w, flat_hand_mean=False, seal=seal)
+    print(f"{case}: largest |g| {float(g.abs().max()):.3e}, largest loss {float(loss.abs().max()):.3e}, largest |H| {float(H.abs().max()):.3e}")
+    assert float(H.abs().max()) > 0 and torch.isfinite(H).all()
+    assert g.abs().max() == 0
+    assert (loss == 0.0).all()
+
+
 # ------------------------------------------------------------------------------------------------
 # 3. the solve
 # ------------------------------------------------------------------------------------------------

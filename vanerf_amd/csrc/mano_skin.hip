@@ -3,18 +3,16 @@
 // tests hold these kernels to is the numpy code of tests/test_mano_skin_cpu.py.
 //
 // Three stages per call, all on the caller's stream:
-//   mano_joint_kernel   one wave per pose.  Lane j: Rodrigues of joint j and J_j from the fp64 joint tables; then the chain joint by joint
-//                       (parents[j] < j, so a loop over j is every tree's order), the twelve elements of G_j on twelve lanes, through LDS.
-//                       All fp64, as the small fp64 cores of vis_vertex_kernel and pose_transforms_kernel.  A (nj x 12) and the pose feature
-//                       ((nj - 1) x 9, R_j - I) are rounded once to fp32 into the workspace; the joints are rounded once into the output.
-//   mano_vertex_kernel  one lane per vertex and MANO_POSES_PER_LANE poses per lane: every value of the transposed tables ([row][k][v]:
-//                       consecutive lanes read consecutive vertices) serves all of a lane's poses.  A, the pose feature, betas and trans of the
-//                       block's poses sit in LDS and are read with wave-uniform indices.  fp32, every product and sum its own IEEE operation
-//                       (-ffp-contract=off), in one fixed order: a pose's bits depend neither on P nor on its place in the batch.
+//   mano_joint_kernel   one wave per pose: joint_forward() of mano_forward.h.  All fp64, as the small fp64 cores of vis_vertex_kernel and
+//                       pose_transforms_kernel.  A (nj x 12) and the pose feature ((nj - 1) x 9, R_j - I) are rounded once to fp32 into the
+//                       workspace; the joints are rounded once into the output.
+//   mano_vertex_kernel  one lane per vertex and MANO_POSES_PER_LANE poses per lane: vertex_forward() of mano_forward.h.  A, the pose feature,
+//                       betas and trans of the block's poses sit in LDS.  A pose's bits depend neither on P nor on its place in the batch.
 //   mano_seal_kernel    the appended wrist vertex: the fp32 sum of the WRITTEN ring vertices in the ring's order, from the left, times 1 / n.
 // The pack (once per model) transposes the tables and folds J_regressor into the template and the shape directions in fp64, so that J costs
 // 3 nj nb products per pose instead of a pass over the vertices.  No atomics, no device-side state; every output element is written.
 #include "common.h"
+#include "mano_forward.h"
 #include "mano_tables.h"
 
 #include <cmath>
@@ -32,7 +30,7 @@ namespace {
 constexpr int PP = MANO_POSES_PER_LANE;
 static_assert(PP >= 1 && PP <= 16, "MANO_POSES_PER_LANE: 1 .. 16");
 
-// (the packed model's layout, the limits and the entries' host-side helpers: mano_tables.h, shared with mano_skin_backward.hip)
+// (the packed model's layout, the limits and the entries' host-side helpers: mano_tables.h; the forward's arithmetic: mano_forward.h)
 
 // ------------------------------------------------------------------------------------------------------------------------------------------
 // pack
@@ -95,70 +93,13 @@ __global__ __launch_bounds__(64) void mano_joint_kernel(const ManoTables t, int 
                                                        int64_t trans_stride, int flat_hand_mean, float* __restrict__ ws, float* __restrict__ joints,
                                                        int64_t joints_stride)
 {
-    __shared__ double sR[MANO_MAX_NJ][9], sJ[MANO_MAX_NJ][3], sG[MANO_MAX_NJ][12];
+    __shared__ double sr[MANO_MAX_NJ][3], sR[MANO_MAX_NJ][9], sJ[MANO_MAX_NJ][3], sG[MANO_MAX_NJ][12];
     const size_t p = blockIdx.x;
     const int lane = threadIdx.x;
-    const int wsf = nj * 12 + (nj - 1) * 9;
-    float* A = ws + p * wsf;
-    float* pf = A + nj * 12;
-    if (lane < nj) {
-        double r[3];
-        for (int k = 0; k < 3; ++k) r[k] = (double)pose[p * pose_stride + 3 * lane + k] + (flat_hand_mean ? 0.0 : t.hm[3 * lane + k]);
-        const double e0 = r[0] + 1e-8, e1 = r[1] + 1e-8, e2 = r[2] + 1e-8; // the constant enters the norm only
-        const double angle = sqrt((e0 * e0 + e1 * e1) + e2 * e2);
-        const double dx = r[0] / angle, dy = r[1] / angle, dz = r[2] / angle;
-        const double s = sin(angle), c1 = 1.0 - cos(angle);
-        // R - I = sin K + (1 - cos) K^2 with K = skew(d); r = 0 gives d = 0 and R = I exactly
-        double m[9];
-        m[0] = c1 * -(dz * dz + dy * dy);
-        m[1] = s * -dz + c1 * (dx * dy);
-        m[2] = s * dy + c1 * (dx * dz);
-        m[3] = s * dz + c1 * (dx * dy);
-        m[4] = c1 * -(dz * dz + dx * dx);
-        m[5] = s * -dx + c1 * (dy * dz);
-        m[6] = s * -dy + c1 * (dx * dz);
-        m[7] = s * dx + c1 * (dy * dz);
-        m[8] = c1 * -(dx * dx + dy * dy);
-        for (int e = 0; e < 9; ++e) {
-            sR[lane][e] = (e % 4 == 0 ? 1.0 : 0.0) + m[e];
-            if (lane >= 1) pf[(lane - 1) * 9 + e] = (float)m[e];
-        }
-        for (int k = 0; k < 3; ++k) {
-            double sum = 0.0;
-            for (int b = 0; b < nb; ++b) sum = sum + t.Js[(lane * 3 + k) * nb + b] * (double)betas[p * betas_stride + b];
-            sJ[lane][k] = t.Jt[lane * 3 + k] + sum;
-        }
-    }
-    __syncthreads();
-    // the chain, joint by joint; element (row, col) of G_j on lane 4 row + col
-    const int row = (lane >> 2) % 3, col = lane & 3;
-    for (int j = 0; j < nj; ++j) {
-        if (lane < 12) {
-            double g;
-            if (j == 0) {
-                g = col < 3 ? sR[0][row * 3 + col] : sJ[0][row];
-            } else {
-                int par = t.parents[j];
-                par = par < 0 ? 0 : (par > j - 1 ? j - 1 : par); // (checked at the pack; a foreign buffer must not index outside the block's LDS)
-                const double* G = sG[par];
-                double l0, l1, l2;
-                if (col < 3) { l0 = sR[j][col]; l1 = sR[j][3 + col]; l2 = sR[j][6 + col]; }
-                else { l0 = sJ[j][0] - sJ[par][0]; l1 = sJ[j][1] - sJ[par][1]; l2 = sJ[j][2] - sJ[par][2]; }
-                g = (G[row * 4] * l0 + G[row * 4 + 1] * l1) + G[row * 4 + 2] * l2;
-                if (col == 3) g = g + G[row * 4 + 3];
-            }
-            sG[j][row * 4 + col] = g;
-        }
-        __syncthreads();
-    }
-    if (lane < nj) {
-        const double* G = sG[lane];
-        for (int k = 0; k < 3; ++k) {
-            for (int c = 0; c < 3; ++c) A[lane * 12 + k * 4 + c] = (float)G[k * 4 + c];
-            A[lane * 12 + k * 4 + 3] = (float)(G[k * 4 + 3] - ((G[k * 4] * sJ[lane][0] + G[k * 4 + 1] * sJ[lane][1]) + G[k * 4 + 2] * sJ[lane][2]));
-            joints[p * joints_stride + 3 * lane + k] = (float)(G[k * 4 + 3] + (double)trans[p * trans_stride + k]);
-        }
-    }
+    float* A = ws + p * (size_t)(nj * 12 + (nj - 1) * 9);
+    joint_forward(t, nj, nb, pose + p * pose_stride, betas + p * betas_stride, flat_hand_mean, lane, sr, sR, sJ, sG, A, A + nj * 12);
+    if (lane < nj)
+        for (int k = 0; k < 3; ++k) joints[p * joints_stride + 3 * lane + k] = (float)(sG[lane][k * 4 + 3] + (double)trans[p * trans_stride + k]);
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------------------
@@ -181,69 +122,14 @@ __global__ __launch_bounds__(MV_BLOCK) void mano_vertex_kernel(const ManoTables 
     __syncthreads();
     const int v = vb * MV_BLOCK + threadIdx.x;
     if (v >= nv) return;
-    const size_t n = (size_t)nv;
-    float acc[PP][3], vp[PP][3];
-    const float t0 = t.vt[v], t1 = t.vt[n + v], t2 = t.vt[2 * n + v];
-    // v_shaped = v_template + (sum over b, from b = 0, of shapedirs_b betas_b)
-#pragma unroll
-    for (int q = 0; q < PP; ++q) acc[q][0] = acc[q][1] = acc[q][2] = 0.0f;
-    for (int b = 0; b < nb; ++b) {
-        const float x0 = t.sd[(size_t)(b * 3) * n + v], x1 = t.sd[(size_t)(b * 3 + 1) * n + v], x2 = t.sd[(size_t)(b * 3 + 2) * n + v];
-#pragma unroll
-        for (int q = 0; q < PP; ++q) {
-            const float be = sm[q * per + wsf + b];
-            acc[q][0] = acc[q][0] + x0 * be;
-            acc[q][1] = acc[q][1] + x1 * be;
-            acc[q][2] = acc[q][2] + x2 * be;
-        }
-    }
-#pragma unroll
-    for (int q = 0; q < PP; ++q) {
-        vp[q][0] = t0 + acc[q][0];
-        vp[q][1] = t1 + acc[q][1];
-        vp[q][2] = t2 + acc[q][2];
-        acc[q][0] = acc[q][1] = acc[q][2] = 0.0f;
-    }
-    // v_posed = v_shaped + (sum over the rows, from row 0, of posedirs_row feature_row)
-    const int rows = (nj - 1) * 9;
-    for (int r = 0; r < rows; ++r) {
-        const float x0 = t.pd[(size_t)(r * 3) * n + v], x1 = t.pd[(size_t)(r * 3 + 1) * n + v], x2 = t.pd[(size_t)(r * 3 + 2) * n + v];
-#pragma unroll
-        for (int q = 0; q < PP; ++q) {
-            const float f = sm[q * per + nj * 12 + r];
-            acc[q][0] = acc[q][0] + x0 * f;
-            acc[q][1] = acc[q][1] + x1 * f;
-            acc[q][2] = acc[q][2] + x2 * f;
-        }
-    }
-#pragma unroll
-    for (int q = 0; q < PP; ++q) {
-        vp[q][0] = vp[q][0] + acc[q][0];
-        vp[q][1] = vp[q][1] + acc[q][1];
-        vp[q][2] = vp[q][2] + acc[q][2];
-    }
-    // T = sum over j, from j = 0, of w_vj A_j
-    float T[PP][12];
-#pragma unroll
-    for (int q = 0; q < PP; ++q)
-#pragma unroll
-        for (int e = 0; e < 12; ++e) T[q][e] = 0.0f;
-    for (int j = 0; j < nj; ++j) {
-        const float w = t.wt[(size_t)j * n + v];
-#pragma unroll
-        for (int q = 0; q < PP; ++q)
-#pragma unroll
-            for (int e = 0; e < 12; ++e) T[q][e] = T[q][e] + w * sm[q * per + j * 12 + e];
-    }
+    float x[PP][3], T[PP][12], pos[PP][3];
+    vertex_forward<PP>(t, v, nv, nj, nb, PoseValues{sm, sm + nj * 12, sm + wsf, sm + wsf + nb, per}, x, T, pos);
 #pragma unroll
     for (int q = 0; q < PP; ++q) {
         if (p0 + q < (size_t)P) { // (block-uniform)
             float* o = verts + (p0 + q) * verts_stride + (size_t)v * 3;
 #pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                const float x = ((T[q][4 * k] * vp[q][0] + T[q][4 * k + 1] * vp[q][1]) + T[q][4 * k + 2] * vp[q][2]) + T[q][4 * k + 3];
-                o[k] = x + sm[q * per + wsf + nb + k];
-            }
+            for (int k = 0; k < 3; ++k) o[k] = pos[q][k];
         }
     }
 }
@@ -266,23 +152,19 @@ __global__ __launch_bounds__(MV_BLOCK) void mano_seal_kernel(float* __restrict__
 
 extern "C" int64_t vanerf_mano_packed_bytes(int nv, int nj, int nb)
 {
-    int64_t bytes = -1;
-    const int rc = guarded([&] {
+    return size_query([&] {
         check_sizes("vanerf_mano_packed_bytes", nv, nj, nb);
-        bytes = mano_layout(nv, nj, nb).bytes;
+        return mano_layout(nv, nj, nb).bytes;
     });
-    return rc == VANERF_OK ? bytes : (int64_t)rc;
 }
 
 extern "C" int64_t vanerf_mano_workspace_bytes(int nj, int P)
 {
-    int64_t bytes = -1;
-    const int rc = guarded([&] {
+    return size_query([&] {
         if (nj < 1 || nj > MANO_MAX_NJ) throw_error("vanerf_mano_workspace_bytes: nj=%d joints (1 .. %d)", nj, MANO_MAX_NJ);
         if (P < 0) throw_error("vanerf_mano_workspace_bytes: P=%d poses (at least 0)", P);
-        bytes = (int64_t)P * ws_floats(nj) * 4;
+        return (int64_t)P * ws_floats(nj) * 4;
     });
-    return rc == VANERF_OK ? bytes : (int64_t)rc;
 }
 
 extern "C" int vanerf_mano_poses_per_lane(void) { return PP; }
@@ -325,20 +207,12 @@ extern "C" int vanerf_mano_skin(const void* packed, int nv, int nj, int nb, cons
         const char* who = "vanerf_mano_skin";
         check_sizes(who, nv, nj, nb);
         if (P < 0) throw_error("%s: P=%d poses (at least 0)", who, P);
-        if (n_ring < 0 || n_ring > MANO_MAX_RING) throw_error("%s: n_ring=%d (0 = no seal .. %d)", who, n_ring, MANO_MAX_RING);
-        if (n_ring > 0 && !ring) throw_error("%s: null argument (ring with n_ring=%d)", who, n_ring);
-        IntList64 rg;
-        for (int u = 0; u < MANO_MAX_RING; ++u) rg.v[u] = 0;
-        for (int u = 0; u < n_ring; ++u) {
-            if (ring[u] < 0 || ring[u] >= nv) throw_error("%s: ring[%d]=%d names no vertex of nv=%d", who, u, ring[u], nv);
-            rg.v[u] = ring[u];
-        }
-        const int64_t row = ((int64_t)nv + (n_ring > 0 ? 1 : 0)) * 3;
-        if (pose_stride < (int64_t)nj * 3) throw_error("%s: pose_stride=%lld is below a row's %d floats", who, (long long)pose_stride, nj * 3);
-        if (betas_stride < nb) throw_error("%s: betas_stride=%lld is below a row's %d floats", who, (long long)betas_stride, nb);
-        if (trans_stride < 3) throw_error("%s: trans_stride=%lld is below a row's 3 floats", who, (long long)trans_stride);
-        if (verts_stride < row) throw_error("%s: verts_stride=%lld is below a row's %lld floats", who, (long long)verts_stride, (long long)row);
-        if (joints_stride < (int64_t)nj * 3) throw_error("%s: joints_stride=%lld is below a row's %d floats", who, (long long)joints_stride, nj * 3);
+        const IntList64 rg = ring_list(who, ring, n_ring, nv);
+        check_stride(who, "pose", pose_stride, nj * 3);
+        check_stride(who, "betas", betas_stride, nb);
+        check_stride(who, "trans", trans_stride, 3);
+        check_stride(who, "verts", verts_stride, ((int64_t)nv + (n_ring > 0 ? 1 : 0)) * 3);
+        check_stride(who, "joints", joints_stride, nj * 3);
         if (P == 0) return;
         if (!packed || !pose || !betas || !trans || !workspace || !verts || !joints) throw_error("%s: null argument", who);
         if ((uintptr_t)packed & 15) throw_error("%s: packed must be 16-byte aligned", who);

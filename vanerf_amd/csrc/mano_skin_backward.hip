@@ -1,22 +1,22 @@
 // mano_skin_backward.hip -- the vector-Jacobian product of vanerf_mano_skin (the definition is the comment of
 // vanerf_mano_skin in the header, steps 1-7): gradients of the vertices and joints -> gradients of pose, betas and trans, on the device, for a
-// batch of poses.  Stateless: what the forward computed is recomputed from pose and betas.  The restatement the tests hold these kernels to
-// is the torch code of tests/test_mano_backward_cpu.py under fp64 autograd.
+// batch of poses.  Stateless: what the forward computed is recomputed from pose and betas by the forward's own functions (mano_forward.h).
+// The restatement the tests hold these kernels to is the torch code of tests/test_mano_backward_cpu.py under fp64 autograd.
 //
 // Three launches per call, all on the caller's stream:
-//   mano_bwd_joint_forward_kernel  one wave per pose, fp64: R, J and the chain exactly as mano_joint_kernel computes them; A (nj x 12) and the
-//                                  pose feature ((nj-1) x 9) rounded once to fp32 into the workspace (the forward's bits).
-//   mano_bwd_vertex_kernel         one block per pose and chunk of 256 vertices.  Phase 1, one lane per vertex, fp32 in the forward's order:
-//                                  x = v_posed and T = sum_j w A_j again, the seal's share folded into the ring vertices' gradient g,
+//   mano_bwd_joint_forward_kernel  one wave per pose, fp64: joint_forward(); A (nj x 12) and the pose feature ((nj-1) x 9) rounded once to
+//                                  fp32 into the workspace.
+//   mano_bwd_vertex_kernel         one block per pose and chunk of 256 vertices.  Phase 1, one lane per vertex, fp32: vertex_forward() for
+//                                  x = v_posed and T = sum_j w A_j, the seal's share folded into the ring vertices' gradient g,
 //                                  g_x = T^R^T g; g_x, g and x staged in LDS.  Phase 2, one wave per output value (or per joint's twelve):
 //                                  lanes over the chunk's vertices with coalesced reads of the [row][k][v] tables, fp32 products summed in
 //                                  fp64, a butterfly over the wave, one fp64 partial per (pose, chunk, value) into the workspace.
-//   mano_bwd_joint_kernel          one wave per pose, fp64: the chain again, the chunks' partials summed in chunk order, the chain in reverse
+//   mano_bwd_joint_kernel          one wave per pose, fp64: joint_forward(), the chunks' partials summed in chunk order, the chain in reverse
 //                                  (j = nj-1 .. 1 into parents[j]), the Rodrigues backward per joint, J_shapedirs^T . dJ; rounded once to fp32.
 // A and the pose feature sit in LDS and are read with wave-uniform indices.  No atomics, no device-side state, every requested output
 // element written, every sum in one fixed order: a pose's gradient bits depend neither on P nor on its row in the batch.
 #include "common.h"
-#include "mano_joint_forward.h"
+#include "mano_forward.h"
 #include "mano_tables.h"
 
 #include <cmath>
@@ -43,13 +43,6 @@ __global__ __launch_bounds__(64) void mano_bwd_joint_forward_kernel(const ManoTa
     joint_forward(t, nj, nb, pose + p * pose_stride, betas + p * betas_stride, flat_hand_mean, threadIdx.x, sr, sR, sJ, sG, A, A + nj * 12);
 }
 
-__device__ __forceinline__ double wave_sum(double x)
-{
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) x = x + __shfl_xor(x, o, 64); // a butterfly: the same order of additions whatever the data
-    return x;
-}
-
 // ------------------------------------------------------------------------------------------------------------------------------------------
 // vertices: one block per pose and chunk of 256 vertices
 // ------------------------------------------------------------------------------------------------------------------------------------------
@@ -72,36 +65,8 @@ __global__ __launch_bounds__(BW_CHUNK) void mano_bwd_vertex_kernel(const ManoTab
     const int v = ch * BW_CHUNK + tid;
     float g[3] = {0.0f, 0.0f, 0.0f}, x[3] = {0.0f, 0.0f, 0.0f}, gx[3] = {0.0f, 0.0f, 0.0f};
     if (v < nv) {
-        // x = v_posed, in the forward's order
-        float acc0 = 0.0f, acc1 = 0.0f, acc2 = 0.0f;
-        for (int b = 0; b < nb; ++b) {
-            const float be = sb[b];
-            acc0 = acc0 + t.sd[(size_t)(b * 3) * n + v] * be;
-            acc1 = acc1 + t.sd[(size_t)(b * 3 + 1) * n + v] * be;
-            acc2 = acc2 + t.sd[(size_t)(b * 3 + 2) * n + v] * be;
-        }
-        x[0] = t.vt[v] + acc0;
-        x[1] = t.vt[n + v] + acc1;
-        x[2] = t.vt[2 * n + v] + acc2;
-        acc0 = acc1 = acc2 = 0.0f;
-        for (int r = 0; r < rows; ++r) {
-            const float f = sf[r];
-            acc0 = acc0 + t.pd[(size_t)(r * 3) * n + v] * f;
-            acc1 = acc1 + t.pd[(size_t)(r * 3 + 1) * n + v] * f;
-            acc2 = acc2 + t.pd[(size_t)(r * 3 + 2) * n + v] * f;
-        }
-        x[0] = x[0] + acc0;
-        x[1] = x[1] + acc1;
-        x[2] = x[2] + acc2;
-        // the rotation of T = sum over j, from j = 0, of w_vj A_j
-        float T[9];
-#pragma unroll
-        for (int e = 0; e < 9; ++e) T[e] = 0.0f;
-        for (int j = 0; j < nj; ++j) {
-            const float w = t.wt[(size_t)j * n + v];
-#pragma unroll
-            for (int e = 0; e < 9; ++e) T[e] = T[e] + w * sA[j * 12 + (e / 3) * 4 + e % 3];
-        }
+        float T[12]; // (only T's rotation is read: its translation's sums are dead code)
+        vertex_forward<1>(t, v, nv, nj, nb, PoseValues{sA, sf, sb, nullptr, 0}, &x, &T, nullptr);
         // g: the vertex's own gradient, and 1 / n_ring of the sealed vertex's for every time the ring names this vertex
         const float* gv = grad_verts + p * gv_stride;
 #pragma unroll
@@ -119,7 +84,7 @@ __global__ __launch_bounds__(BW_CHUNK) void mano_bwd_vertex_kernel(const ManoTab
             }
         }
 #pragma unroll
-        for (int c = 0; c < 3; ++c) gx[c] = (T[c] * g[0] + T[3 + c] * g[1]) + T[6 + c] * g[2];
+        for (int c = 0; c < 3; ++c) gx[c] = (T[c] * g[0] + T[4 + c] * g[1]) + T[8 + c] * g[2];
     }
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
@@ -233,8 +198,7 @@ __global__ __launch_bounds__(64) void mano_bwd_joint_kernel(const ManoTables t, 
     __syncthreads();
     // the chain in reverse: G_j^R = Gp^R R_j, G_j^t = Gp^R (J_j - J_par) + Gp^t; every child of a joint comes before the joint itself
     for (int j = nj - 1; j >= 1; --j) {
-        int par = t.parents[j];
-        par = par < 0 ? 0 : (par > j - 1 ? j - 1 : par);
+        const int par = parent_of(t, j);
         const double* Gp = sG[par];
         const double* dG = sdG[j];
         if (lane < 9) {
@@ -260,18 +224,11 @@ __global__ __launch_bounds__(64) void mano_bwd_joint_kernel(const ManoTables t, 
         double M[9];
 #pragma unroll
         for (int e = 0; e < 9; ++e) M[e] = sdR[lane][e] + (lane >= 1 ? sIn[nj * 12 + (lane - 1) * 9 + e] : 0.0);
-        const double r0 = sr[lane][0], r1 = sr[lane][1], r2 = sr[lane][2];
-        const double e0 = r0 + 1e-8, e1 = r1 + 1e-8, e2 = r2 + 1e-8;
-        const double a = sqrt((e0 * e0 + e1 * e1) + e2 * e2);
-        const double d0 = r0 / a, d1 = r1 / a, d2 = r2 / a;
-        const double s = sin(a), co = cos(a), c1 = 1.0 - co;
-        const double K[9] = {0.0, -d2, d1, d2, 0.0, -d0, -d1, d0, 0.0};
-        double K2[9], dK[9];
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-            for (int k = 0; k < 3; ++k) K2[i * 3 + k] = (K[i * 3] * K[k] + K[i * 3 + 1] * K[3 + k]) + K[i * 3 + 2] * K[6 + k];
-        double ds = 0.0, dc1 = 0.0;
+        const double* r = sr[lane];
+        const RodriguesTerms q = rodrigues_terms(r);
+        const double a = q.a, s = q.s, co = q.co, c1 = q.c1;
+        const double *e = q.e, *K = q.K, *K2 = q.K2;
+        double dK[9], ds = 0.0, dc1 = 0.0;
 #pragma unroll
         for (int e = 0; e < 9; ++e) {
             ds = ds + M[e] * K[e];
@@ -286,11 +243,11 @@ __global__ __launch_bounds__(64) void mano_bwd_joint_kernel(const ManoTables t, 
                 dK[i * 3 + k] = s * M[i * 3 + k] + c1 * (mkt + ktm);
             }
         const double dd0 = dK[7] - dK[5], dd1 = dK[2] - dK[6], dd2 = dK[3] - dK[1];
-        const double da = (ds * co + dc1 * s) - ((dd0 * r0 + dd1 * r1) + dd2 * r2) / (a * a);
+        const double da = (ds * co + dc1 * s) - ((dd0 * r[0] + dd1 * r[1]) + dd2 * r[2]) / (a * a);
         float* o = grad_pose + p * gp_stride + 3 * lane;
-        o[0] = (float)(dd0 / a + da * (e0 / a));
-        o[1] = (float)(dd1 / a + da * (e1 / a));
-        o[2] = (float)(dd2 / a + da * (e2 / a));
+        o[0] = (float)(dd0 / a + da * (e[0] / a));
+        o[1] = (float)(dd1 / a + da * (e[1] / a));
+        o[2] = (float)(dd2 / a + da * (e[2] / a));
     }
     // grad_betas = shapedirs^T . g_x + J_shapedirs^T . dJ
     if (grad_betas && lane < nb) {
@@ -318,14 +275,12 @@ int64_t bw_partial_bytes(int nv, int nj, int nb, int P)
 
 extern "C" int64_t vanerf_mano_skin_backward_workspace_bytes(int nv, int nj, int nb, int P)
 {
-    int64_t bytes = -1;
-    const int rc = guarded([&] {
+    return size_query([&] {
         const char* who = "vanerf_mano_skin_backward_workspace_bytes";
         check_sizes(who, nv, nj, nb);
         if (P < 0) throw_error("%s: P=%d poses (at least 0)", who, P);
-        bytes = bw_partial_bytes(nv, nj, nb, P) + (int64_t)P * ws_floats(nj) * 4; // the fp64 partials first, then A and the pose feature
+        return bw_partial_bytes(nv, nj, nb, P) + (int64_t)P * ws_floats(nj) * 4; // the fp64 partials first, then A and the pose feature
     });
-    return rc == VANERF_OK ? bytes : (int64_t)rc;
 }
 
 extern "C" int vanerf_mano_skin_backward(const void* packed, int nv, int nj, int nb, const float* pose, int64_t pose_stride, const float* betas,
@@ -338,25 +293,14 @@ extern "C" int vanerf_mano_skin_backward(const void* packed, int nv, int nj, int
         const char* who = "vanerf_mano_skin_backward";
         check_sizes(who, nv, nj, nb);
         if (P < 0) throw_error("%s: P=%d poses (at least 0)", who, P);
-        if (n_ring < 0 || n_ring > MANO_MAX_RING) throw_error("%s: n_ring=%d (0 = no seal .. %d)", who, n_ring, MANO_MAX_RING);
-        if (n_ring > 0 && !ring) throw_error("%s: null argument (ring with n_ring=%d)", who, n_ring);
-        IntList64 rg;
-        for (int u = 0; u < MANO_MAX_RING; ++u) rg.v[u] = -1;
-        for (int u = 0; u < n_ring; ++u) {
-            if (ring[u] < 0 || ring[u] >= nv) throw_error("%s: ring[%d]=%d names no vertex of nv=%d", who, u, ring[u], nv);
-            rg.v[u] = ring[u];
-        }
-        const int64_t row = ((int64_t)nv + (n_ring > 0 ? 1 : 0)) * 3;
-        if (pose_stride < (int64_t)nj * 3) throw_error("%s: pose_stride=%lld is below a row's %d floats", who, (long long)pose_stride, nj * 3);
-        if (betas_stride < nb) throw_error("%s: betas_stride=%lld is below a row's %d floats", who, (long long)betas_stride, nb);
-        if (grad_verts && grad_verts_stride < row)
-            throw_error("%s: grad_verts_stride=%lld is below a row's %lld floats", who, (long long)grad_verts_stride, (long long)row);
-        if (grad_joints && grad_joints_stride < (int64_t)nj * 3)
-            throw_error("%s: grad_joints_stride=%lld is below a row's %d floats", who, (long long)grad_joints_stride, nj * 3);
-        if (grad_pose && grad_pose_stride < (int64_t)nj * 3)
-            throw_error("%s: grad_pose_stride=%lld is below a row's %d floats", who, (long long)grad_pose_stride, nj * 3);
-        if (grad_betas && grad_betas_stride < nb) throw_error("%s: grad_betas_stride=%lld is below a row's %d floats", who, (long long)grad_betas_stride, nb);
-        if (grad_trans && grad_trans_stride < 3) throw_error("%s: grad_trans_stride=%lld is below a row's 3 floats", who, (long long)grad_trans_stride);
+        const IntList64 rg = ring_list(who, ring, n_ring, nv);
+        check_stride(who, "pose", pose_stride, nj * 3);
+        check_stride(who, "betas", betas_stride, nb);
+        if (grad_verts) check_stride(who, "grad_verts", grad_verts_stride, ((int64_t)nv + (n_ring > 0 ? 1 : 0)) * 3);
+        if (grad_joints) check_stride(who, "grad_joints", grad_joints_stride, nj * 3);
+        if (grad_pose) check_stride(who, "grad_pose", grad_pose_stride, nj * 3);
+        if (grad_betas) check_stride(who, "grad_betas", grad_betas_stride, nb);
+        if (grad_trans) check_stride(who, "grad_trans", grad_trans_stride, 3);
         if (P == 0) return;
         if (!packed || !pose || !betas) throw_error("%s: null argument", who);
         if (!grad_verts && !grad_joints) throw_error("%s: null argument (grad_verts and grad_joints are both null: nothing to differentiate)", who);

@@ -2,8 +2,8 @@
 // needs (the definition is the comment of vanerf_mano_skin in the header, steps 1-7, differentiated exactly as
 // vanerf_mano_skin_backward differentiates it).  With x = (pose, betas, trans), n = 3 nj + nb + 3 unknowns, the residuals r = (v - v*, j - j*),
 // their Jacobian J = dr/dx and the weights W = (w_v / nv_out, 1 / nj), vanerf_mano_skin_normal writes H = J^T W J, g = J^T W r and
-// loss = r^T W r per pose.  Stateless: the forward is recomputed with the forward's arithmetic.  The restatement the tests hold these kernels
-// to is the torch code of tests/test_mano_lm_cpu.py (forward-mode autograd in fp64).
+// loss = r^T W r per pose.  Stateless: the forward is recomputed by the forward's own functions (mano_forward.h).  The restatement the tests
+// hold these kernels to is the torch code of tests/test_mano_lm_cpu.py (forward-mode autograd in fp64).
 //
 // The tangents.  A pose parameter (a, axis) turns everything below joint a about that joint: with D = G_par(a)^R (dR_a / dr_axis) G_a^R^-1,
 // dA_j = D [A_j^R | A_j^t - G_a^t] for EVERY descendant j of a (a itself included) and zero elsewhere.  So the table a pose needs is D (three
@@ -12,11 +12,10 @@
 // A shape coefficient moves x (shapedirs) and the translation parts: dA_j^t = dG_j^t - G_j^R (J_regressor . shapedirs)_j.
 //
 // Three launches per call, all on the caller's stream:
-//   mano_nrm_joint_kernel   one wave per pose, fp64: the chain of mano_bwd_joint_forward_kernel, operation for operation; the Rodrigues
-//                           derivative, D, G^t, dA^t / dbetas, each rounded once to fp32 into the workspace beside A and the pose feature; the
-//                           joints' residual rows (dG_j^t / dx and j - j*) in fp64.
-//   mano_nrm_vertex_kernel  one block of one wave per pose and chunk of 64 vertices.  Phase 1, one lane per vertex, fp32: x = v_posed, T and
-//                           the vertex as the forward computes them, the 3 x (n + 1) block of (J | r) into an LDS panel [column][row] (rows
+//   mano_nrm_joint_kernel   one wave per pose, fp64: joint_forward(); the Rodrigues derivative, D, G^t, dA^t / dbetas, each rounded once to
+//                           fp32 into the workspace beside A and the pose feature; the joints' residual rows (dG_j^t / dx and j - j*) in fp64.
+//   mano_nrm_vertex_kernel  one block of one wave per pose and chunk of 64 vertices.  Phase 1, one lane per vertex, fp32: vertex_forward() for
+//                           x = v_posed, T and the vertex, the 3 x (n + 1) block of (J | r) into an LDS panel [column][row] (rows
 //                           k * 64 + lane: conflict-free writes).  Phase 2: the lower triangle of panel^T diag(W) panel in 32 x 32 tiles of the
 //                           exact-fp32 MFMA (v_mfma_f32_32x32x2_f32) over the 192 rows in row order: fp32 products w * b, then per element the
 //                           chain fmaf(a, w b, acc) in fp32 (the loss, one entry, is added in fp64 instead: a lane's three rows, then a butterfly).
@@ -28,7 +27,7 @@
 // Tangent tables sit in LDS and are read with wave-uniform indices; no per-lane array is indexed at run time.  No atomics, no device-side
 // state; every sum has one fixed order: a pose's bits depend neither on P nor on its row in the batch.
 #include "common.h"
-#include "mano_joint_forward.h"
+#include "mano_forward.h"
 #include "mano_tables.h"
 
 #include <cmath>
@@ -64,12 +63,6 @@ __host__ __device__ inline TanLayout tan_layout(int nj, int nb)
 
 __host__ __device__ inline int tri_size(int ne) { return ne * (ne + 1) / 2; }
 
-__device__ __forceinline__ int parent_of(const ManoTables& t, int j) // j >= 1; clamped as the forward clamps it
-{
-    const int par = t.parents[j];
-    return par < 0 ? 0 : (par > j - 1 ? j - 1 : par);
-}
-
 __device__ __forceinline__ unsigned ancestors_of(const ManoTables& t, int j) // bit a: a is j or above it
 {
     unsigned m = 1u << j;
@@ -100,17 +93,9 @@ __global__ __launch_bounds__(64) void mano_nrm_joint_kernel(const ManoTables t, 
         sAnc[lane] = ancestors_of(t, lane);
         // the Rodrigues derivative: R = I + sin(a) K + (1 - cos(a)) K K, K = skew(d), d = r / a, a = |r + 1e-8|;
         // da/dr_x = e_x / a, dd_i/dr_x = (delta_ix - d_i e_x / a) / a
-        const double r0 = sr[lane][0], r1 = sr[lane][1], r2 = sr[lane][2];
-        const double e[3] = {r0 + 1e-8, r1 + 1e-8, r2 + 1e-8};
-        const double a = sqrt((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]);
-        const double d[3] = {r0 / a, r1 / a, r2 / a};
-        const double s = sin(a), co = cos(a), c1 = 1.0 - co;
-        const double K[9] = {0.0, -d[2], d[1], d[2], 0.0, -d[0], -d[1], d[0], 0.0};
-        double K2[9];
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-            for (int k = 0; k < 3; ++k) K2[i * 3 + k] = (K[i * 3] * K[k] + K[i * 3 + 1] * K[3 + k]) + K[i * 3 + 2] * K[6 + k];
+        const RodriguesTerms q = rodrigues_terms(sr[lane]);
+        const double a = q.a, s = q.s, co = q.co, c1 = q.c1;
+        const double *e = q.e, *d = q.d, *K = q.K, *K2 = q.K2;
         double Gp[9], Ga[9];
         const int par = lane >= 1 ? parent_of(t, lane) : 0;
 #pragma unroll
@@ -300,44 +285,9 @@ __global__ __launch_bounds__(NQ_CHUNK) void mano_nrm_vertex_kernel(const ManoTab
         for (int u = 1; u < MANO_MAX_RING; ++u)
             if (u == lane && u < n_ring) v = ring.v[u]; // (compile-time indices: the list stays in scalar registers)
     }
-    const float* sb = sT + L.total;
-    // x = v_posed, T and the vertex, in the forward's order
+    // x = v_posed, T and the vertex
     float x[3], T[12], pos[3];
-    {
-        float acc0 = 0.0f, acc1 = 0.0f, acc2 = 0.0f;
-        for (int b = 0; b < nb; ++b) {
-            const float be = sb[b];
-            acc0 = acc0 + t.sd[(size_t)(b * 3) * nvs + v] * be;
-            acc1 = acc1 + t.sd[(size_t)(b * 3 + 1) * nvs + v] * be;
-            acc2 = acc2 + t.sd[(size_t)(b * 3 + 2) * nvs + v] * be;
-        }
-        x[0] = t.vt[v] + acc0;
-        x[1] = t.vt[nvs + v] + acc1;
-        x[2] = t.vt[2 * nvs + v] + acc2;
-        acc0 = acc1 = acc2 = 0.0f;
-        const int rows = (nj - 1) * 9;
-        for (int r = 0; r < rows; ++r) {
-            const float f = sT[L.pf + r];
-            acc0 = acc0 + t.pd[(size_t)(r * 3) * nvs + v] * f;
-            acc1 = acc1 + t.pd[(size_t)(r * 3 + 1) * nvs + v] * f;
-            acc2 = acc2 + t.pd[(size_t)(r * 3 + 2) * nvs + v] * f;
-        }
-        x[0] = x[0] + acc0;
-        x[1] = x[1] + acc1;
-        x[2] = x[2] + acc2;
-#pragma unroll
-        for (int e = 0; e < 12; ++e) T[e] = 0.0f;
-        for (int j = 0; j < nj; ++j) {
-            const float w = t.wt[(size_t)j * nvs + v];
-#pragma unroll
-            for (int e = 0; e < 12; ++e) T[e] = T[e] + w * sT[L.A + j * 12 + e];
-        }
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const float o = ((T[4 * k] * x[0] + T[4 * k + 1] * x[1]) + T[4 * k + 2] * x[2]) + T[4 * k + 3];
-            pos[k] = o + sb[nb + k];
-        }
-    }
+    vertex_forward<1>(t, v, nv, nj, nb, PoseValues{sT + L.A, sT + L.pf, sT + L.total, sT + L.total + nb, 0}, &x, &T, &pos);
     // the rows' weights, the residual column and the identity of trans
     {
         float w = 0.0f;
@@ -440,8 +390,7 @@ __global__ __launch_bounds__(NQ_CHUNK) void mano_nrm_vertex_kernel(const ManoTab
             const float rr = Pt[n * NQ_RS + k * NQ_CHUNK + lane];
             l = l + (double)(sW[k * NQ_CHUNK + lane] * rr) * (double)rr;
         }
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) l = l + __shfl_xor(l, o, 64);
+        l = wave_sum(l);
         if (lane == 0) out[tri_size(ne) - 1] = (float)l;
     }
     // phase 2: the rest of the lower triangle of panel^T diag(w) panel on the matrix cores
@@ -567,14 +516,12 @@ NrmSizes nrm_sizes(int nv, int nj, int nb, int P)
 
 extern "C" int64_t vanerf_mano_skin_normal_workspace_bytes(int nv, int nj, int nb, int P)
 {
-    int64_t bytes = -1;
-    const int rc = guarded([&] {
+    return size_query([&] {
         const char* who = "vanerf_mano_skin_normal_workspace_bytes";
         check_sizes(who, nv, nj, nb);
         if (P < 0) throw_error("%s: P=%d poses (at least 0)", who, P);
-        bytes = nrm_sizes(nv, nj, nb, P).total;
+        return nrm_sizes(nv, nj, nb, P).total;
     });
-    return rc == VANERF_OK ? bytes : (int64_t)rc;
 }
 
 extern "C" int vanerf_mano_skin_normal(const void* packed, int nv, int nj, int nb, const float* pose, int64_t pose_stride, const float* betas,
@@ -588,26 +535,17 @@ extern "C" int vanerf_mano_skin_normal(const void* packed, int nv, int nj, int n
         const char* who = "vanerf_mano_skin_normal";
         check_sizes(who, nv, nj, nb);
         if (P < 0) throw_error("%s: P=%d poses (at least 0)", who, P);
-        if (n_ring < 0 || n_ring > MANO_MAX_RING) throw_error("%s: n_ring=%d (0 = no seal .. %d)", who, n_ring, MANO_MAX_RING);
-        if (n_ring > 0 && !ring) throw_error("%s: null argument (ring with n_ring=%d)", who, n_ring);
-        IntList64 rg;
-        for (int u = 0; u < MANO_MAX_RING; ++u) rg.v[u] = 0;
-        for (int u = 0; u < n_ring; ++u) {
-            if (ring[u] < 0 || ring[u] >= nv) throw_error("%s: ring[%d]=%d names no vertex of nv=%d", who, u, ring[u], nv);
-            rg.v[u] = ring[u];
-        }
+        const IntList64 rg = ring_list(who, ring, n_ring, nv);
         const int64_t nvo = (int64_t)nv + (n_ring > 0 ? 1 : 0), n = 3 * nj + nb + 3;
-        if (pose_stride < (int64_t)nj * 3) throw_error("%s: pose_stride=%lld is below a row's %d floats", who, (long long)pose_stride, nj * 3);
-        if (betas_stride < nb) throw_error("%s: betas_stride=%lld is below a row's %d floats", who, (long long)betas_stride, nb);
-        if (trans_stride < 3) throw_error("%s: trans_stride=%lld is below a row's 3 floats", who, (long long)trans_stride);
-        if (target_verts && target_verts_stride < nvo * 3)
-            throw_error("%s: target_verts_stride=%lld is below a row's %lld floats", who, (long long)target_verts_stride, (long long)(nvo * 3));
+        check_stride(who, "pose", pose_stride, nj * 3);
+        check_stride(who, "betas", betas_stride, nb);
+        check_stride(who, "trans", trans_stride, 3);
+        if (target_verts) check_stride(who, "target_verts", target_verts_stride, nvo * 3);
         if (vert_weight && vert_weight_stride != 0 && vert_weight_stride < nvo)
             throw_error("%s: vert_weight_stride=%lld is neither 0 (one shared row) nor at least a row's %lld floats", who, (long long)vert_weight_stride, (long long)nvo);
-        if (target_joints && target_joints_stride < (int64_t)nj * 3)
-            throw_error("%s: target_joints_stride=%lld is below a row's %d floats", who, (long long)target_joints_stride, nj * 3);
+        if (target_joints) check_stride(who, "target_joints", target_joints_stride, nj * 3);
         if (H && H_stride < n * n) throw_error("%s: H_stride=%lld is below a matrix's %lld floats", who, (long long)H_stride, (long long)(n * n));
-        if (g && g_stride < n) throw_error("%s: g_stride=%lld is below a row's %lld floats", who, (long long)g_stride, (long long)n);
+        if (g) check_stride(who, "g", g_stride, n);
         if (loss && loss_stride < 1) throw_error("%s: loss_stride=%lld (at least 1)", who, (long long)loss_stride);
         if (P == 0) return;
         if (!packed || !pose || !betas || !trans) throw_error("%s: null argument", who);
@@ -653,8 +591,8 @@ extern "C" int vanerf_mano_lm_solve(const float* M, int64_t M_stride, const floa
         if (n < 1 || n > LM_MAX_N) throw_error("%s: n=%d unknowns (1 .. %d)", who, n, LM_MAX_N);
         if (P < 0) throw_error("%s: P=%d systems (at least 0)", who, P);
         if (M_stride < (int64_t)n * n) throw_error("%s: M_stride=%lld is below a matrix's %d floats", who, (long long)M_stride, n * n);
-        if (g_stride < n) throw_error("%s: g_stride=%lld is below a row's %d floats", who, (long long)g_stride, n);
-        if (delta_stride < n) throw_error("%s: delta_stride=%lld is below a row's %d floats", who, (long long)delta_stride, n);
+        check_stride(who, "g", g_stride, n);
+        check_stride(who, "delta", delta_stride, n);
         if (P == 0) return;
         if (!M || !g || !delta || !ok) throw_error("%s: null argument", who);
         const size_t lds = ((size_t)n * (n | 1) + n) * sizeof(double);

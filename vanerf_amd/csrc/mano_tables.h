@@ -1,5 +1,6 @@
-// mano_tables.h -- what mano_skin.hip (the forward) and mano_skin_backward.hip share: the limits of a MANO-shaped model, the layout of the
-// buffer vanerf_mano_pack writes, and the small host-side helpers of both entries.  Host code only; the kernels take ManoTables by value.
+// mano_tables.h -- what mano_skin.hip (the forward), mano_skin_backward.hip and mano_skin_normal.hip share on the host: the limits of a
+// MANO-shaped model, the layout of the buffer vanerf_mano_pack writes, and the small helpers of their entries.  Host code only; the kernels
+// take ManoTables by value (the device code the three share is mano_forward.h).
 #pragma once
 #include "common.h"
 
@@ -74,6 +75,34 @@ inline void check_sizes(const char* who, int nv, int nj, int nb)
 
 struct IntList32 { int32_t v[MANO_MAX_NJ]; };
 struct IntList64 { int32_t v[MANO_MAX_RING]; };
+
+// The seal's ring as a kernel argument, checked; entries from n_ring on are 0 and every reader guards with u < n_ring.
+inline IntList64 ring_list(const char* who, const int32_t* ring, int n_ring, int nv)
+{
+    if (n_ring < 0 || n_ring > MANO_MAX_RING) throw_error("%s: n_ring=%d (0 = no seal .. %d)", who, n_ring, MANO_MAX_RING);
+    if (n_ring > 0 && !ring) throw_error("%s: null argument (ring with n_ring=%d)", who, n_ring);
+    IntList64 rg;
+    for (int u = 0; u < MANO_MAX_RING; ++u) rg.v[u] = 0;
+    for (int u = 0; u < n_ring; ++u) {
+        if (ring[u] < 0 || ring[u] >= nv) throw_error("%s: ring[%d]=%d names no vertex of nv=%d", who, u, ring[u], nv);
+        rg.v[u] = ring[u];
+    }
+    return rg;
+}
+
+inline void check_stride(const char* who, const char* what, int64_t stride, int64_t floats)
+{
+    if (stride < floats) throw_error("%s: %s_stride=%lld is below a row's %lld floats", who, what, (long long)stride, (long long)floats);
+}
+
+// A size query of the C ABI: the bytes `size()` returns, or its refusal as a negative error code.
+template <class F>
+inline int64_t size_query(F&& size)
+{
+    int64_t bytes = -1;
+    const int rc = guarded([&] { bytes = size(); });
+    return rc == VANERF_OK ? bytes : (int64_t)rc;
+}
 
 inline unsigned blocks_of(const char* who, int64_t n, int per)
 {

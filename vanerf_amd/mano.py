@@ -131,30 +131,62 @@ def _rows(t, cols, P, dev, what):
     return c_void_p(t.data_ptr()), (t.stride(0) if t.shape[0] > 1 else cols)
 
 
+def _rows_apart(t, n, P):
+    """Whether a (P, n, 3) tensor is anything but rows of n packed triples (the stride between the rows is free)."""
+    return P > 0 and n > 0 and (t.stride(2) != 1 or (n > 1 and t.stride(1) != 3) or (P > 1 and t.stride(0) < 3 * n))
+
+
 def _out_rows(t, n, P, dev, what):
     if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and tuple(t.shape) == (P, n, 3) and t.device == dev):
         raise ValueError(f"{what}: expected a fp32 device tensor ({P}, {n}, 3) on {dev} (no CPU fallback)")
-    if P > 0 and n > 0 and (t.stride(2) != 1 or (n > 1 and t.stride(1) != 3) or (P > 1 and t.stride(0) < 3 * n)):
+    if _rows_apart(t, n, P):
         raise ValueError(f"{what}: expected contiguous rows (strides {t.stride()})")
     return c_void_p(t.data_ptr()), (t.stride(0) if P > 1 else 3 * n)
 
 
-def _skin(model, pose, betas, trans, flat_hand_mean=False, seal=True, out=None):
-    """skin_hand without autograd: the checks and the one call into the library."""
+def _on_device(pose, betas, trans, shape=""):
     for t, what in ((pose, "pose"), (betas, "betas"), (trans, "trans")):
         if not torch.is_tensor(t) or not t.is_cuda:
-            raise ValueError(f"{what}: expected a fp32 device tensor (no CPU fallback)")
+            raise ValueError(f"{what}: expected a fp32 device tensor {shape}(no CPU fallback)")
+
+
+def _model_seal(model, seal):
+    """The model and seal check -> (nv + seal, the ring as the library takes it, its length)."""
     if not isinstance(model, ManoModel):
         raise ValueError("model: expected a ManoModel")
+    if seal and model.seal_ring is None:
+        raise ValueError("seal=True: the model carries no seal_ring")
+    return (model.nv + (1 if seal else 0), *_ring_arg(model.seal_ring if seal else None, model.nv))
+
+
+def _two_models(right, left, seal):
+    """The two-model check -> the vertex counts (nvr, nvl) of their outputs."""
+    if not (isinstance(right, ManoModel) and isinstance(left, ManoModel)):
+        raise ValueError("right, left: expected two ManoModels")
+    if right.device != left.device or right.nj != left.nj or right.nb != left.nb:
+        raise ValueError("right, left: expected models of the same nj and nb on one device")
+    return right.nv + (1 if seal else 0), left.nv + (1 if seal else 0)
+
+
+def _workspace(query, *sizes, dev):
+    """What `query(*sizes)` of the library asks for (a negative answer is its refusal), allocated on dev -> (pointer, bytes, the tensor to keep
+    alive).  Never empty, so that the pointer is one."""
+    nbytes = query(*sizes)
+    if nbytes < 0:
+        check(int(nbytes))
+    ws = torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=dev)
+    return c_void_p(ws.data_ptr()), nbytes, ws
+
+
+def _skin(model, pose, betas, trans, flat_hand_mean=False, seal=True, out=None):
+    """skin_hand without autograd: the checks and the one call into the library."""
+    _on_device(pose, betas, trans)
+    nvo, ring, n_ring = _model_seal(model, seal)
     dev = model.device
     pp, ps = _rows(pose, model.nj * 3, None, dev, "pose")
     P = pose.shape[0]
     bp, bs = _rows(betas, model.nb, P, dev, "betas")
     tp, ts = _rows(trans, 3, P, dev, "trans")
-    if seal and model.seal_ring is None:
-        raise ValueError("seal=True: the model carries no seal_ring")
-    ring, n_ring = _ring_arg(model.seal_ring if seal else None, model.nv)
-    nvo = model.nv + (1 if seal else 0)
     with torch.cuda.device(dev):
         if out is None:
             verts, joints = torch.empty(P, nvo, 3, dtype=torch.float32, device=dev), torch.empty(P, model.nj, 3, dtype=torch.float32, device=dev)
@@ -162,12 +194,9 @@ def _skin(model, pose, betas, trans, flat_hand_mean=False, seal=True, out=None):
             verts, joints = out
         vp, vs = _out_rows(verts, nvo, P, dev, "out[0] (verts)")
         jp, js = _out_rows(joints, model.nj, P, dev, "out[1] (joints)")
-        nbytes = lib.vanerf_mano_workspace_bytes(model.nj, P)
-        if nbytes < 0:
-            check(int(nbytes))
-        ws = torch.empty(max(int(nbytes), 4), dtype=torch.uint8, device=dev)
+        wp, nbytes, _ws = _workspace(lib.vanerf_mano_workspace_bytes, model.nj, P, dev=dev)
         check(lib.vanerf_mano_skin(c_void_p(model.packed.data_ptr()), model.nv, model.nj, model.nb, pp, ps, bp, bs, tp, ts, P, int(bool(flat_hand_mean)),
-                                   ring, n_ring, c_void_p(ws.data_ptr()), nbytes, vp, vs, jp, js, _stream()))
+                                   ring, n_ring, wp, nbytes, vp, vs, jp, js, _stream()))
     return verts, joints
 
 
@@ -182,7 +211,7 @@ def _grad_rows(t, n, P, dev, what):
         return None, None, 3 * n
     if t.dtype != torch.float32 or tuple(t.shape) != (P, n, 3) or t.device != dev:
         raise ValueError(f"{what}: expected a fp32 tensor ({P}, {n}, 3) on {dev}, got {t.dtype} {tuple(t.shape)} on {t.device}")
-    if P > 0 and n > 0 and (t.stride(2) != 1 or (n > 1 and t.stride(1) != 3) or (P > 1 and t.stride(0) < 3 * n)):
+    if _rows_apart(t, n, P):
         t = t.contiguous()
     return t, c_void_p(t.data_ptr()), (t.stride(0) if P > 1 else 3 * n)
 
@@ -194,10 +223,7 @@ def _skin_backward(model, pose, betas, flat_hand_mean, seal, grad_verts, grad_jo
     dev, P = model.device, pose.shape[0]
     pp, ps = _rows(pose, model.nj * 3, None, dev, "pose")
     bp, bs = _rows(betas, model.nb, P, dev, "betas")
-    if seal and model.seal_ring is None:
-        raise ValueError("seal=True: the model carries no seal_ring")
-    ring, n_ring = _ring_arg(model.seal_ring if seal else None, model.nv)
-    nvo = model.nv + (1 if seal else 0)
+    nvo, ring, n_ring = _model_seal(model, seal)
     with torch.cuda.device(dev):
         gv, gvp, gvs = _grad_rows(grad_verts, nvo, P, dev, "grad_verts")
         gj, gjp, gjs = _grad_rows(grad_joints, model.nj, P, dev, "grad_joints")
@@ -212,12 +238,9 @@ def _skin_backward(model, pose, betas, flat_hand_mean, seal, grad_verts, grad_jo
             g = out[i] if out is not None and out[i] is not None else torch.empty(P, cols, dtype=torch.float32, device=dev)
             grads.append(g)
             ptrs += list(_rows(g, cols, P, dev, what))
-        nbytes = lib.vanerf_mano_skin_backward_workspace_bytes(model.nv, model.nj, model.nb, P)
-        if nbytes < 0:
-            check(int(nbytes))
-        ws = torch.empty(max(int(nbytes), 8), dtype=torch.uint8, device=dev)
+        wp, nbytes, _ws = _workspace(lib.vanerf_mano_skin_backward_workspace_bytes, model.nv, model.nj, model.nb, P, dev=dev)
         check(lib.vanerf_mano_skin_backward(c_void_p(model.packed.data_ptr()), model.nv, model.nj, model.nb, pp, ps, bp, bs, P, int(bool(flat_hand_mean)),
-                                            ring, n_ring, gvp, gvs, gjp, gjs, c_void_p(ws.data_ptr()), nbytes, *ptrs, _stream()))
+                                            ring, n_ring, gvp, gvs, gjp, gjs, wp, nbytes, *ptrs, _stream()))
     return tuple(grads)
 
 
@@ -289,20 +312,12 @@ def skin_hand(model, pose, betas, trans, flat_hand_mean=False, seal=True, out=No
 
 def _skin_two(right, left, pose, betas, trans, flat_hand_mean=False, seal=True, out=None):
     """skin_two_hands without autograd."""
-    for t, what in ((pose, "pose"), (betas, "betas"), (trans, "trans")):
-        if not torch.is_tensor(t) or not t.is_cuda:
-            raise ValueError(f"{what}: expected a fp32 device tensor (P, 2, .) (no CPU fallback)")
-    if not (isinstance(right, ManoModel) and isinstance(left, ManoModel)):
-        raise ValueError("right, left: expected two ManoModels")
-    if right.device != left.device or right.nj != left.nj or right.nb != left.nb:
-        raise ValueError("right, left: expected models of the same nj and nb on one device")
+    _on_device(pose, betas, trans, "(P, 2, .) ")
+    nvr, nvl = _two_models(right, left, seal)
     for t, c, what in ((pose, right.nj * 3, "pose"), (betas, right.nb, "betas"), (trans, 3, "trans")):
-        if not torch.is_tensor(t) or not t.is_cuda:
-            raise ValueError(f"{what}: expected a fp32 device tensor (P, 2, {c}) (no CPU fallback)")
         if t.dim() != 3 or t.shape[1:] != (2, c) or t.shape[0] != pose.shape[0]:
             raise ValueError(f"{what}: expected a tensor (P, 2, {c}), got {tuple(t.shape)}")
     P, dev = pose.shape[0], right.device
-    nvr, nvl = right.nv + (1 if seal else 0), left.nv + (1 if seal else 0)
     if out is None:
         with torch.cuda.device(dev):
             out = torch.empty(P, nvr + nvl, 3, dtype=torch.float32, device=dev), torch.empty(P, 2 * right.nj, 3, dtype=torch.float32, device=dev)
@@ -414,36 +429,45 @@ def _fit(forward, backward, params, target_verts, target_joints, vert_weight, fu
             p.addcdiv_(m, (v.sqrt() / c2 ** 0.5).add_(ADAM_EPS), value=-(lr * ratio) / c1)
 
 
+def _targets(model, nvo, P, target_verts, target_joints, vert_weight, rows):
+    """The checks of the targets and of where the weights are that the fits and skin_normal_equations share -> the targets detached and
+    contiguous, or None.  `rows` is how the first refusal writes the count of poses; the shape of the weights is the caller's to check."""
+    if target_verts is None and target_joints is None:
+        raise ValueError("target_verts, target_joints: expected at least one target")
+    got = []
+    for t, n, what in ((target_verts, nvo, "target_verts"), (target_joints, model.nj, "target_joints")):
+        if t is not None:
+            if not torch.is_tensor(t) or not t.is_cuda:
+                raise ValueError(f"{what}: expected a fp32 device tensor ({rows}, {n}, 3) (no CPU fallback)")
+            if t.dtype != torch.float32 or tuple(t.shape) != (P, n, 3) or t.device != model.device:
+                raise ValueError(f"{what}: expected a fp32 tensor ({P}, {n}, 3) on {model.device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+            t = t.detach().contiguous()
+        got.append(t)
+    if vert_weight is not None and (not torch.is_tensor(vert_weight) or not vert_weight.is_cuda):
+        raise ValueError(f"vert_weight: expected a device tensor ({nvo},) or ({P}, {nvo}) (no CPU fallback)")
+    return got
+
+
+def _fit_result(params, verts, joints, tv, tj, **more):
+    """The dict fit_hand returns: rms from the distances of the vertices (of the joints when there is no vertex target) to the target."""
+    d = (verts - tv) if tv is not None else (joints - tj)
+    rms = (d * d).sum(-1).mean(-1).sqrt()
+    return {"pose": params[0], "betas": params[1], "trans": params[2], "verts": verts, "joints": joints, "rms": rms, **more}
+
+
 def _fit_setup(model, target_verts, target_joints, init, steps, vert_weight, prior, flat_hand_mean, seal, count="steps"):
     """The checks and the start that fit_hand and fit_hand_lm share -> (P, nvo, tv, tj, w, params, offset): the targets detached and contiguous,
     the weights as (nvo, 1) or (P, nvo, 1) or None, the three parameter tensors (clones of init, or the rigid start) and what flat_hand_mean=False
     adds to pose[3:] (0.0 or hands_mean on the device).  `count` is what the caller calls `steps` in its refusal."""
-    if not isinstance(model, ManoModel):
-        raise ValueError("model: expected a ManoModel")
-    if target_verts is None and target_joints is None:
-        raise ValueError("target_verts, target_joints: expected at least one target")
-    dev = model.device
-    if seal and model.seal_ring is None:
-        raise ValueError("seal=True: the model carries no seal_ring")
-    nvo = model.nv + (1 if seal else 0)
+    nvo, dev = _model_seal(model, seal)[0], model.device
     first = target_verts if target_verts is not None else target_joints
     P = first.shape[0] if torch.is_tensor(first) and first.dim() == 3 else None
-    for t, n, what in ((target_verts, nvo, "target_verts"), (target_joints, model.nj, "target_joints")):
-        if t is None:
-            continue
-        if not torch.is_tensor(t) or not t.is_cuda:
-            raise ValueError(f"{what}: expected a fp32 device tensor (P, {n}, 3) (no CPU fallback)")
-        if t.dtype != torch.float32 or t.dim() != 3 or tuple(t.shape[1:]) != (n, 3) or t.shape[0] != P or t.device != dev:
-            raise ValueError(f"{what}: expected a fp32 tensor ({P}, {n}, 3) on {dev}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+    tv, tj = _targets(model, nvo, P, target_verts, target_joints, vert_weight, "P")
     if len(prior) != 2 or steps < 0:
         raise ValueError(f"prior: expected (pose weight, betas weight); {count}: at least 0")
     with torch.cuda.device(dev), torch.no_grad():
-        tv = None if target_verts is None else target_verts.detach().contiguous()
-        tj = None if target_joints is None else target_joints.detach().contiguous()
         w = None
         if vert_weight is not None:
-            if not torch.is_tensor(vert_weight) or not vert_weight.is_cuda:
-                raise ValueError(f"vert_weight: expected a device tensor ({nvo},) or ({P}, {nvo}) (no CPU fallback)")
             if tuple(vert_weight.shape) not in ((nvo,), (P, nvo)):
                 raise ValueError(f"vert_weight: expected ({nvo},) or ({P}, {nvo}), got {tuple(vert_weight.shape)}")
             w = vert_weight.detach().to(dev, torch.float32)[..., None]
@@ -491,19 +515,13 @@ def fit_hand(model, target_verts=None, target_joints=None, init=None, steps=300,
         if P > 0:
             _fit(forward, backward, params, tv, tj, w, offset, steps, lr, prior)
         forward(*params)
-        d = (verts - tv) if tv is not None else (joints - tj)
-        rms = (d * d).sum(-1).mean(-1).sqrt()
-    return {"pose": params[0], "betas": params[1], "trans": params[2], "verts": verts, "joints": joints, "rms": rms}
+        return _fit_result(params, verts, joints, tv, tj)
 
 
 def _fit_two(fit_one, stacked, right, left, target_verts, target_joints, init, vert_weight, seal):
     """What fit_two_hands and fit_two_hands_lm share: the checks, the two fits one after the other -- fit_one(model, target_verts, target_joints,
     init, vert_weight) on the halves -- and the stacking; `stacked` names the per-hand results that become (P, 2, ...)."""
-    if not (isinstance(right, ManoModel) and isinstance(left, ManoModel)):
-        raise ValueError("right, left: expected two ManoModels")
-    if right.device != left.device or right.nj != left.nj or right.nb != left.nb:
-        raise ValueError("right, left: expected models of the same nj and nb on one device")
-    nvr, nvl, nj = right.nv + (1 if seal else 0), left.nv + (1 if seal else 0), right.nj
+    (nvr, nvl), nj = _two_models(right, left, seal), right.nj
     if not torch.is_tensor(target_verts) or not target_verts.is_cuda:
         raise ValueError(f"target_verts: expected a fp32 device tensor (P, {nvr + nvl}, 3) (no CPU fallback)")
     if target_verts.dim() != 3 or tuple(target_verts.shape[1:]) != (nvr + nvl, 3):
@@ -545,45 +563,29 @@ def _skin_normal(model, pose, betas, trans, tv, tj, w, flat_hand_mean, seal, out
     pp, ps = _rows(pose, model.nj * 3, None, dev, "pose")
     bp, bs = _rows(betas, model.nb, P, dev, "betas")
     tp, ts = _rows(trans, 3, P, dev, "trans")
-    ring, n_ring = _ring_arg(model.seal_ring if seal else None, model.nv)
-    nvo = model.nv + (1 if seal else 0)
+    nvo, ring, n_ring = _model_seal(model, seal)
     with torch.cuda.device(dev):
         if out is None:
             out = (torch.empty(P, n, n, dtype=torch.float32, device=dev), torch.empty(P, n, dtype=torch.float32, device=dev),
                    torch.empty(P, dtype=torch.float32, device=dev))
         ptr = lambda t: None if t is None else c_void_p(t.data_ptr())  # noqa: E731
-        nbytes = lib.vanerf_mano_skin_normal_workspace_bytes(model.nv, model.nj, model.nb, P)
-        if nbytes < 0:
-            check(int(nbytes))
-        ws = torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=dev)
+        wp, nbytes, _ws = _workspace(lib.vanerf_mano_skin_normal_workspace_bytes, model.nv, model.nj, model.nb, P, dev=dev)
         check(lib.vanerf_mano_skin_normal(c_void_p(model.packed.data_ptr()), model.nv, model.nj, model.nb, pp, ps, bp, bs, tp, ts, P, int(bool(flat_hand_mean)),
                                           ring, n_ring, ptr(tv), nvo * 3, ptr(w), 0 if w is None or w.dim() == 1 else nvo, ptr(tj), model.nj * 3,
-                                          c_void_p(ws.data_ptr()), nbytes, ptr(out[0]), n * n, ptr(out[1]), n, ptr(out[2]), 1, _stream()))
+                                          wp, nbytes, ptr(out[0]), n * n, ptr(out[1]), n, ptr(out[2]), 1, _stream()))
     return out
 
 
-def _normal_targets(model, P, target_verts, target_joints, vert_weight, seal):
+def _normal_targets(model, nvo, P, target_verts, target_joints, vert_weight):
     """The targets and weights of skin_normal_equations, checked -> contiguous fp32 tensors or None."""
-    dev, nvo = model.device, model.nv + (1 if seal else 0)
-    if target_verts is None and target_joints is None:
-        raise ValueError("target_verts, target_joints: expected at least one target")
-    got = []
-    for t, n, what in ((target_verts, nvo, "target_verts"), (target_joints, model.nj, "target_joints")):
-        if t is not None:
-            if not torch.is_tensor(t) or not t.is_cuda:
-                raise ValueError(f"{what}: expected a fp32 device tensor ({P}, {n}, 3) (no CPU fallback)")
-            if t.dtype != torch.float32 or tuple(t.shape) != (P, n, 3) or t.device != dev:
-                raise ValueError(f"{what}: expected a fp32 tensor ({P}, {n}, 3) on {dev}, got {t.dtype} {tuple(t.shape)} on {t.device}")
-            t = t.detach().contiguous()
-        got.append(t)
+    dev = model.device
+    tv, tj = _targets(model, nvo, P, target_verts, target_joints, vert_weight, P)
     w = None
     if vert_weight is not None:
-        if not torch.is_tensor(vert_weight) or not vert_weight.is_cuda:
-            raise ValueError(f"vert_weight: expected a device tensor ({nvo},) or ({P}, {nvo}) (no CPU fallback)")
         if target_verts is None or tuple(vert_weight.shape) not in ((nvo,), (P, nvo)) or vert_weight.device != dev:
             raise ValueError(f"vert_weight: expected ({nvo},) or ({P}, {nvo}) on {dev} beside target_verts, got {tuple(vert_weight.shape)}")
         w = vert_weight.detach().to(torch.float32).contiguous()
-    return got[0], got[1], w
+    return tv, tj, w
 
 
 def skin_normal_equations(model, pose, betas, trans, target_verts=None, target_joints=None, vert_weight=None, flat_hand_mean=False, seal=True):
@@ -591,15 +593,10 @@ def skin_normal_equations(model, pose, betas, trans, target_verts=None, target_j
     ordered x = (pose, betas, trans), n = 3 nj + nb + 3, the residuals r = (verts - target_verts, joints - target_joints) (either target may be
     None), J = dr/dx and W = (vert_weight / (nv + seal), 1 / nj): -> H = J^T W J (P, n, n), symmetric bit for bit, g = J^T W r (P, n) and
     loss = r^T W r (P), fp32 device tensors.  fit_hand's loss is loss + its priors and the loss's gradient is 2 g."""
-    for t, what in ((pose, "pose"), (betas, "betas"), (trans, "trans")):
-        if not torch.is_tensor(t) or not t.is_cuda:
-            raise ValueError(f"{what}: expected a fp32 device tensor (no CPU fallback)")
-    if not isinstance(model, ManoModel):
-        raise ValueError("model: expected a ManoModel")
-    if seal and model.seal_ring is None:
-        raise ValueError("seal=True: the model carries no seal_ring")
+    _on_device(pose, betas, trans)
+    nvo = _model_seal(model, seal)[0]
     _rows(pose, model.nj * 3, None, model.device, "pose")
-    tv, tj, w = _normal_targets(model, pose.shape[0], target_verts, target_joints, vert_weight, seal)
+    tv, tj, w = _normal_targets(model, nvo, pose.shape[0], target_verts, target_joints, vert_weight)
     return _skin_normal(model, pose.detach(), betas.detach(), trans.detach(), tv, tj, w, flat_hand_mean, seal)
 
 
@@ -661,9 +658,7 @@ def fit_hand_lm(model, target_verts=None, target_joints=None, init=None, iterati
                 accepted += take
         params = [t.contiguous() for t in split(x)]
         verts, joints = _skin(model, *params, flat_hand_mean, seal)
-        d = (verts - tv) if tv is not None else (joints - tj)
-        rms = (d * d).sum(-1).mean(-1).sqrt()
-    return {"pose": params[0], "betas": params[1], "trans": params[2], "verts": verts, "joints": joints, "rms": rms, "damping": lam, "accepted": accepted}
+        return _fit_result(params, verts, joints, tv, tj, damping=lam, accepted=accepted)
 
 
 def fit_two_hands_lm(right, left, target_verts, target_joints=None, init=None, iterations=10, damping=1e-3, vert_weight=None, prior=(0.0, 0.0),
